@@ -8,15 +8,21 @@ N = 1 scans config 2's 1M documents; N > 1 scans config 3's 10M documents
 10M / N (strong scaling).  ``--total-docs T`` fixes another total,
 ``--docs-per-gpu D`` gives every rank D documents (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Rank 0 prints one JSON line.  ``roofline`` prices the scan kernel against
 HBM (8.0 TB/s) with the algorithmic bytes = sum of UTF-8 bytes of every
 article's text and title; the kernel time is the HIP-event
-time of the scan kernel on the stream it runs on.  ``cpu_baseline`` times the
-oracle's CPU port (oracle/cpu_port.py) on a bounded sample of the same
-corpus, rank 0 at N = 1 only.
+time of the scan kernel on the stream it runs on.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+``--dump-outputs DIR`` also writes what the last timed step computed (the hit
+records a caller of the scan receives, see ``dump_match_outputs``) as
+``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared
+output for output.  ``--full`` adds ``cpu_baseline``: the oracle's CPU port
+(oracle/cpu_port.py) timed on a bounded sample of the same corpus, rank 0 at
+N = 1 only (null without ``--full``).
 """
 from __future__ import annotations
 
@@ -46,11 +52,17 @@ def _parse():
                     help='documents of the whole job, split in contiguous shards (default: 1M = config 2 at N = 1, '
                          '10M = config 3 at N > 1)')
     ap.add_argument('--seed', type=int, default=20250905)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run what the headline figure does not need: the CPU port '
+                         'baseline (cpu_baseline, sized by --cpu-sample / --cpu-procs)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, a seeded '
+                         'sample where the whole output exceeds 64 MB)')
     ap.add_argument('--cpu-sample', type=int, default=10000,
-                    help='docs of the same corpus timed on the CPU port of the reference loop (0 = skip)')
+                    help='--full: docs of the same corpus timed on the CPU port of the reference loop (0 = skip)')
     ap.add_argument('--cpu-procs', type=int, default=0,
-                    help='CPU port processes (0 = the CPUs this process may use: affinity, capped by the cgroup '
-                         'CPU quota; the reference uses Pool(cpu_count()))')
+                    help='--full: CPU port processes (0 = the CPUs this process may use: affinity, capped by the '
+                         'cgroup CPU quota; the reference uses Pool(cpu_count()))')
     ap.add_argument('--lib-variant', default=None,
                     help='time lib/libkwmatch_<TAG>.so (a tuning build, advanced_scrapper_amd/build.py) instead of '
                          'the default library; the line names the library and its sha256 either way')
@@ -67,7 +79,10 @@ def _parse():
                     help='scans in flight per GPU: 2 = two libkwmatch handles on two streams, step i + 1 is '
                          'launched before step i\'s hits are read (its filter overlaps step i\'s latency-bound '
                          'epilogue and task kernels); 1 = one scan at a time')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def _launch_ranks(args) -> int:
@@ -145,6 +160,57 @@ def hits_digest(hits) -> str:
     x = x * -0x40A7B892E31B1A47
     x = x ^ ((x >> 29) & 0x7FFFFFFFF)
     return f'{int(x.sum().item()) & 0xFFFFFFFFFFFFFFFF:016x}'
+
+
+# --dump-outputs: at most 64 MB in all (40 MB of sampled records + 16 MB of per-document counts; 32 MB of codes)
+DUMP_SAMPLE_DOCS = 200_000
+DUMP_MAX_RECORDS = 1_250_000
+DUMP_COUNT_DOCS = 4_000_000
+DUMP_SAMPLE_ROWS = 8_000_000
+
+
+def dump_match_outputs(out_dir: str, hits, hits_total: int, total_docs: int, seed: int) -> None:
+    """What the last timed step computed, as .npy files a run of another build can be compared with.
+
+    ``hits`` = its [n, 4] records (doc, pattern, pos, field; global document ids) or None when the step
+    exchanged counts only.  The library leaves the record order open, so the records are written sorted by
+    (doc, field, pos, pattern):
+    * hits_total.npy    float64 [1]: records of the whole job;
+    * hits_per_doc.npy  float32 [min(total_docs, 4M)]: records of each of the first documents;
+    * hits_sample.npy   float64 [m, 4]: every record of a sample of 200 000 documents chosen from the seed
+      alone (all documents of a smaller job), the first 1.25M of them in sorted order."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'hits_total.npy'), np.asarray([hits_total], dtype=np.float64))
+    if hits is None:
+        return
+    h = hits.to(torch.int64) & 0xFFFFFFFF
+    doc = h[:, 0]
+    n_cnt = min(total_docs, DUMP_COUNT_DOCS)
+    per_doc = torch.bincount(doc[doc < n_cnt], minlength=n_cnt)
+    np.save(os.path.join(out_dir, 'hits_per_doc.npy'), per_doc.cpu().numpy().astype(np.float32))
+    keep = np.ones(total_docs, dtype=bool)
+    if total_docs > DUMP_SAMPLE_DOCS:
+        keep[:] = False
+        keep[np.random.default_rng(seed).choice(total_docs, DUMP_SAMPLE_DOCS, replace=False)] = True
+    keep = torch.from_numpy(keep).to(h.device)
+    inside = doc < total_docs
+    sel = h[inside & keep[doc.clamp(max=max(total_docs - 1, 0))]].cpu().numpy()
+    sel = sel[np.lexsort((sel[:, 1], sel[:, 2], sel[:, 3], sel[:, 0]))][:DUMP_MAX_RECORDS]
+    np.save(os.path.join(out_dir, 'hits_sample.npy'), sel.astype(np.float64))
+
+
+def dump_dedup_outputs(out_dir: str, code, counts, seed: int) -> None:
+    """The last timed kw_dedup_run's outputs: counts.npy (float64 [4], GpuUrlDedup.counts) and codes.npy
+    (float32: the KW_URL_* code of every row, or of 8M rows drawn from the seed alone where there are more)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'counts.npy'), np.asarray(counts, dtype=np.float64))
+    n = int(code.shape[0])
+    if n > DUMP_SAMPLE_ROWS:
+        rows = np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE_ROWS))
+        code = code[torch.from_numpy(rows).to(code.device)]
+    np.save(os.path.join(out_dir, 'codes.npy'), code.cpu().numpy().astype(np.float32))
 
 
 def host_cpus() -> dict:
@@ -300,6 +366,10 @@ def main():
     else:
         digest = None
     st = m.stats()
+    if args.dump_outputs and rank == 0:
+        # the records of the last timed step: the handle that scanned it (N = 1), rank 0's gathered ones (N > 1)
+        last_hits = ms[(args.steps - 1) % len(ms)].hits_device() if comm is None else last['gathered']
+        dump_match_outputs(args.dump_outputs, last_hits, int(sum(counts)), total_docs, args.seed)
     if comm is not None:
         comm.close()
     if rank != 0:
@@ -310,7 +380,7 @@ def main():
     scan_avg = kavg['filter']         # the kernel that streams every article byte (HIP events on its stream)
     achieved = local_bytes / (scan_avg * 1e-3) / 1e9
     cpu = None
-    if world == 1 and args.cpu_sample > 0:
+    if args.full and world == 1 and args.cpu_sample > 0:
         # the port walks every name occurrence per field: config 4's 52k names take ~1 s per article
         n_cpu = args.cpu_sample if args.workload == 'match' else min(args.cpu_sample, 64)
         cpu = cpu_baseline(processed, corpus, n_cpu, args.cpu_procs)
@@ -410,7 +480,7 @@ def bench_dedup(args):
     kt = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        g.run(d_a, d_o, rows.n)
+        code = g.run(d_a, d_o, rows.n)
         kt.append(g.last_ms())
     torch.cuda.synchronize()
     if world > 1:
@@ -426,13 +496,15 @@ def bench_dedup(args):
     counts = g.counts()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_dedup_outputs(args.dump_outputs, code, counts, args.seed)
     k = np.mean(np.asarray(kt), axis=0)
     names = ('transform_insert', 'slow_rows', 'decide', 'compact', 'total')
     kms = {a: round(float(b), 4) for a, b in zip(names, k)}
     transform_gbs = rows.n_bytes / (kms['transform_insert'] * 1e-3) / 1e9
     lib_id = _native.lib_identity()
     cpu = None
-    if world == 1 and args.cpu_sample > 0:
+    if args.full and world == 1 and args.cpu_sample > 0:
         cpu = cpu_baseline_dedup(rows, min(n, 2_000_000))
     out = {
         'metric': 'CDX URL dedup GB/s (URL bytes + 8 B offsets), bit-exact vs pandas drop_duplicates keep-first',

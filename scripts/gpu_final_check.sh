@@ -1,8 +1,9 @@
 #!/bin/bash
-# every -m gpu test, smoke(), and the default bench line (the driver's round-end sequence)
+# every -m gpu test, smoke(), and the default bench line with its CPU baseline (--full) (the driver's round-end sequence)
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 500 --timeout-method thread > gpurun_out/final_tests.log 2>&1 || exit $?
-timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/final_smoke.log 2>&1 || exit $?
-timeout -k 10 300 python bench.py > gpurun_out/final_bench.log 2>&1
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 500 --timeout-method thread > $OUT/final_tests.log 2>&1 || exit $?
+timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/final_smoke.log 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full > $OUT/final_bench.log 2>&1
