@@ -229,6 +229,93 @@ struct FastBuild {
     std::vector<uint64_t> use_wild;                 // per use: wildcard positions of an RXM string
 };
 
+// What a (checked) regex program holds, for the choice of its engine and of its documents' route.
+struct RxShape {
+    uint32_t npos = 0;      // consuming atoms (LIT / ANY / SET rows)
+    uint32_t frames = 0;    // repeats + branches (rx_match's stack frames)
+    bool quant = false, at = false, wordb = false, alt = false, nopos = false;
+    bool set_ext = false;   // a set with a member >= 128
+    bool lit_ext = false;   // a literal >= 128
+    // quantifier-free, <= 64 positions, no assertion, no branch, ASCII-only sets: the shift-and search
+    bool fixed() const { return !quant && !at && !alt && !nopos && !set_ext && npos >= 1 && npos <= 64; }
+};
+
+// Checks rows [b, e) of a regex program (include/kwmatch.h, KW_RX_*) and describes it; false: malformed.
+bool rx_check(const int32_t *rows, int64_t b, int64_t e, RxShape &S, int64_t &minlen)
+{
+    auto unit = [&](int64_t &a, int64_t end, int64_t &mn) -> bool {   // one LIT / ANY / SET (with its rows) / AT at a
+        const int32_t *t = rows + 4 * a;
+        const int op = t[0] & 0xFF;
+        if (t[0] & ~(0xFF | KW_RX_LAZY)) return false;
+        if (op == KW_RX_AT) {
+            if (t[0] != KW_RX_AT || t[1] < KW_AT_BOS || t[1] > KW_AT_NWORD || t[2] != 0 || t[3] != 0) return false;
+            S.at = true;
+            S.wordb |= t[1] == KW_AT_WORD || t[1] == KW_AT_NWORD;
+            ++a;
+            return true;
+        }
+        if (op != KW_RX_LIT && op != KW_RX_ANY && op != KW_RX_SET) return false;
+        if (t[2] < 0 || (t[3] >= 0 && t[3] < t[2]) || t[3] < -1) return false;
+        const bool rep = !(t[2] == 1 && t[3] == 1);
+        if ((t[0] & KW_RX_LAZY) && t[3] == t[2]) return false;
+        if (rep) { S.quant = true; ++S.frames; }
+        mn += t[2];
+        ++S.npos;
+        if (op == KW_RX_LIT) {
+            if (t[1] < 0 || t[1] > 0x10FFFF) return false;
+            S.lit_ext |= t[1] >= 128;
+        }
+        ++a;
+        if (op == KW_RX_SET) {
+            const int64_t R = t[1];
+            if (R < 0 || R > KW_RX_MAX_RANGES || a + R > end) return false;
+            int64_t prev = -1;
+            for (int64_t k = 0; k < R; ++k, ++a) {
+                const int32_t *r = rows + 4 * a;
+                if (r[0] != KW_RX_RANGE || r[1] <= prev || r[2] < r[1] || r[2] > 0x10FFFF || r[3] != 0) return false;
+                prev = r[2];
+                S.set_ext |= r[2] >= 128;
+            }
+        }
+        return true;
+    };
+    S = RxShape();
+    minlen = 0;
+    if (e - b == 1 && rows[4 * b] == KW_RX_NOPOS) {
+        S.nopos = true;
+        minlen = 1;
+        return rows[4 * b + 1] == 0 && rows[4 * b + 2] == 0 && rows[4 * b + 3] == 0;
+    }
+    for (int64_t a = b; a < e;) {
+        const int32_t *t = rows + 4 * a;
+        if (t[0] != KW_RX_ALT) {
+            if (!unit(a, e, minlen)) return false;
+            continue;
+        }
+        const int64_t arms = t[1], end = a + 1 + (int64_t)t[2];
+        if (arms < 2 || t[2] < arms || t[3] != 0 || end > e) return false;
+        S.alt = true;
+        ++S.frames;
+        ++a;
+        int64_t best = INT64_MAX;
+        for (int64_t k = 0; k < arms; ++k) {
+            if (a >= end) return false;
+            const int32_t *r = rows + 4 * a;
+            const int64_t aend = a + 1 + (int64_t)r[1];
+            if (r[0] != KW_RX_ARM || r[1] < 0 || aend > end || a + (int64_t)r[2] != end || r[3] != 0) return false;
+            ++a;
+            int64_t mn = 0;
+            while (a < aend)
+                if (!unit(a, aend, mn)) return false;
+            if (a != aend) return false;
+            best = std::min(best, mn);
+        }
+        if (a != end) return false;
+        minlen += best;
+    }
+    return true;
+}
+
 // rarest 4-byte window inside bytes [lo, hi) (hi - lo >= 4); returns its start
 size_t rarest4(const QStats &Q, const uint8_t *s, size_t lo, size_t hi, size_t max_start)
 {
@@ -244,7 +331,8 @@ size_t rarest4(const QStats &Q, const uint8_t *s, size_t lo, size_t hi, size_t m
 int build_fast(FastBuild &B, const QStats &Q, int n_pat, const uint8_t *pat_bytes, const int64_t *pat_off,
                const std::vector<std::vector<uint32_t>> &cps, const std::vector<std::vector<uint32_t>> &tcps,
                const std::vector<uint32_t> &pat_info,
-               const std::vector<int4> &atoms, const std::vector<uint32_t> &rxo, std::string &err)
+               const std::vector<int4> &atoms, const std::vector<uint32_t> &rxo, const std::vector<RxShape> &shapes,
+               std::string &err)
 {
     struct Use { uint32_t pat, i0, i1; uint32_t rxs = 0xFFFFFFFFu; uint64_t wild = 0; };   // rxs: RXM string offset
     std::unordered_map<std::string, uint32_t> aid;
@@ -299,44 +387,50 @@ int build_fast(FastBuild &B, const QStats &Q, int n_pat, const uint8_t *pat_byte
         // positions: literal search, or the regex engine after the decision
         if (rxo[i + 1] > rxo[i]) {
             B.rxk[i] = RXK_REGEX;
-            // quantifier-free programs of <= 64 atoms take the shift-and search
-            bool fixed = rxo[i + 1] - rxo[i] <= 64;
-            for (uint32_t a = rxo[i]; a < rxo[i + 1] && fixed; ++a) fixed = atoms[a].z == 1 && atoms[a].w == 1;
-            if (fixed) {
+            // quantifier-free programs of <= 64 positions without assertions and branches, whose sets hold ASCII
+            // members only, take the shift-and search (a set or-s its bit into several of the 128 rows)
+            if (shapes[i].fixed()) {
                 const uint32_t r = (uint32_t)B.rxf_len.size();
+                const uint32_t L = shapes[i].npos;
                 B.rxf_idx[i] = (int32_t)r;
-                B.rxf_len.push_back(rxo[i + 1] - rxo[i]);
+                B.rxf_len.push_back(L);
                 uint64_t any = 0;
                 std::vector<std::pair<uint32_t, uint64_t>> ext;
                 B.rxf_pm.resize((size_t)(r + 1) * 128, 0);
-                for (uint32_t a = rxo[i]; a < rxo[i + 1]; ++a) {
-                    const uint64_t bit = 1ull << (a - rxo[i]);
-                    if (atoms[a].x == KW_RX_ANY) { any |= bit; continue; }
+                // the RXM string: the program as bytes with '.' wildcards (literal + '.' programs over ASCII only)
+                bool ascii_prog = true;
+                std::string rs(L, '\0');
+                uint64_t wild = 0;
+                uint32_t k = 0;
+                for (uint32_t a = rxo[i]; a < rxo[i + 1]; ++a, ++k) {
+                    const uint64_t bit = 1ull << k;
+                    const int op = atoms[a].x & 0xFF;
+                    if (op == KW_RX_ANY) { any |= bit; wild |= bit; continue; }
+                    if (op == KW_RX_SET) {
+                        ascii_prog = false;
+                        for (int32_t q = 1; q <= atoms[a].y; ++q)
+                            for (int32_t c = atoms[a + q].y; c <= atoms[a + q].z && c < 128; ++c)
+                                B.rxf_pm[(size_t)r * 128 + c] |= bit;
+                        a += (uint32_t)atoms[a].y;
+                        continue;
+                    }
                     const uint32_t c = (uint32_t)atoms[a].y;
+                    if (c >= 128u || c == 0) ascii_prog = false;
+                    rs[k] = (char)c;
                     if (c < 128) { B.rxf_pm[(size_t)r * 128 + c] |= bit; continue; }
-                    size_t k = 0;
-                    while (k < ext.size() && ext[k].first != c) ++k;
-                    if (k == ext.size()) ext.emplace_back(c, 0);
-                    ext[k].second |= bit;
+                    size_t e = 0;
+                    while (e < ext.size() && ext[e].first != c) ++e;
+                    if (e == ext.size()) ext.emplace_back(c, 0);
+                    ext[e].second |= bit;
                 }
                 for (uint32_t c = 0; c < 128; ++c)
                     if (c != '\n') B.rxf_pm[(size_t)r * 128 + c] |= any;   // '.' matches anything but '\n'
                 B.rxf_any.push_back(any);
                 B.rxf_ext_off.push_back((uint32_t)B.rxf_ext_cp.size());
                 for (auto &e : ext) { B.rxf_ext_cp.push_back(e.first); B.rxf_ext_mask.push_back(e.second); }
-                // an RXM use: the program as a byte string with '.' wildcards (ASCII atoms only), anchored at
-                // its rarest 4-byte window of literals; the probe's RXM items are then exactly the program's
-                // matches in an ASCII field (re.finditer positions without a search over the field)
-                const uint32_t L = rxo[i + 1] - rxo[i];
-                bool ascii_prog = true;
-                std::string rs(L, '\0');
-                uint64_t wild = 0;
-                for (uint32_t a = rxo[i]; a < rxo[i + 1]; ++a) {
-                    const uint32_t k = a - rxo[i];
-                    if (atoms[a].x == KW_RX_ANY) { wild |= 1ull << k; continue; }
-                    if ((uint32_t)atoms[a].y >= 128u || atoms[a].y == 0) ascii_prog = false;
-                    rs[k] = (char)atoms[a].y;
-                }
+                // an RXM use: anchored at the string's rarest 4-byte window of literals; the probe's RXM items are
+                // then exactly the program's matches in an ASCII field (re.finditer positions without a search
+                // over the field)
                 if (ascii_prog) rxm_todo.push_back({(uint32_t)i, L, wild, rs});
             }
         }
@@ -697,6 +791,7 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
     // ---- regex programs
     std::vector<int4> atoms;
     std::vector<uint32_t> rxo(n_pat + 1, 0);
+    std::vector<RxShape> shapes(n_pat);
     for (int i = 0; i < n_pat; ++i) {
         rxo[i] = (uint32_t)atoms.size();
         const bool fuzzy = pat_info[i] & PI_FUZZY;
@@ -705,21 +800,29 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
             if (fuzzy) pat_info[i] |= PI_LITERAL;
             continue;
         }
-        int nq = 0, minsum = 0;
+        int64_t minsum = 0;
+        if (!rx_check(rx_atoms, a0, a1, shapes[i], minsum))
+            return fail(KW_EUNSUPPORTED, "kw_compile: bad regex atom in pattern " + std::to_string(i));
+        if (a1 - a0 > (int64_t)RXF_ROW_MASK)
+            return fail(KW_EUNSUPPORTED, "kw_compile: more than 2^18 - 1 regex rows in pattern " + std::to_string(i));
+        if (shapes[i].frames > (uint32_t)RX_MAX_QUANT)
+            return fail(KW_EUNSUPPORTED, "kw_compile: too many quantified atoms and branches in pattern " + std::to_string(i));
+        if (minsum == 0) return fail(KW_EUNSUPPORTED, "kw_compile: regex that can match the empty string in pattern " + std::to_string(i));
         for (int64_t a = a0; a < a1; ++a) {
             int4 t;
             t.x = rx_atoms[4 * a]; t.y = rx_atoms[4 * a + 1]; t.z = rx_atoms[4 * a + 2]; t.w = rx_atoms[4 * a + 3];
-            if ((t.x != KW_RX_LIT && t.x != KW_RX_ANY) || t.z < 0 || (t.w >= 0 && t.w < t.z))
-                return fail(KW_EUNSUPPORTED, "kw_compile: bad regex atom in pattern " + std::to_string(i));
-            if (!(t.z == 1 && t.w == 1)) ++nq;
-            minsum += t.z;
             atoms.push_back(t);
         }
-        if (nq > RX_MAX_QUANT) return fail(KW_EUNSUPPORTED, "kw_compile: too many quantified atoms in pattern " + std::to_string(i));
-        if (minsum == 0) return fail(KW_EUNSUPPORTED, "kw_compile: regex that can match the empty string in pattern " + std::to_string(i));
     }
     rxo[n_pat] = (uint32_t)atoms.size();
     if (atoms.empty()) atoms.push_back(int4{0, 0, 1, 1});
+    // per row: the 128 ASCII membership bits of a SET row (zero for every other row)
+    std::vector<uint32_t> rx_mask(4 * atoms.size(), 0);
+    for (size_t a = 0; a < atoms.size(); ++a) {
+        if ((atoms[a].x & 0xFF) != KW_RX_SET) continue;
+        for (int32_t k = 1; k <= atoms[a].y; ++k)
+            for (int32_t c = atoms[a + k].y; c <= atoms[a + k].z && c < 128; ++c) rx_mask[4 * a + (c >> 5)] |= 1u << (c & 31);
+    }
 
     // ---- anchor strings and their uses
     std::unordered_map<std::string, uint32_t> as_id;
@@ -808,8 +911,8 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
 
     // ---- bit-parallel match vectors (needle = name)
     // ---- the epilogue's transcoded view of non-ASCII documents: the non-ASCII code points of the fuzzy names,
-    // most frequent first, get the one-byte markers 0x81..0xFF; a name with a code point beyond them, or with
-    // quantified regex atoms and a non-ASCII code point, is PI_TXUNSAFE (its documents go to the resolve kernel)
+    // most frequent first, get the one-byte markers 0x81..0xFF; a name with a code point beyond them, or whose
+    // regex program needs what the view loses (below), is PI_TXUNSAFE (its documents go to the resolve kernel)
     std::vector<uint32_t> tx_key(256, 0xFFFFFFFFu), tx_val(256, 0x80u), tx_inv(128, 0xFFFFFFFFu);
     std::vector<std::vector<uint32_t>> tcps(n_pat);
     std::vector<uint32_t> pat_tcps;
@@ -849,11 +952,15 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
             }
             pat_tcps.insert(pat_tcps.end(), tcps[i].begin(), tcps[i].end());
             if (!(pat_info[i] & PI_FUZZY)) continue;
-            bool quantified = false;
-            for (uint32_t a = rxo[i]; a < rxo[i + 1]; ++a) quantified |= !(atoms[a].z == 1 && atoms[a].w == 1);
-            quantified |= rxo[i + 1] - rxo[i] > 64;
-            const bool nonascii = !(pat_info[i] & PI_ASCII);
-            if (unmapped || (nonascii && quantified)) {
+            // a program for rx_match (not the shift-and search) compares code points: the view's markers are none.
+            // A set with a member >= 128 (every negated set and every category has one) and \b / \B need the
+            // true code points too; so does a literal >= 128 the name itself does not hold (an escape: no marker)
+            const bool has_prog = rxo[i + 1] > rxo[i];
+            const bool backtracks = has_prog && !shapes[i].fixed() && !shapes[i].nopos;
+            bool nonascii = !(pat_info[i] & PI_ASCII) || shapes[i].lit_ext;
+            for (uint32_t a = rxo[i]; a < rxo[i + 1]; ++a)
+                if ((atoms[a].x & 0xFF) == KW_RX_LIT && atoms[a].y >= 128) unmapped |= !mk.count((uint32_t)atoms[a].y);
+            if (unmapped || (nonascii && backtracks) || shapes[i].set_ext || shapes[i].wordb) {
                 pat_info[i] |= PI_TXUNSAFE;
                 tx_unsafe_short = 1;
                 txu_pat.push_back((uint32_t)i);
@@ -946,7 +1053,7 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
     FastBuild FB;
     {
         std::string ferr;
-        int frc = build_fast(FB, Q, n_pat, pat_bytes, pat_off, cps, tcps, pat_info, atoms, rxo, ferr);
+        int frc = build_fast(FB, Q, n_pat, pat_bytes, pat_off, cps, tcps, pat_info, atoms, rxo, shapes, ferr);
         if (frc) return fail(frc, ferr);
     }
     if (const char *dump = kw_env("KW_DUMP_ANCHORS")) {
@@ -977,7 +1084,7 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
            o_pec = push_array(blob, pm_ext_cp), o_pem = push_array(blob, pm_ext_mask), o_rxo = push_array(blob, rxo),
            o_rxa = push_array(blob, atoms), o_wb = push_array(blob, wb), o_fc = push_array(blob, f_count_ge),
            o_sk = push_array(blob, sub_key), o_sb = push_array(blob, sub_begin), o_sc = push_array(blob, sub_cnt),
-           o_sp = push_array(blob, sub_pat);
+           o_sp = push_array(blob, sub_pat), o_rxm = push_array(blob, rx_mask);
     size_t f_s1 = push_array(blob, FB.s1), f_p2 = push_array(blob, FB.p2), f_b2 = push_array(blob, FB.b2), f_l2 = push_array(blob, FB.l2),
            f_t3 = push_array(blob, FB.t3), f_epre = push_array(blob, FB.edge_pre), f_esuf = push_array(blob, FB.edge_suf), f_htk = push_array(blob, FB.ht_key),
            f_htb = push_array(blob, FB.ht_begin), f_htc = push_array(blob, FB.ht_cnt), f_kl = push_array(blob, FB.kl),
@@ -1026,6 +1133,7 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
     T.pm_ext_mask = (const uint64_t *)(B + o_pem);
     T.rx_off = (const uint32_t *)(B + o_rxo);
     T.rx_atoms = (const int4 *)(B + o_rxa);
+    T.rx_mask = (const uint32_t *)(B + o_rxm);
     T.word_bits = (const uint32_t *)(B + o_wb);
     T.f_count_ge = (const int32_t *)(B + o_fc);
     T.sub_key = (const uint64_t *)(B + o_sk);

@@ -21,7 +21,7 @@ constexpr int ITEM_CAP = 16384;                     // anchor uses per field per
 constexpr int CP_CAP = 65536;                       // decoded code points per non-ASCII field, initial (grows)
 constexpr int MAXM = 64;                            // longest fuzzy name (rapidfuzz short-needle path)
 constexpr int SHORT_EXACT_MAX = 10;                 // fields this short can only match exactly
-constexpr int RX_MAX_QUANT = 16;                    // quantified atoms per regex program
+constexpr int RX_MAX_QUANT = KW_RX_MAX_FRAMES;      // repeats + branches per regex program (rx_match's stack)
 constexpr uint32_t HASH_MUL = 0x9E3779B1u;
 constexpr uint64_t SUB_B = 0x100000001B3ull;        // substring polynomial hash base
 
@@ -44,7 +44,8 @@ constexpr uint32_t PI_WORD_FIRST = 4u;   // U: first code point is a \b word cha
 constexpr uint32_t PI_WORD_LAST = 8u;    // U: last code point is a \b word char
 constexpr uint32_t PI_ASCII = 16u;       // every code point < 128 (bytes = code points)
 constexpr uint32_t PI_TXUNSAFE = 32u;    // F: the transcoded view cannot decide it (a code point without a
-                                         // marker, or quantified regex atoms over non-ASCII code points)
+                                         // marker; a backtracking regex program over non-ASCII code points, a
+                                         // set with a member >= 128, \b or \B)
 // m (code points) in bits [15:8], byte length in bits [31:16]
 __host__ __device__ inline uint32_t pi_m(uint32_t pi) { return (pi >> 8) & 0xFF; }
 __host__ __device__ inline uint32_t pi_blen(uint32_t pi) { return pi >> 16; }
@@ -75,6 +76,7 @@ struct DevTables {
     const uint64_t *pm_ext_mask;
     const uint32_t *rx_off;        // [n_pat+1], index into rx_atoms
     const int4 *rx_atoms;
+    const uint32_t *rx_mask;       // [rows][4]: a SET row's 128 ASCII membership bits
     const uint32_t *word_bits;     // 0x110000 bits
     const int32_t *f_count_ge;     // [MAXM+2]
     // exact-substring table for short fields (<= SHORT_EXACT_MAX code points)

@@ -467,7 +467,8 @@ uint32_t fk_edge_items(const FastTables &FT, const FieldCtx &F, uint64_t *items,
     return added;
 }
 
-// re.finditer positions of a quantifier-free regex name (literals and '.'):
+// re.finditer positions of a quantifier-free regex name (literals, '.' and sets of ASCII members; no
+// assertion, no branch: kw_compile's RxShape::fixed):
 // shift-and over the field, lane l owning the 32 start positions
 // [r0 + 32 l, r0 + 32 l + 32) of each 2048-position round.  tab = this wave's
 // LDS copy of the row's 128 ASCII masks; txt = this wave's LDS staging buffer

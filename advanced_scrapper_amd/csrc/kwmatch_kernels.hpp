@@ -220,53 +220,142 @@ __device__ __forceinline__ uint32_t kfull(uint32_t m)
 }
 
 // ------------------------------------------------------------------ regex atoms
-// greedy backtracking matcher for the atom subset; returns end or -1
-__device__ int rx_match(const DevTables &T, const FieldCtx &F, uint32_t pat, uint32_t s)
+// What the backtracking engine reads, by value: the engine is one out-of-line function (rx_match), so the kernels
+// that reach it keep their own register allocation and only the engine holds its frame stack.
+struct RxCtx {
+    const int4 *rows;           // the program's rows
+    const uint32_t *mask;       // [rows][4]: the SET rows' ASCII bits
+    const uint32_t *word_bits;  // \b word class
+    const uint8_t *bytes;       // an ASCII field's (or transcoded view's) bytes, or null
+    const uint32_t *cps;        // else its code points
+    uint32_t na;                // rows
+    int n;                      // code points of the field
+};
+
+__device__ __forceinline__ uint32_t rx_cp(const RxCtx &C, int i) { return C.bytes ? (uint32_t)C.bytes[i] : C.cps[i]; }
+
+__device__ __forceinline__ bool rx_is_word(const RxCtx &C, uint32_t c)
 {
-    const uint32_t ab = T.rx_off[pat], ae = T.rx_off[pat + 1];
-    const uint32_t na = ae - ab;
-    int st_atom[RX_MAX_QUANT], st_pos[RX_MAX_QUANT], st_cnt[RX_MAX_QUANT];
+    if (c < 128) return (c >= '0' && c <= '9') || (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || c == '_';
+    return c < 0x110000u && ((C.word_bits[c >> 5] >> (c & 31)) & 1u);
+}
+
+// one code point against the LIT / ANY / SET row `at` (row index ai of the program)
+__device__ __forceinline__ bool rx_cp_ok(const RxCtx &C, const int4 &at, uint32_t ai, uint32_t c)
+{
+    const int op = at.x & 0xFF;
+    if (op == KW_RX_LIT) return c == (uint32_t)at.y;
+    if (op == KW_RX_ANY) return c != '\n';
+    if (c < 128u) return (C.mask[4 * (size_t)ai + (c >> 5)] >> (c & 31u)) & 1u;
+    // the first RANGE row whose hi >= c holds c or no row does (rows sorted, disjoint)
+    int lo = 0, hi = at.y;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((uint32_t)C.rows[ai + 1 + mid].z < c) lo = mid + 1; else hi = mid;
+    }
+    return lo < at.y && (uint32_t)C.rows[ai + 1 + lo].y <= c;
+}
+
+// rows a LIT / ANY / SET row takes in the stream (a SET carries its RANGE rows)
+__device__ __forceinline__ uint32_t rx_rows(const int4 &at) { return (at.x & 0xFF) == KW_RX_SET ? 1u + (uint32_t)at.y : 1u; }
+
+// the zero-width test `kind` (KW_AT_*) at offset pos
+__device__ __forceinline__ bool rx_at_ok(const RxCtx &C, int kind, int pos)
+{
+    const int n = C.n;
+    if (kind == KW_AT_BOS) return pos == 0;
+    if (kind == KW_AT_EOS) return pos == n;
+    if (kind == KW_AT_EOL) return pos == n || (pos == n - 1 && rx_cp(C, pos) == '\n');
+    const bool before = pos > 0 && rx_is_word(C, rx_cp(C, pos - 1));
+    const bool after = pos < n && rx_is_word(C, rx_cp(C, pos));
+    return (before != after) == (kind == KW_AT_WORD);
+}
+
+// backtracking matcher for the atom programs of include/kwmatch.h (sre's priority order), from row a at offset
+// pos (rows before a hold no repeat and no branch: the caller matched them); returns end or -1.
+// One stack of frames, one 64-bit word each (a per-lane array indexed at run time lives in scratch: one store
+// or load per frame operation): row [17:0], start offset [40:18], count [63:41] (kw_compile checks the rows
+// of a program; fields hold at most 2^23 - 1 code points).  A repeat's frame is (its row, start offset,
+// current count): greedy ones give back and lazy ones take one more on backtracking; a branch's frame is (the
+// ARM row being tried, the offset at the branch, 0), and backtracking into it starts the next arm.
+constexpr int RXF_POS = 18, RXF_CNT = 41;
+constexpr uint64_t RXF_ROW_MASK = (1ull << RXF_POS) - 1, RXF_POS_MASK = (1ull << (RXF_CNT - RXF_POS)) - 1;
+static_assert((int64_t)RXF_POS_MASK >= MAX_FIELD_BYTES, "a frame holds any offset of a field");
+
+__device__ __forceinline__ uint64_t rx_frame(uint32_t row, int pos, int cnt)
+{
+    return (uint64_t)row | ((uint64_t)(uint32_t)pos << RXF_POS) | ((uint64_t)(uint32_t)cnt << RXF_CNT);
+}
+
+__device__ __noinline__ int rx_match(RxCtx C, int pos, uint32_t a)
+{
+    const uint32_t na = C.na;
+    uint64_t st[RX_MAX_QUANT];
     int sp = 0;
-    uint32_t a = 0;
-    int pos = (int)s;
-    const int n = (int)F.n;
+    const int n = C.n;
     for (;;) {
         bool fail = false;
         if (a == na) return pos;
-        int4 at = T.rx_atoms[ab + a];
-        if (at.z == 1 && at.w == 1) {
-            if (pos < n) {
-                uint32_t c = fcp(F, (uint32_t)pos);
-                bool ok = (at.x == KW_RX_LIT) ? (c == (uint32_t)at.y) : (c != '\n');
-                if (ok) { ++pos; ++a; continue; }
-            }
+        int4 at = C.rows[a];
+        const int op = at.x & 0xFF;
+        if (op <= KW_RX_SET && at.z == 1 && at.w == 1) {
+            if (pos < n && rx_cp_ok(C, at, a, rx_cp(C, pos))) { ++pos; a += rx_rows(at); continue; }
             fail = true;
-        } else {
+        } else if (op <= KW_RX_SET) {
+            // a greedy repeat takes all it can, a lazy one its minimum
+            const int want = (at.x & KW_RX_LAZY) ? at.z : at.w;
             int k = 0;
-            while ((at.w < 0 || k < at.w) && pos + k < n) {
-                uint32_t c = fcp(F, (uint32_t)(pos + k));
-                bool ok = (at.x == KW_RX_LIT) ? (c == (uint32_t)at.y) : (c != '\n');
-                if (!ok) break;
-                ++k;
-            }
+            while ((want < 0 || k < want) && pos + k < n && rx_cp_ok(C, at, a, rx_cp(C, pos + k))) ++k;
             if (k < at.z) {
                 fail = true;
             } else {
-                st_atom[sp] = (int)a; st_pos[sp] = pos; st_cnt[sp] = k; ++sp;
+                st[sp++] = rx_frame(a, pos, k);
                 pos += k;
-                ++a;
+                a += rx_rows(at);
                 continue;
             }
+        } else if (op == KW_RX_AT) {
+            if (rx_at_ok(C, at.y, pos)) { ++a; continue; }
+            fail = true;
+        } else if (op == KW_RX_ALT) {
+            st[sp++] = rx_frame(a + 1, pos, 0);
+            a += 2;
+            continue;
+        } else if (op == KW_RX_ARM) {   // the arm before this one ended: go on after the branch
+            a += (uint32_t)at.z;
+            continue;
+        } else {                        // KW_RX_NOPOS: positions are the host's
+            return -1;
         }
         if (fail) {
             bool resumed = false;
             while (sp > 0) {
-                int t = sp - 1;
-                int4 qa = T.rx_atoms[ab + st_atom[t]];
-                if (st_cnt[t] > qa.z) {
-                    st_cnt[t]--;
-                    pos = st_pos[t] + st_cnt[t];
-                    a = (uint32_t)st_atom[t] + 1;
+                const uint64_t f = st[sp - 1];
+                const uint32_t qi = (uint32_t)(f & RXF_ROW_MASK);
+                const int p0 = (int)((f >> RXF_POS) & RXF_POS_MASK), cnt = (int)(f >> RXF_CNT);
+                const int4 qa = C.rows[qi];
+                if ((qa.x & 0xFF) == KW_RX_ARM) {
+                    const uint32_t next = qi + 1u + (uint32_t)qa.y;
+                    if (next != qi + (uint32_t)qa.z) {
+                        st[sp - 1] = rx_frame(next, p0, 0);
+                        pos = p0;
+                        a = next + 1u;
+                        resumed = true;
+                        break;
+                    }
+                } else if (qa.x & KW_RX_LAZY) {
+                    const int p = p0 + cnt;
+                    if ((qa.w < 0 || cnt < qa.w) && p < n && rx_cp_ok(C, qa, qi, rx_cp(C, p))) {
+                        st[sp - 1] = f + (1ull << RXF_CNT);
+                        pos = p + 1;
+                        a = qi + rx_rows(qa);
+                        resumed = true;
+                        break;
+                    }
+                } else if (cnt > qa.z) {
+                    st[sp - 1] = f - (1ull << RXF_CNT);
+                    pos = p0 + cnt - 1;
+                    a = qi + rx_rows(qa);
                     resumed = true;
                     break;
                 }
@@ -277,14 +366,37 @@ __device__ int rx_match(const DevTables &T, const FieldCtx &F, uint32_t pat, uin
     }
 }
 
+__device__ __forceinline__ RxCtx rx_ctx(const DevTables &T, const FieldCtx &F, uint32_t pat)
+{
+    const uint32_t ab = T.rx_off[pat];
+    RxCtx C;
+    C.rows = T.rx_atoms + ab;
+    C.mask = T.rx_mask + 4 * (size_t)ab;
+    C.word_bits = T.word_bits;
+    C.bytes = F.ascii ? F.arena + F.fb : nullptr;
+    C.cps = F.cps;
+    C.na = T.rx_off[pat + 1] - ab;
+    C.n = (int)F.n;
+    return C;
+}
+
 // wave-cooperative re.finditer positions of a regex-program pattern; returns count emitted
 __device__ uint32_t rx_positions(const DevTables &T, const DevScratch &S, const FieldCtx &F, OutCtx &O, uint32_t pat)
 {
     const int lane = lane_id();
     uint32_t last_end = 0, emitted = 0;
+    const RxCtx C = rx_ctx(T, F, pat);
+    const int4 first = C.rows[0];
+    if (first.x == KW_RX_NOPOS) return 0;   // (the caller emits the KW_NOPOS record)
+    // a program that starts with a consuming atom of min >= 1 can only match where that atom takes the first
+    // code point: the engine is called for those starts only, and after that atom when it is unrepeated
+    const bool head = (first.x & 0xFF) <= KW_RX_SET && first.z >= 1;
+    const bool skip = head && first.z == 1 && first.w == 1;
+    const uint32_t a0 = skip ? rx_rows(first) : 0u;
     for (uint32_t s0 = 0; s0 < F.n; s0 += WAVE) {
         uint32_t s = s0 + lane;
-        int e = (s < F.n) ? rx_match(T, F, pat, s) : -1;
+        int e = -1;
+        if (s < F.n && (!head || rx_cp_ok(C, first, 0, rx_cp(C, (int)s)))) e = rx_match(C, (int)s + (skip ? 1 : 0), a0);
         uint64_t m = __ballot(e >= 0);
         uint64_t keep = 0;
         while (m) {

@@ -271,6 +271,182 @@ def regex_atoms_sre(name: str):
     return atoms
 
 
+# --------------------------------------------------------------------- regex programs
+# Further rows of the atom stream (include/kwmatch.h, KW_RX_*).
+RX_SET, RX_RANGE, RX_AT, RX_ALT, RX_ARM, RX_NOPOS = 2, 3, 4, 5, 6, 7
+RX_LAZY = 0x100
+AT_BOS, AT_EOL, AT_EOS, AT_WORD, AT_NWORD = 0, 1, 2, 3, 4
+RX_MAX_FRAMES = 16      # repeats + branches of one program (KW_RX_MAX_FRAMES)
+RX_MAX_RANGES = 1024    # RANGE rows of one set (KW_RX_MAX_RANGES)
+RX_HOST = 'host'        # regex_program: re.compile takes the name, the atom stream does not
+NOPOS_PROGRAM = [(RX_NOPOS, 0, 0, 0)]
+
+_AT_KIND = {
+    _sre_c.AT_BEGINNING: AT_BOS, _sre_c.AT_BEGINNING_STRING: AT_BOS, _sre_c.AT_END: AT_EOL,
+    _sre_c.AT_END_STRING: AT_EOS, _sre_c.AT_BOUNDARY: AT_WORD, _sre_c.AT_NON_BOUNDARY: AT_NWORD,
+}
+# category -> (its positive class as re source, negated)
+_CATEGORY = {
+    _sre_c.CATEGORY_DIGIT: (r'\d', False), _sre_c.CATEGORY_NOT_DIGIT: (r'\d', True),
+    _sre_c.CATEGORY_SPACE: (r'\s', False), _sre_c.CATEGORY_NOT_SPACE: (r'\s', True),
+    _sre_c.CATEGORY_WORD: (r'\w', False), _sre_c.CATEGORY_NOT_WORD: (r'\w', True),
+}
+_CLASS_FLAGS: Dict[str, np.ndarray] = {}
+_SET_RANGES: Dict[tuple, Optional[List[Tuple[int, int]]]] = {}
+
+
+class _NotExpressible(Exception):
+    """The walk met a construct the atom stream does not hold."""
+
+
+def _every_code_point() -> str:
+    return np.arange(0x110000, dtype='<u4').tobytes().decode('utf-32-le', 'surrogatepass')
+
+
+def _class_flags(src: str) -> np.ndarray:
+    """Membership of every code point in the class ``src`` (``\\d`` / ``\\s`` / ``\\w``), by re itself."""
+    flags = _CLASS_FLAGS.get(src)
+    if flags is None:
+        flags = np.zeros(0x110000, dtype=bool)
+        flags[[m.start() for m in re.finditer(src, _every_code_point())]] = True
+        _CLASS_FLAGS[src] = flags
+    return flags
+
+
+def set_ranges(items) -> Optional[List[Tuple[int, int]]]:
+    """The sorted, disjoint inclusive code-point ranges of an sre ``IN`` item list (negation and categories
+    resolved with re's own classes; cached per set), or ``None`` when the set holds something else."""
+    key = tuple((str(op), av if not isinstance(av, tuple) else tuple(av)) for op, av in items)
+    if key in _SET_RANGES:
+        return _SET_RANGES[key]
+    flags = np.zeros(0x110000, dtype=bool)
+    negate = False
+    ok = True
+    for op, av in items:
+        if op is _sre_c.NEGATE:
+            negate = True
+        elif op is _sre_c.LITERAL:
+            flags[int(av)] = True
+        elif op is _sre_c.RANGE:
+            flags[int(av[0]):int(av[1]) + 1] = True
+        elif op is _sre_c.CATEGORY and av in _CATEGORY:
+            src, neg = _CATEGORY[av]
+            cls = _class_flags(src)
+            flags |= ~cls if neg else cls
+        else:
+            ok = False
+    ranges = None
+    if ok:
+        if negate:
+            flags = ~flags
+        edge = np.flatnonzero(np.diff(np.concatenate(([0], flags.view(np.int8), [0]))))
+        ranges = [(int(lo), int(hi) - 1) for lo, hi in zip(edge[0::2], edge[1::2])]
+    _SET_RANGES[key] = ranges
+    return ranges
+
+
+def _host_or_invalid(name: str):
+    try:
+        re.compile(name)
+    except re.error:
+        return 'invalid'
+    return RX_HOST
+
+
+def regex_program(name: str):
+    """Atom program for ``re.finditer(name, s)`` over the whole stream of include/kwmatch.h.
+
+    ``None`` (literal search), ``'invalid'`` (``re.compile`` raises) or a list of ``(op, value, min, max)``
+    rows as :func:`regex_atoms` gives them, for every name regex_atoms takes the same rows.  Beyond its subset:
+    sets (``[...]``, ``\\d \\D \\w \\W \\s \\S``, negation resolved into ranges), the assertions
+    ``^ \\A $ \\Z \\b \\B``, lazy repeats of one literal / ``.`` / set, and branches in the top-level
+    sequence whose arms are plain sequences.  ``RX_HOST`` for a name re compiles but the stream cannot hold
+    (quantified groups, nested branches, backreferences, look-around, inline flags, an empty shortest match, a
+    set of more than RX_MAX_RANGES ranges, more than RX_MAX_FRAMES repeats and branches): the device decides
+    such a name and the host finds its positions (matcher.resolve_host_positions).
+    """
+    meta = _META & set(name)
+    if not meta:
+        return None
+    if meta == _DOT:
+        return [(RX_ANY, 0, 1, 1) if ch == '.' else (RX_LIT, ord(ch), 1, 1) for ch in name]
+    try:
+        parsed = _sre_p.parse(name)
+    except re.error:
+        return 'invalid'
+    try:
+        if parsed.state.flags & ~_sre_c.SRE_FLAG_UNICODE:
+            raise _NotExpressible
+        rows, minlen, frames = _program_rows(parsed, True)
+        if minlen == 0 or frames > RX_MAX_FRAMES:
+            raise _NotExpressible
+    except _NotExpressible:
+        return _host_or_invalid(name)
+    return rows
+
+
+def _program_rows(items, top: bool):
+    """(rows, shortest match, frames) of an sre item sequence; ``top``: branches may stand in it."""
+    rows: List[Tuple[int, int, int, int]] = []
+    minlen = frames = 0
+
+    def single(op, av):
+        """(op, value, RANGE rows) of a one-code-point item, or None."""
+        if op is _sre_c.LITERAL:
+            return RX_LIT, int(av), []
+        if op is _sre_c.ANY:
+            return RX_ANY, 0, []
+        if op is _sre_c.NOT_LITERAL:
+            op, av = _sre_c.IN, [(_sre_c.NEGATE, None), (_sre_c.LITERAL, av)]
+        if op is _sre_c.IN:
+            ranges = set_ranges(av)
+            if ranges is None or len(ranges) > RX_MAX_RANGES:
+                raise _NotExpressible
+            return RX_SET, len(ranges), [(RX_RANGE, lo, hi, 0) for lo, hi in ranges]
+        return None
+
+    for op, av in items:
+        s = single(op, av)
+        if s is not None:
+            rows.append((s[0], s[1], 1, 1))
+            rows.extend(s[2])
+            minlen += 1
+        elif op is _sre_c.MAX_REPEAT or op is _sre_c.MIN_REPEAT:
+            lo, hi, sub = av
+            sub = list(sub)
+            s = single(*sub[0]) if len(sub) == 1 else None
+            if s is None:
+                raise _NotExpressible
+            lo, hi = int(lo), (-1 if hi == _sre_c.MAXREPEAT else int(hi))
+            lazy = RX_LAZY if op is _sre_c.MIN_REPEAT and lo != hi else 0
+            rows.append((s[0] | lazy, s[1], lo, hi))
+            rows.extend(s[2])
+            minlen += lo
+            frames += not (lo == 1 and hi == 1)
+        elif op is _sre_c.AT and av in _AT_KIND:
+            rows.append((RX_AT, _AT_KIND[av], 0, 0))
+        elif op is _sre_c.SUBPATTERN and not av[1] and not av[2]:
+            r, m, f = _program_rows(av[3], top)
+            rows.extend(r)
+            minlen += m
+            frames += f
+        elif op is _sre_c.BRANCH and top:
+            arms = [_program_rows(arm, False) for arm in av[1]]
+            total = sum(1 + len(r) for r, _m, _f in arms)
+            rows.append((RX_ALT, len(arms), total, 0))
+            left = total
+            for r, _m, f in arms:
+                rows.append((RX_ARM, len(r), left, 0))   # left: rows from this ARM row to the branch's end
+                rows.extend(r)
+                left -= 1 + len(r)
+                frames += f
+            minlen += min(m for _r, m, _f in arms)
+            frames += 1
+        else:
+            raise _NotExpressible
+    return rows, minlen, frames
+
+
 # --------------------------------------------------------------------- word table
 _WORD_BITMAP: Optional[np.ndarray] = None
 
@@ -303,6 +479,9 @@ class CompiledKB:
     rx_atoms: np.ndarray                   # int32 [n_atoms, 4]
     rx_off: np.ndarray                     # int64, n+1
     invalid_regex: List[bool]
+    # host_regex[pid]: re compiles the name but the atom stream cannot hold it; the device gets the KW_RX_NOPOS
+    # program and the writer finds the positions (matcher.resolve_host_positions)
+    host_regex: List[bool] = field(default_factory=list)
     # occurrences[pid] = list of (ticker index, traversal rank, start, end)
     occurrences: List[List[Tuple[int, int, object, object]]] = field(default_factory=list)
     n_occurrences: int = 0
@@ -329,15 +508,14 @@ PAR_MIN_REGEX = 65536  # regex-bearing names from which compile_kb parses the pr
 
 
 def _atoms_of(names: List[str]):
-    """Worker: regex_atoms of each name (UnsupportedPattern propagates to the caller)."""
-    return [regex_atoms(n) for n in names]
+    """Worker: regex_program of each name."""
+    return [regex_program(n) for n in names]
 
 
 def regex_programs(names: List[str], fuzzy: List[bool], workers: Optional[int] = None) -> list:
-    """regex_atoms of every fuzzy-class name (None for the others), in order.  Only names with a regex
+    """regex_program of every fuzzy-class name (None for the others), in order.  Only names with a regex
     metacharacter need sre_parse; from PAR_MIN_REGEX of them (a Wikidata-scale KB, config 4) they are
-    parsed by ``workers`` spawned processes (default min(16, os.cpu_count())) in contiguous chunks, so
-    the first unsupported name in KB order is the one reported, as in the serial loop."""
+    parsed by ``workers`` spawned processes (default min(16, os.cpu_count())) in contiguous chunks."""
     progs: list = [None] * len(names)
     todo = [i for i, n in enumerate(names) if fuzzy[i] and (_META & set(n))]
     if workers is None:
@@ -355,7 +533,7 @@ def regex_programs(names: List[str], fuzzy: List[bool], workers: Optional[int] =
                     progs[i] = prog
     else:
         for i in todo:
-            progs[i] = regex_atoms(names[i])
+            progs[i] = regex_program(names[i])
     return progs
 
 
@@ -401,15 +579,19 @@ def compile_kb(processed_data: Dict[str, Dict[str, Dict[str, tuple]]], workers: 
     atoms: List[Tuple[int, int, int, int]] = []
     rx_off = np.zeros(len(ordered) + 1, dtype=np.int64)
     invalid = []
+    host = []
     progs = regex_programs(ordered, [c == CLASS_FUZZY for c in classes], workers)
     for i, prog in enumerate(progs):
         rx_off[i] = len(atoms)
         invalid.append(prog == 'invalid')
+        host.append(prog == RX_HOST)
+        if host[-1]:
+            prog = NOPOS_PROGRAM
         if isinstance(prog, list):
             atoms.extend(prog)
     rx_off[len(ordered)] = len(atoms)
     rx = np.asarray(atoms, dtype=np.int32).reshape(-1, 4) if atoms else np.zeros((0, 4), np.int32)
     return CompiledKB(
         tickers=tickers, names=ordered, classes=classes, pat_bytes=pat_bytes, pat_off=pat_off,
-        pat_class=pat_class, rx_atoms=rx, rx_off=rx_off, invalid_regex=invalid,
+        pat_class=pat_class, rx_atoms=rx, rx_off=rx_off, invalid_regex=invalid, host_regex=host,
         occurrences=[occ_by_name[n] for n in ordered], n_occurrences=rank)

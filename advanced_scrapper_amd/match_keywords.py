@@ -38,7 +38,7 @@ from .kb import (ATTRIBUTES, compile_kb, extract_time_periods, is_within_period,
                  process_json_data, read_and_process_json_files)
 from .rows import assemble_json_raw, assemble_json_rows
 from .matcher import (GpuMatcher, assemble_ticker_matches, background_sample, field_str, group_hits,  # noqa: F401
-                      pack_fields, records_from_tensor)
+                      pack_fields, records_from_tensor, resolve_host_positions)
 
 OUTPUT_COLUMNS = ('time_unix', 'date_time', 'text_matches', 'title_matches', 'title', 'url', 'source',
                   'source_url', 'article_text')
@@ -192,10 +192,29 @@ def match_chunk(chunk, processed_data, matcher: Optional[GpuMatcher] = None):
 def _match(chunk, processed_data, matcher: Optional[GpuMatcher] = None):
     """``ticker_matches`` of every row of ``chunk`` (list aligned with the rows), the error, the dates."""
     hits, error, dates, matcher = _match_hits(chunk, processed_data, matcher)
+    hits = _host_positions(chunk, matcher, hits)
     results, err_asm = _results(matcher, hits, dates)
     if err_asm is not None:
         raise err_asm
     return results, error, dates
+
+
+_FIELD_COLUMNS = ('article_text', 'title')
+
+
+def _host_positions(chunk, matcher, hits):
+    """``hits`` with the positions of the names whose regex the device cannot run (``CompiledKB.host_regex``)
+    found by ``re`` in the chunk's own text (matcher.resolve_host_positions): only decided fields of such
+    names are searched.  ``hits`` index the chunk's rows."""
+    if hits is None or not any(matcher.ckb.host_regex):
+        return hits
+    if isinstance(chunk, NativeChunk):
+        def text(doc, field):
+            return field_str(chunk.value(doc, _FIELD_COLUMNS[field]))
+    else:
+        def text(doc, field):
+            return field_str(chunk[_FIELD_COLUMNS[field]].iloc[doc])
+    return resolve_host_positions(matcher.ckb, hits, text)
 
 
 def _results(matcher, hits, dates):
@@ -311,6 +330,7 @@ def _native_rows(chunk, matcher, hits, dates, error):
 def _append_hits(source_name, chunk, matcher, hits, dates, error):
     """Append the rows of a matched chunk up to its first failing article; returns that article's exception
     and row (``None, None`` if none fails, see :func:`_hit_rows`)."""
+    hits = _host_positions(chunk, matcher, hits)
     nat = _native_rows(chunk, matcher, hits, dates, error)
     if nat is not None:
         rendered, exc, row = nat
@@ -435,7 +455,7 @@ def _write_shard(source_name, chunk: ShardChunk, processed_data, matcher, exchan
         arena, off = chunk.arena()
         d_arena, d_off = matcher.upload(arena, off[:2 * n_ok + 1])
         matcher.scan(d_arena, d_off, n_ok)
-        hits = matcher.fetch()
+        hits = _host_positions(chunk, matcher, matcher.fetch())
     nat = _native_rows(chunk, matcher, hits, dates, error)
     if nat is not None:
         rendered, exc, row = nat

@@ -228,6 +228,48 @@ def records_from_tensor(t) -> np.ndarray:
     return np.ascontiguousarray(host).view(np.uint32).reshape(-1, 4).copy().view(_native.HIT_DTYPE).reshape(-1)
 
 
+# --------------------------------------------------------------------- host regex positions
+def resolve_host_positions(ckb: CompiledKB, hits: np.ndarray, field_text) -> np.ndarray:
+    """The records with the positions of the host-resolved names filled in.
+
+    A name with ``ckb.host_regex`` set runs the KW_RX_NOPOS program on the device: every decided (doc, field,
+    name) comes back as one KW_NOPOS record.  Each such record is replaced by one record per
+    ``re.finditer(name, field)`` position (code-point offsets, match_keywords.py:177-180), and kept when there
+    is none.  ``field_text(doc, field)`` gives the field as the reference matched it (field 0 =
+    article_text, 1 = title).  Other names' records, invalid-regex names included, pass through; the order
+    of the records is kept.
+    """
+    host = getattr(ckb, 'host_regex', None)
+    if hits is None or not len(hits) or not host or not any(host):
+        return hits
+    host_pat = np.asarray(host, dtype=bool)
+    sel = np.flatnonzero(host_pat[hits['pattern']] & (hits['pos'] == _native.KW_NOPOS))
+    if not len(sel):
+        return hits
+    compiled: Dict[int, "re.Pattern"] = {}
+    pieces: List[np.ndarray] = []
+    prev = 0
+    for k in sel.tolist():
+        rec = hits[k]
+        pat = int(rec['pattern'])
+        rx = compiled.get(pat)
+        if rx is None:
+            rx = compiled[pat] = re.compile(ckb.names[pat])
+        pos = [m.start() for m in rx.finditer(field_text(int(rec['doc']), int(rec['field'])))]
+        if not pos:
+            continue
+        pieces.append(hits[prev:k])
+        new = np.empty(len(pos), dtype=hits.dtype)
+        new[:] = rec
+        new['pos'] = pos
+        pieces.append(new)
+        prev = k + 1
+    if not pieces:
+        return hits
+    pieces.append(hits[prev:])
+    return np.concatenate(pieces)
+
+
 # --------------------------------------------------------------------- assembly
 def group_hits(hits: np.ndarray) -> Dict[int, Dict[int, Dict[int, List[int]]]]:
     """doc -> field -> pattern -> sorted positions ([] for a position-less match)."""

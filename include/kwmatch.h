@@ -49,9 +49,60 @@ extern "C" {
  * {op, value, min, max}; op 0 = literal code point `value`, op 1 = '.'
  * (any code point except '\n'); the atom repeats greedily min..max times
  * (max = -1: unbounded).  A pattern with rx_off[i] == rx_off[i+1] is matched
- * literally (its atoms are its code points). */
+ * literally (its atoms are its code points).
+ *
+ * Further rows of the same stream (rx_off counts rows):
+ *   KW_RX_SET    one code point out of a set, repeated min..max times like
+ *                LIT / ANY.  value = R >= 0, the number of KW_RX_RANGE rows
+ *                that follow directly: {KW_RX_RANGE, lo, hi, 0} with
+ *                0 <= lo <= hi <= 0x10FFFF, sorted and disjoint (row k+1's lo
+ *                > row k's hi), R <= KW_RX_MAX_RANGES.  The host has resolved
+ *                negation and the categories \d \D \w \W \s \S into ranges.
+ *   KW_RX_AT     {KW_RX_AT, kind, 0, 0}: a zero-width test at the current
+ *                offset p of the field of n code points (no MULTILINE):
+ *                KW_AT_BOS   ^ \A   p == 0
+ *                KW_AT_EOL   $      p == n, or p == n-1 and the last is '\n'
+ *                KW_AT_EOS   \Z     p == n
+ *                KW_AT_WORD  \b     word(p-1) != word(p)  (word_bitmap; a
+ *                KW_AT_NWORD \B     word(p-1) == word(p)   neighbour outside
+ *                                                          the field: non-word)
+ *   KW_RX_LAZY   or-ed into the op of a LIT / ANY / SET row with min < max
+ *                (or max = -1): the repeat is lazy (*? +? ?? {m,n}?).
+ *   KW_RX_ALT    {KW_RX_ALT, arms, rows, 0}: a branch of arms >= 2 arms; rows =
+ *                the number of rows after this one that belong to it.  Each arm
+ *                is {KW_RX_ARM, n, d, 0} followed by its n rows (LIT / ANY /
+ *                SET with their RANGE rows / AT; no ALT inside an arm), d =
+ *                the distance in rows from this ARM row to the first row after
+ *                the branch.  Arms are tried in order, each with its own
+ *                backtracking; when all fail the engine backtracks into what
+ *                precedes the branch; matching goes on after the branch when an
+ *                arm ends (CPython's sre semantics).  Branches stand in the
+ *                top-level sequence only.
+ *   KW_RX_NOPOS  {KW_RX_NOPOS, 0, 0, 0} as the whole program: the name's regex
+ *                is outside this subset.  The fuzzy decision is taken as for
+ *                every name, and each decided (doc, field, name) gets one
+ *                KW_NOPOS record; the caller finds the positions itself
+ *                (advanced_scrapper_amd.matcher.resolve_host_positions).
+ * A program may hold at most KW_RX_MAX_FRAMES repeats (rows with min != 1 or
+ * max != 1) plus branches and at most 2^18 - 1 rows, and its shortest match
+ * must not be empty (the sum of the top-level mins plus each branch's shortest
+ * arm). */
 #define KW_RX_LIT 0
 #define KW_RX_ANY 1
+#define KW_RX_SET 2
+#define KW_RX_RANGE 3
+#define KW_RX_AT 4
+#define KW_RX_ALT 5
+#define KW_RX_ARM 6
+#define KW_RX_NOPOS 7
+#define KW_RX_LAZY 0x100
+#define KW_AT_BOS 0
+#define KW_AT_EOL 1
+#define KW_AT_EOS 2
+#define KW_AT_WORD 3
+#define KW_AT_NWORD 4
+#define KW_RX_MAX_FRAMES 16
+#define KW_RX_MAX_RANGES 1024
 
 typedef struct kw_handle kw_handle;
 
@@ -74,7 +125,9 @@ typedef struct {
  *                       Order: all 'U' names first, then the 'F' names sorted by
  *                       code-point length, longest first.
  *   rx_atoms/rx_off   : regex programs (see KW_RX_*), rx_off has n_pat+1 entries;
- *                       may be NULL (all names literal).
+ *                       may be NULL (all names literal).  Every program is checked
+ *                       before the device is touched: a malformed one (see KW_RX_*) is
+ *                       KW_EUNSUPPORTED, and kw_last_error names the pattern index.
  *   word_bitmap       : 0x110000 bits, bit c set iff chr(c).isalnum() or c == '_'
  *                       (CPython's \b word class, Unicode database of the host).
  *   bg/bg_len         : optional background sample of the article text (UTF-8).  Its
