@@ -45,7 +45,19 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_allgather_hits_planned', 'kw_exchange_plan', 'kw_exchange_caps_ok', 'kw_comm_last_error',
            'kw_comm_destroy',
            'kw_dedup_create', 'kw_dedup_run', 'kw_dedup_counts', 'kw_dedup_kept_size', 'kw_dedup_kept_copy',
-           'kw_dedup_last_ms', 'kw_dedup_last_error', 'kw_dedup_destroy', 'dedup_urls')
+           'kw_dedup_last_ms', 'kw_dedup_last_error', 'kw_dedup_destroy', 'dedup_urls',
+           'kw_cdx_begin', 'kw_cdx_append', 'kw_cdx_rows', 'kw_cdx_store_copy', 'kw_cdx_run', 'kw_cdx_csv_size',
+           'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes')
+
+# KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
+(KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
+ KW_CDX_HEADER) = range(9)
+
+
+class CdxDialect(ctypes.Structure):
+    """kw_cdx_dialect (include/kwdedup.h)."""
+    _fields_ = [('delim', ctypes.c_uint8), ('ts_col', ctypes.c_int32), ('url_col', ctypes.c_int32),
+                ('skip_lines', ctypes.c_int32), ('exact_fields', ctypes.c_int32)]
 
 # KW_URL_* row codes (include/kwdedup.h)
 KW_URL_NO_HTML, KW_URL_KEPT, KW_URL_FILTERED, KW_URL_DUPLICATE = 0, 1, 2, 3
@@ -90,6 +102,19 @@ def lib() -> ctypes.CDLL:
     L.dedup_urls.argtypes = [vp, vp, i64, vp, vp]
     for f in ('kw_dedup_create', 'kw_dedup_run', 'kw_dedup_counts', 'kw_dedup_kept_size', 'kw_dedup_kept_copy',
               'kw_dedup_last_ms', 'kw_dedup_destroy', 'dedup_urls'):
+        getattr(L, f).restype = ctypes.c_int
+    L.kw_cdx_begin.argtypes = [vp]
+    L.kw_cdx_append.argtypes = [vp, vp, i64, ctypes.POINTER(CdxDialect), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                ctypes.POINTER(i64), vp]
+    L.kw_cdx_rows.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.kw_cdx_store_copy.argtypes = [vp, vp, vp, vp, vp]
+    L.kw_cdx_run.argtypes = [vp, i32, vp]
+    L.kw_cdx_csv_size.argtypes = [vp, ctypes.POINTER(i64), vp]
+    L.kw_cdx_csv_copy.argtypes = [vp, vp, vp]
+    L.kw_cdx_last_ms.argtypes = [vp, vp, i32]
+    L.kw_cdx_tile_bytes.argtypes = []
+    for f in ('kw_cdx_begin', 'kw_cdx_append', 'kw_cdx_rows', 'kw_cdx_store_copy', 'kw_cdx_run', 'kw_cdx_csv_size',
+              'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_compile.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)]
     L.kw_compile.restype = ctypes.c_int

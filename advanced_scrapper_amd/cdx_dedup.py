@@ -5,12 +5,18 @@
     merge_parts(folder, out='yfin_urls.csv')  :160-179  glob order, concat, keep-first -> yfin_urls.csv
     GpuUrlDedup                           the libkwmatch handle (include/kwdedup.h)
 
-The CDX text is parsed on the host with the reference's own pandas call
-(``read_csv(delimiter=' ', header=None, usecols=[1, 2])``); the URL column goes
-to HBM as a UTF-8 arena + int64 offsets and the rewrite + keep-first runs in
-HIP kernels (csrc/dedup.hip).  CSV writing stays on the host (pandas
-``to_csv(index=False)``, as the reference).  There is no CPU fallback: without
-a GPU or without libkwmatch.so the entry points raise.
+Raw listing bytes in, final CSV bytes out: the file's bytes are uploaded once,
+parsed on the device into a UTF-8 URL arena + int64 offsets + int64 timestamps
+(csrc/cdx.hip), the rewrite + keep-first runs in HIP kernels (csrc/dedup.hip),
+and the kept rows' ``timestamp,url`` lines are rendered on the device; nothing
+per row runs on the host.  The device parser is used only where its result
+provably equals the reference's pandas call (``read_csv(delimiter=' ',
+header=None, usecols=[1, 2])``; the rule: DESIGN.md §7, tests/cdx_rule.py).  Any
+other text, and everything under ``KW_CDX_NATIVE=0``, takes the pandas parse +
+``to_csv(index=False)`` around the same kernels, so the reference's exceptions
+and messages stay as they are and the output files are byte-identical on either
+route.  There is no CPU fallback: without a GPU or without libkwmatch.so the
+entry points raise.
 
 ``python -m advanced_scrapper_amd.cdx_dedup [folder]`` runs the reference's
 post-scrape pipeline: every ``yahoo_links_1/*.txt`` -> part CSV, then the merge.
@@ -29,6 +35,12 @@ import numpy as np
 from . import _native
 
 ARENA_PAD = 64
+
+# kw_cdx_dialect values (delimiter, ts_col, url_col, skip_lines, exact_fields) of the two texts the reference reads
+CDX_DIALECTS = {
+    'listing': (ord(' '), 1, 2, 0, 0),   # read_csv(delimiter=' ', header=None, usecols=[1, 2])   (:59)
+    'part': (ord(','), 0, 1, 1, 2),      # read_csv(part) under the header line "date_time,url"    (:164-167)
+}
 
 
 def pack_urls(urls: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
@@ -125,6 +137,80 @@ class GpuUrlDedup:
         self._check(_native.lib().kw_dedup_last_ms(self.h, _native.ptr(v), 5))
         return [float(x) for x in v]
 
+    # ---- raw text in, CSV bytes out (include/kwdedup.h kw_cdx_*; csrc/cdx.hip)
+    def cdx_begin(self) -> None:
+        """Empty the handle's row store."""
+        self._check(_native.lib().kw_cdx_begin(self.h))
+
+    def cdx_text_device(self, data):
+        """The text as a device tensor kw_cdx_append takes (16-byte aligned, padded), and its length: bytes-like,
+        a uint8 numpy array or a uint8 device tensor."""
+        t = self.torch
+        dev = t.device('cuda', self.device)
+        if isinstance(data, t.Tensor):
+            src = data.to(dev).contiguous().view(-1)
+        else:
+            a = data if isinstance(data, np.ndarray) else np.frombuffer(bytearray(data), dtype=np.uint8)
+            src = t.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+        d = t.empty(src.numel() + ARENA_PAD, dtype=t.uint8, device=dev)
+        d[:src.numel()].copy_(src)
+        return d, int(src.numel())
+
+    def cdx_append(self, data, dialect='listing') -> Tuple[int, int, int]:
+        """Parse one text on the device and append its rows to the store: (verdict KW_CDX_*, offending line or
+        -1, rows appended).  Nothing is appended unless the verdict is KW_CDX_OK."""
+        t = self.torch
+        d_text, n = self.cdx_text_device(data)
+        dia = dialect if isinstance(dialect, _native.CdxDialect) else _native.CdxDialect(*CDX_DIALECTS[dialect])
+        rows, verdict, bad = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+        st = t.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_append(self.h, _native.ptr(d_text), n, ctypes.byref(dia), ctypes.byref(rows),
+                                                ctypes.byref(verdict), ctypes.byref(bad),
+                                                ctypes.c_void_p(st.cuda_stream)))
+        return int(verdict.value), int(bad.value), int(rows.value)
+
+    def cdx_rows(self):
+        """The store on the host: (URL arena bytes, offsets [n + 1], timestamps [n])."""
+        t = self.torch
+        n, nb = ctypes.c_int64(), ctypes.c_int64()
+        self._check(_native.lib().kw_cdx_rows(self.h, ctypes.byref(n), ctypes.byref(nb)))
+        dev = t.device('cuda', self.device)
+        a = t.empty(max(nb.value, 1), dtype=t.uint8, device=dev)
+        o = t.zeros(n.value + 1, dtype=t.int64, device=dev)
+        ts = t.empty(max(n.value, 1), dtype=t.int64, device=dev)
+        st = t.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_store_copy(self.h, _native.ptr(a), _native.ptr(o), _native.ptr(ts),
+                                                    ctypes.c_void_p(st.cuda_stream)))
+        st.synchronize()
+        return a[:nb.value].cpu().numpy().tobytes(), o.cpu().numpy(), ts[:n.value].cpu().numpy()
+
+    def cdx_run(self, normalize: bool = True) -> None:
+        """kw_dedup_run over the store; counts() and kept() then describe this run."""
+        st = self.torch.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_run(self.h, _native.KW_DEDUP_NORMALIZE if normalize else 0,
+                                             ctypes.c_void_p(st.cuda_stream)))
+
+    def cdx_csv(self) -> bytes:
+        """The last cdx_run's kept rows as the bytes of ``to_csv(index=False)`` (columns date_time, url),
+        rendered on the device."""
+        t = self.torch
+        st = t.cuda.current_stream(self.device)
+        nb = ctypes.c_int64()
+        self._check(_native.lib().kw_cdx_csv_size(self.h, ctypes.byref(nb), ctypes.c_void_p(st.cuda_stream)))
+        out = t.empty(nb.value + 16, dtype=t.uint8, device=t.device('cuda', self.device))
+        self._check(_native.lib().kw_cdx_csv_copy(self.h, _native.ptr(out), ctypes.c_void_p(st.cuda_stream)))
+        return out[:nb.value].cpu().numpy().tobytes()
+
+    def cdx_last_ms(self) -> List[float]:
+        """Device times (ms): parse and compaction (summed over the appends since cdx_begin), the last render."""
+        v = np.zeros(3, dtype=np.float32)
+        self._check(_native.lib().kw_cdx_last_ms(self.h, _native.ptr(v), 3))
+        return [float(x) for x in v]
+
+    @staticmethod
+    def cdx_tile_bytes() -> int:
+        return int(_native.lib().kw_cdx_tile_bytes())
+
     def dedup_strings(self, urls: Sequence[str], normalize: bool = True) -> Tuple[np.ndarray, List[str]]:
         """Pack, upload, classify: (kept row indices, their normalised URLs)."""
         arena, off = pack_urls(urls)
@@ -163,16 +249,94 @@ def dedup_frame(df, normalize: bool = True):
     return out
 
 
+def native_enabled() -> bool:
+    """The device parse + render route is on unless ``KW_CDX_NATIVE=0`` (then: pandas parse and to_csv, for A/B
+    runs and tests).  Output files are byte-identical on either route."""
+    return os.environ.get('KW_CDX_NATIVE', '1') != '0'
+
+
+def _file_bytes(path: str) -> Optional[np.ndarray]:
+    try:
+        return np.fromfile(path, dtype=np.uint8)
+    except (OSError, ValueError):
+        return None   # the pandas route raises the reference's error
+
+
+def _native_part(txt_path: str) -> Optional[bytes]:
+    """The part CSV's bytes when the listing is eligible (the rule: DESIGN.md §7), else None."""
+    data = _file_bytes(txt_path)
+    if data is None:
+        return None
+    g = _dedup()
+    g.cdx_begin()
+    verdict, _, rows = g.cdx_append(data, 'listing')
+    if verdict != _native.KW_CDX_OK or rows == 0:   # (no rows: left to pandas, which decides what an empty file is)
+        return None
+    g.cdx_run(normalize=True)
+    return g.cdx_csv()
+
+
 def process_part(txt_path: str, csv_path: str) -> None:
     """yahoo_links_selenium.py:59-82 for one scraped CDX listing."""
+    if native_enabled():
+        csv = _native_part(txt_path)
+        if csv is not None:
+            with open(csv_path, 'wb') as fh:
+                fh.write(csv)
+            return
     dedup_frame(read_cdx(txt_path)).to_csv(csv_path, index=False)
+
+
+def _native_merge(files: Sequence[str]):
+    """(messages of the unreadable parts, parts appended, merged CSV bytes, kept rows) when every readable part
+    is eligible, else None.  A part the device parser does not take is read with pandas: one that raises is
+    unreadable (skipped, as the reference does), one that reads sends the whole merge down the pandas route."""
+    import pandas as pd
+    g = None   # (the handle only once a part has bytes: without parts the reference's messages need no GPU)
+    errors, parts = [], 0
+    for f in files:
+        data = _file_bytes(f)
+        verdict = -1
+        if data is not None and len(data):
+            if g is None:
+                g = _dedup()
+                g.cdx_begin()
+            verdict = g.cdx_append(data, 'part')[0]
+        if verdict == _native.KW_CDX_OK:
+            parts += 1
+            continue
+        try:
+            pd.read_csv(f)
+        except Exception as e:
+            errors.append(f"Error reading {f}: {e}")
+            continue
+        return None
+    if not parts:
+        return errors, 0, b'', 0
+    g.cdx_run(normalize=False)
+    csv = g.cdx_csv()
+    return errors, parts, csv, g.counts()[_native.KW_URL_KEPT]
 
 
 def merge_parts(folder: str = 'yahoo_links_1', out: str = 'yfin_urls.csv') -> Optional[int]:
     """yahoo_links_selenium.py:160-179: part CSVs in glob order, concat, keep-first."""
     import pandas as pd
+    files = glob.glob(os.path.join(folder, '*.csv'))
+    res = _native_merge(files) if native_enabled() else None
+    if res is not None:
+        errors, parts, csv, kept = res
+        for line in errors:
+            print(line)
+        if not parts:
+            print("No CSV files were processed. Check if the scraping was successful.")
+            return None
+        print(f"Found {kept} unique URLs")
+        with open(out, 'wb') as fh:
+            fh.write(csv)
+        print(f"Results saved to {out}")
+        return kept
     dfs = []
-    for f in glob.glob(os.path.join(folder, '*.csv')):
+    for f in files:
         try:
             dfs.append(pd.read_csv(f))
         except Exception as e:  # the reference prints and skips unreadable parts (:168-169)

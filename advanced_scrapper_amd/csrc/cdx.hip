@@ -1,0 +1,846 @@
+// libkwmatch: CDX listings parsed into the dedup's row store and the kept rows rendered as CSV, on the device
+// (include/kwdedup.h, kw_cdx_*).
+//
+// Reference: yahoo_links_selenium.py:59 (read_csv of a listing), :82 / :176 (to_csv), :164-167 (read_csv of the
+// part CSVs); the rule under which a text is taken at all is restated in tests/cdx_rule.py.
+//
+//   cx_lines_kernel<false>  one block a tile of TILE bytes, 16 bytes a lane in one coalesced load: '\n', '"',
+//                           '\r' and NUL bytes as 16-bit masks; a byte starts a row when it is not '\n' and the
+//                           byte before it is (or it is the text's first), so blank-line runs and lines longer
+//                           than a tile need nothing special.  Rows per tile; the first '"' / '\r' / NUL position.
+//   cx_scan_*               exclusive scan of 64-bit counts in two levels (chunk sums, their scan in one block,
+//                           each chunk from its prefix; as dd_tile_sums / dd_scan_tiles), used for the rows per
+//                           tile, the URL lengths and the CSV line lengths.
+//   cx_lines_kernel<true>   the same masks again: every row's start position, at its rank.
+//   cx_parse_kernel         lane = row, 8 bytes a step with per-byte masks: fields counted, the timestamp and URL
+//                           cells located, UTF-8 validated (bytewise only in words with a byte >= 0x80), ':'
+//                           looked for in the URL cell, the digits parsed.  The first offending line by atomicMin
+//                           of (line start, condition).
+//   cx_off_kernel           the rows' arena offsets from the scanned URL lengths.
+//   cx_fill_kernel          destination-major copy: a lane owns one aligned 16-byte chunk of the output, finds
+//                           the segment (row / CSV line) under it by binary search in the offsets (narrowed per
+//                           block), gathers its bytes and stores them at once.  With ArenaGen it compacts the
+//                           URL cells into the arena, with CsvGen it writes the CSV.
+//   cx_linelen_kernel       lane = kept row: decimal digits of the timestamp, the URL's length, whether it holds
+//                           a ',' (then it is quoted).
+//
+// Kernels hand data to each other only across launches.  All byte work: the roofline is HBM bandwidth.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "kwdedup_handle.hpp"
+
+namespace cx {
+
+constexpr int BLOCK = 256;
+constexpr int TILE = BLOCK * 16;     // bytes of text a block classifies at once
+constexpr int SCAN_CHUNKS = 512;
+constexpr unsigned long long NONE = ~0ull;
+constexpr int HEADER_LEN = 14;       // "date_time,url\n"
+__constant__ const char HEADER[HEADER_LEN + 2] = "date_time,url\n";
+static const char HEADER_HOST[HEADER_LEN + 2] = "date_time,url\n";
+
+// priorities of the line conditions inside one line (the low 3 bits of Errs::line)
+enum { P_HEADER = 0, P_UTF8 = 1, P_FIELDS = 2, P_TS = 3, P_URL = 4 };
+
+struct Errs {
+    unsigned long long quote, cr, nul;   // position of the first such byte (NONE)
+    unsigned long long line;             // min over offending lines of (line start << 3 | condition) (NONE)
+};
+
+struct Dialect {
+    uint32_t delim;
+    int ts_col, url_col, skip, exact;
+};
+
+__device__ __forceinline__ uint32_t eq4(uint32_t v, uint32_t pat)   // 0x80 in exactly the bytes equal to pat's
+{
+    const uint32_t d = v ^ pat;
+    return ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
+}
+__device__ __forceinline__ uint64_t eq8(uint64_t v, uint64_t pat)
+{
+    const uint64_t d = v ^ pat;
+    return ~(((d & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | d) & 0x8080808080808080ull;
+}
+__device__ __forceinline__ uint32_t bits4(uint32_t m) { return (((m >> 7) & 0x01010101u) * 0x01020408u) >> 24; }
+// bit k set iff byte k of the 16 equals c
+__device__ __forceinline__ uint32_t mask16(uint4 v, uint32_t c)
+{
+    const uint32_t pat = c * 0x01010101u;
+    return bits4(eq4(v.x, pat)) | (bits4(eq4(v.y, pat)) << 4) | (bits4(eq4(v.z, pat)) << 8) | (bits4(eq4(v.w, pat)) << 12);
+}
+
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long x)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long y = __shfl_xor(x, d, 64);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+// exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
+__device__ __forceinline__ unsigned long long block_scan(unsigned long long x, unsigned long long *ws,
+                                                         unsigned long long *total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned long long inc = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long y = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += y;
+    }
+    __syncthreads();   // ws free again
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (int k = 0; k < BLOCK / 64; ++k) {
+        const unsigned long long s = ws[k];
+        if (k < wv) before += s;
+        all += s;
+    }
+    *total = all;
+    return before + inc - x;
+}
+
+// The text's rows: a row starts at a byte that is not '\n' and follows a '\n' (or starts the text).
+// WRITE = false: rows per tile into tile_cnt, the first '"', '\r', NUL into errs.
+// WRITE = true:  tile_cnt holds the tiles' exclusive prefix; every row's start goes to row_start at its rank.
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK) void cx_lines_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t ntiles,
+                                                         unsigned long long *__restrict__ tile_cnt,
+                                                         Errs *__restrict__ errs, int64_t *__restrict__ row_start)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t p = tile * TILE + (int64_t)threadIdx.x * 16;
+        uint32_t starts = 0;
+        unsigned long long eq = NONE, ec = NONE, ez = NONE;
+        if (p < n) {
+            // (the text is readable up to the next multiple of 16 past n: kw_cdx_append's contract)
+            const uint4 v = *(const uint4 *)(text + p);
+            const uint32_t valid = n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u;
+            const uint32_t nl = mask16(v, 0x0Au) & valid;
+            const uint32_t prev_nl = (p == 0 || text[p - 1] == 0x0A) ? 1u : 0u;
+            starts = ~nl & ((nl << 1) | prev_nl) & valid;
+            if (!WRITE) {
+                const uint32_t q = mask16(v, 0x22u) & valid, c = mask16(v, 0x0Du) & valid, z = mask16(v, 0u) & valid;
+                if (q) eq = (unsigned long long)p + __builtin_ctz(q);
+                if (c) ec = (unsigned long long)p + __builtin_ctz(c);
+                if (z) ez = (unsigned long long)p + __builtin_ctz(z);
+            }
+        }
+        if (!WRITE) {
+            if (__any((eq & ec & ez) != NONE)) {   // (rare: one atomic a wave and condition)
+                eq = wave_min(eq);
+                ec = wave_min(ec);
+                ez = wave_min(ez);
+                if ((threadIdx.x & 63) == 0) {
+                    if (eq != NONE) atomicMin(&errs->quote, eq);
+                    if (ec != NONE) atomicMin(&errs->cr, ec);
+                    if (ez != NONE) atomicMin(&errs->nul, ez);
+                }
+            }
+        }
+        unsigned long long total;
+        const unsigned long long before = block_scan((unsigned long long)__popc(starts), ws, &total);
+        if (!WRITE) {
+            if (threadIdx.x == 0) tile_cnt[tile] = total;
+        } else {
+            unsigned long long r = tile_cnt[tile] + before;
+            while (starts) {
+                row_start[r++] = p + __builtin_ctz(starts);
+                starts &= starts - 1u;
+            }
+        }
+    }
+}
+
+// ---- exclusive scan of m 64-bit values in place, in two levels: chunk c = values [c * per, (c + 1) * per)
+__global__ __launch_bounds__(BLOCK) void cx_scan_sums_kernel(const unsigned long long *__restrict__ a, int64_t m,
+                                                             int64_t per, unsigned long long *__restrict__ chunk)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
+    unsigned long long s = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) s += a[i];
+    unsigned long long total;
+    (void)block_scan(s, ws, &total);
+    if (threadIdx.x == 0) chunk[blockIdx.x] = total;
+}
+
+// one block: the chunk sums' exclusive scan in place (nchunk <= SCAN_CHUNKS = 2 * BLOCK), the grand total
+__global__ __launch_bounds__(BLOCK) void cx_scan_chunks_kernel(unsigned long long *__restrict__ chunk, int nchunk,
+                                                               unsigned long long *__restrict__ grand)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    const int i0 = 2 * (int)threadIdx.x, i1 = i0 + 1;
+    const unsigned long long x0 = i0 < nchunk ? chunk[i0] : 0ull, x1 = i1 < nchunk ? chunk[i1] : 0ull;
+    unsigned long long total;
+    const unsigned long long before = block_scan(x0 + x1, ws, &total);
+    if (i0 < nchunk) chunk[i0] = before;
+    if (i1 < nchunk) chunk[i1] = before + x0;
+    if (threadIdx.x == 0) *grand = total;
+}
+
+__global__ __launch_bounds__(BLOCK) void cx_scan_apply_kernel(unsigned long long *__restrict__ a, int64_t m, int64_t per,
+                                                              const unsigned long long *__restrict__ chunk)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
+    unsigned long long carry = chunk[blockIdx.x];
+    for (int64_t i0 = lo; i0 < hi; i0 += BLOCK) {   // (block-uniform trip count)
+        const int64_t i = i0 + threadIdx.x;
+        const unsigned long long x = i < hi ? a[i] : 0ull;
+        unsigned long long total;
+        const unsigned long long before = block_scan(x, ws, &total);
+        if (i < hi) a[i] = carry + before;
+        carry += total;
+    }
+}
+
+// One row: fields, cells, UTF-8, digits.  Row r of the text starts at row_start[r] and ends before the next
+// '\n' (or at n).  With D.skip row 0 is the header line; rows are written at r - D.skip.
+__global__ __launch_bounds__(BLOCK) void cx_parse_kernel(const uint8_t *__restrict__ text, int64_t n,
+                                                         const int64_t *__restrict__ row_start, int64_t n_lines,
+                                                         Dialect D, int64_t *__restrict__ ts_out,
+                                                         int64_t *__restrict__ url_pos,
+                                                         unsigned long long *__restrict__ url_len,
+                                                         Errs *__restrict__ errs)
+{
+    constexpr uint64_t ONES = 0x0101010101010101ull, HI = 0x8080808080808080ull;
+    for (int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x; r < n_lines; r += (int64_t)gridDim.x * BLOCK) {
+        const int64_t s = row_start[r];
+        if (D.skip && r == 0) {
+            // the header: the text's first HEADER_LEN - 1 bytes, then '\n' or the end
+            bool ok = s == 0 && n >= HEADER_LEN - 1 && (n == HEADER_LEN - 1 || text[HEADER_LEN - 1] == 0x0A);
+            for (int k = 0; ok && k < HEADER_LEN - 1; ++k) ok = text[k] == (uint8_t)HEADER[k];
+            if (!ok) atomicMin(&errs->line, (unsigned long long)P_HEADER);
+            continue;
+        }
+        int f = 0, need = 0;
+        uint32_t lo = 0x80u, hi = 0xBFu;
+        bool bad8 = false, colon = false;
+        int64_t ts_s = D.ts_col == 0 ? s : -1, ts_e = -1, u_s = D.url_col == 0 ? s : -1, u_e = -1, end = -1;
+        for (int64_t w = s & ~(int64_t)7; end < 0; w += 8) {
+            if (w >= n) { end = n; break; }
+            // (aligned 8 bytes at w < n: inside the text's readable 16-byte granule)
+            const uint64_t v = *(const uint64_t *)(text + w);
+            const int b0 = w < s ? (int)(s - w) : 0;
+            const int b1 = n - w >= 8 ? 8 : (int)(n - w);
+            const uint64_t from = ~((1ull << (8 * b0)) - 1ull);
+            const uint64_t nlm = eq8(v, 0x0Aull * ONES) & from & (b1 == 8 ? ~0ull : (1ull << (8 * b1)) - 1ull);
+            const int e = nlm ? (__builtin_ctzll(nlm) >> 3) : b1;   // the row's bytes of this word: [b0, e)
+            const uint64_t in = HI & from & (e == 8 ? ~0ull : (1ull << (8 * e)) - 1ull);
+            if (need || (v & in)) {
+                for (int k = b0; k < e; ++k) {
+                    const uint32_t c = (uint32_t)(v >> (8 * k)) & 0xFFu;
+                    if (need) {
+                        if (c < lo || c > hi) bad8 = true;
+                        --need;
+                        lo = 0x80u; hi = 0xBFu;
+                    } else if (c >= 0x80u) {
+                        if (c >= 0xC2u && c <= 0xDFu) need = 1;
+                        else if (c == 0xE0u) { need = 2; lo = 0xA0u; }
+                        else if (c == 0xEDu) { need = 2; hi = 0x9Fu; }
+                        else if (c >= 0xE1u && c <= 0xEFu) need = 2;
+                        else if (c == 0xF0u) { need = 3; lo = 0x90u; }
+                        else if (c >= 0xF1u && c <= 0xF3u) need = 3;
+                        else if (c == 0xF4u) { need = 3; hi = 0x8Fu; }
+                        else bad8 = true;
+                    }
+                }
+            }
+            uint64_t ev = (eq8(v, (uint64_t)D.delim * ONES) | eq8(v, 0x3Aull * ONES)) & in;
+            while (ev) {
+                const int k = __builtin_ctzll(ev) >> 3;
+                ev &= ev - 1ull;
+                const int64_t pos = w + k;
+                if (((uint32_t)(v >> (8 * k)) & 0xFFu) == D.delim) {
+                    if (f == D.ts_col) ts_e = pos;
+                    if (f == D.url_col) u_e = pos;
+                    ++f;
+                    if (f == D.ts_col) ts_s = pos + 1;
+                    if (f == D.url_col) u_s = pos + 1;
+                } else {
+                    colon |= f == D.url_col;
+                }
+            }
+            if (nlm) end = w + e;
+        }
+        if (need) bad8 = true;
+        if (f == D.ts_col) ts_e = end;
+        if (f == D.url_col) u_e = end;
+        const int fields = f + 1;
+        const int least = (D.ts_col > D.url_col ? D.ts_col : D.url_col) + 1;
+        int cond = -1;
+        int64_t ts = 0;
+        if (bad8) cond = P_UTF8;
+        else if (D.exact ? fields != D.exact : fields < least) cond = P_FIELDS;
+        else {
+            const int64_t tl = ts_e - ts_s;
+            bool ok = tl >= 1 && tl <= 18;
+            for (int64_t k = ts_s; ok && k < ts_e; ++k) {
+                const uint32_t c = text[k];
+                ok = c >= 0x30u && c <= 0x39u;
+                ts = ts * 10 + (int64_t)(c - 0x30u);
+            }
+            if (!ok) cond = P_TS;
+            else if (!colon) cond = P_URL;
+        }
+        if (cond >= 0) {
+            atomicMin(&errs->line, ((unsigned long long)s << 3) | (unsigned long long)cond);
+            continue;
+        }
+        const int64_t o = r - D.skip;
+        ts_out[o] = ts;
+        url_pos[o] = u_s;
+        url_len[o] = (unsigned long long)(u_e - u_s);
+    }
+}
+
+// off[r] = base + the scanned URL lengths (r < m), off[m] = base + their total
+__global__ __launch_bounds__(BLOCK) void cx_off_kernel(int64_t *__restrict__ off, const unsigned long long *__restrict__ excl,
+                                                       const unsigned long long *__restrict__ grand, int64_t m, int64_t base)
+{
+    for (int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x; r <= m; r += (int64_t)gridDim.x * BLOCK)
+        off[r] = base + (int64_t)(r < m ? excl[r] : *grand);
+}
+
+// '\n' bytes in text[0, end): the line number of a position
+__global__ __launch_bounds__(BLOCK) void cx_count_nl_kernel(const uint8_t *__restrict__ text, int64_t end,
+                                                            unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    unsigned long long c = 0;
+    for (int64_t p = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * 16; p < end; p += (int64_t)gridDim.x * BLOCK * 16) {
+        const uint4 v = *(const uint4 *)(text + p);
+        const uint32_t valid = end - p >= 16 ? 0xFFFFu : (1u << (int)(end - p)) - 1u;
+        c += (unsigned long long)__popc(mask16(v, 0x0Au) & valid);
+    }
+    unsigned long long total;
+    (void)block_scan(c, ws, &total);
+    if (threadIdx.x == 0 && total) atomicAdd(out, total);
+}
+
+// largest s in [a, b) with off[s] <= p (off[a] <= p)
+__device__ __forceinline__ int64_t seg_find(const int64_t *__restrict__ off, int64_t a, int64_t b, int64_t p)
+{
+    while (b - a > 1) {
+        const int64_t mid = a + ((b - a) >> 1);
+        if (off[mid] <= p) a = mid; else b = mid;
+    }
+    return a;
+}
+
+// Destination-major write of m segments: segment s is out[off[s], off[s + 1]) and its byte j is
+// g.byte(g.open(s), j).  out is 16-byte aligned; a lane owns the aligned 16-byte chunk c (bytes outside
+// [off[0], off[m]) are left alone: the first and the last chunk are written bytewise when partial).
+template <class Gen>
+__global__ __launch_bounds__(BLOCK) void cx_fill_kernel(uint8_t *__restrict__ out, const int64_t *__restrict__ off,
+                                                        int64_t m, Gen g)
+{
+    __shared__ int64_t rng[2];
+    const int64_t lo = off[0], hi = off[m];
+    const int64_t c0 = lo >> 4, c1 = (hi + 15) >> 4;
+    for (int64_t cb = c0 + (int64_t)blockIdx.x * BLOCK; cb < c1; cb += (int64_t)gridDim.x * BLOCK) {
+        __syncthreads();   // rng free again
+        if (threadIdx.x == 0) {   // the block's chunks lie under segments [rng[0], rng[1]]
+            const int64_t pf = cb * 16 > lo ? cb * 16 : lo;
+            const int64_t pe = (cb + BLOCK) * 16 < hi ? (cb + BLOCK) * 16 : hi;
+            rng[0] = seg_find(off, 0, m, pf);
+            rng[1] = seg_find(off, rng[0], m, pe - 1);
+        }
+        __syncthreads();
+        const int64_t c = cb + threadIdx.x;
+        int64_t p = c * 16 > lo ? c * 16 : lo;
+        const int64_t e = c * 16 + 16 < hi ? c * 16 + 16 : hi;
+        if (p >= e) continue;   // (every thread still reaches both barriers of the next round: none inside)
+        const int64_t p0 = p;
+        int64_t s = seg_find(off, rng[0], rng[1] + 1, p);
+        uint64_t a = 0, b = 0;
+        while (p < e) {
+            const int64_t so = off[s], se = off[s + 1];
+            if (se <= p) { ++s; continue; }   // (an empty segment)
+            const auto ctx = g.open(s);
+            const int64_t stop = se < e ? se : e;
+            for (int64_t j = p - so; p < stop; ++p, ++j) {
+                const uint64_t x = g.byte(ctx, j);
+                const int k = (int)(p - c * 16);
+                if (k < 8) a |= x << (8 * k); else b |= x << (8 * (k - 8));
+            }
+            ++s;
+        }
+        if (e - p0 == 16) {
+            *(uint4 *)(out + c * 16) = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+        } else {
+            for (int64_t q = p0; q < e; ++q) {
+                const int k = (int)(q - c * 16);
+                out[q] = (uint8_t)(k < 8 ? a >> (8 * k) : b >> (8 * (k - 8)));
+            }
+        }
+    }
+}
+
+// segment r (a row being appended) = its URL cell in the text
+struct ArenaGen {
+    const uint8_t *text;
+    const int64_t *url_pos;
+    __device__ __forceinline__ const uint8_t *open(int64_t s) const { return text + url_pos[s]; }
+    __device__ __forceinline__ uint64_t byte(const uint8_t *src, int64_t j) const { return src[j]; }
+};
+
+__device__ __forceinline__ int dec_digits(int64_t v)   // v in [0, 10^18)
+{
+    int d = 1;
+    for (int64_t t = 10; d < 18 && v >= t; t *= 10) ++d;
+    return d;
+}
+
+// segment 0 = the header line, segment k + 1 = kept row k: decimal(ts) ',' ['"'] url ['"'] '\n'
+struct CsvGen {
+    const int64_t *ts, *kept_row, *kept_off;
+    const uint8_t *kept_bytes, *quoted;
+    struct Ctx {
+        int64_t ts, ulen;
+        const uint8_t *url;
+        int nd, q;
+    };
+    __device__ __forceinline__ Ctx open(int64_t s) const
+    {
+        Ctx c{0, 0, nullptr, 0, 0};
+        if (s == 0) { c.nd = -1; return c; }
+        const int64_t k = s - 1;
+        c.ts = ts[kept_row[k]];
+        c.nd = dec_digits(c.ts);
+        c.url = kept_bytes + kept_off[k];
+        c.ulen = kept_off[k + 1] - kept_off[k];
+        c.q = quoted[k];
+        return c;
+    }
+    __device__ __forceinline__ uint64_t byte(const Ctx &c, int64_t j) const
+    {
+        if (c.nd < 0) return (uint64_t)(uint8_t)HEADER[j];
+        if (j < c.nd) {
+            int64_t v = c.ts;
+            for (int t = c.nd - 1 - (int)j; t > 0; --t) v /= 10;
+            return (uint64_t)(0x30 + v % 10);
+        }
+        j -= c.nd;
+        if (j == 0) return 0x2Cull;
+        j -= 1;
+        if (c.q) {
+            if (j == 0 || j == c.ulen + 1) return 0x22ull;
+            j -= 1;
+        }
+        return j < c.ulen ? (uint64_t)c.url[j] : 0x0Aull;
+    }
+};
+
+// seglen[0] = the header's length, seglen[k + 1] = the length of kept row k's line; quoted[k] = its URL has a ','
+__global__ __launch_bounds__(BLOCK) void cx_linelen_kernel(int64_t n_kept, const int64_t *__restrict__ ts,
+                                                           const int64_t *__restrict__ kept_row,
+                                                           const int64_t *__restrict__ kept_off,
+                                                           const uint8_t *__restrict__ kept_bytes,
+                                                           unsigned long long *__restrict__ seglen,
+                                                           uint8_t *__restrict__ quoted)
+{
+    constexpr uint64_t ONES = 0x0101010101010101ull;
+    for (int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x; k < n_kept; k += (int64_t)gridDim.x * BLOCK) {
+        const int64_t b = kept_off[k], e = kept_off[k + 1];
+        bool comma = false;
+        // (aligned 8 bytes under [b, e): inside the kept bytes and their padding)
+        for (int64_t w = b & ~(int64_t)7; w < e && !comma; w += 8) {
+            const uint64_t v = *(const uint64_t *)(kept_bytes + w);
+            const int b0 = w < b ? (int)(b - w) : 0;
+            const int b1 = e - w >= 8 ? 8 : (int)(e - w);
+            const uint64_t in = ~((1ull << (8 * b0)) - 1ull) & (b1 == 8 ? ~0ull : (1ull << (8 * b1)) - 1ull);
+            comma = (eq8(v, 0x2Cull * ONES) & in) != 0;
+        }
+        quoted[k] = comma ? 1 : 0;
+        seglen[k + 1] = (unsigned long long)(dec_digits(ts[kept_row[k]]) + 1 + (e - b) + (comma ? 2 : 0) + 1);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) seglen[0] = HEADER_LEN;
+}
+
+}  // namespace cx
+
+using namespace cx;
+
+struct kw_cdx_store {
+    // the rows: arena (URL bytes; 64 readable bytes past n_bytes), off (n + 1), ts (n)
+    uint8_t *arena = nullptr;
+    size_t arena_cap = 0;
+    int64_t *off = nullptr, *ts = nullptr;
+    size_t rows_cap = 0;
+    int64_t n = 0, n_bytes = 0;
+    uint8_t *code = nullptr;
+    size_t code_cap = 0;
+    // append scratch
+    void *d_tiles = nullptr;
+    size_t tiles_bytes = 0;
+    void *d_rows = nullptr;
+    size_t rows_bytes = 0;
+    // render
+    void *d_csv = nullptr;       // segment offsets (n_kept + 2) + quoted flags
+    size_t csv_scratch = 0;
+    int64_t csv_bytes = 0, csv_kept = 0;
+    uint64_t run_serial = 0;     // the kw_dedup_run kw_cdx_run made (0: none since the store changed)
+    bool csv_ready = false;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float ms[3] = {0.f, 0.f, 0.f};
+};
+
+void kw_cdx_store_destroy(kw_cdx_store *s)
+{
+    if (!s) return;
+    if (s->arena) (void)hipFree(s->arena);
+    if (s->off) (void)hipFree(s->off);
+    if (s->ts) (void)hipFree(s->ts);
+    if (s->code) (void)hipFree(s->code);
+    if (s->d_tiles) (void)hipFree(s->d_tiles);
+    if (s->d_rows) (void)hipFree(s->d_rows);
+    if (s->d_csv) (void)hipFree(s->d_csv);
+    for (auto &e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static int store_get(kw_dedup *h, kw_cdx_store **out)
+{
+    if (!h->cdx) {
+        kw_cdx_store *s = new kw_cdx_store();
+        h->cdx = s;
+        for (auto &e : s->ev) DDCHK(h, hipEventCreate(&e));
+    }
+    *out = h->cdx;
+    return KW_OK;
+}
+
+// a scratch buffer of at least `bytes`
+static int scratch_fit(kw_dedup *h, void **buf, size_t *have, size_t bytes)
+{
+    if (bytes <= *have) return KW_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    bytes += bytes / 4;
+    DDCHK(h, hipMalloc(buf, bytes));
+    *have = bytes;
+    return KW_OK;
+}
+
+// a store buffer of at least `need` bytes that keeps its first `used` bytes
+static int grow_keep(kw_dedup *h, void **buf, size_t *cap, size_t need, size_t used, hipStream_t st)
+{
+    if (need <= *cap) return KW_OK;
+    const size_t want = std::max(need, *cap * 2);
+    void *nb = nullptr;
+    DDCHK(h, hipMalloc(&nb, want));
+    if (*buf && used) {
+        hipError_t e = hipMemcpyAsync(nb, *buf, used, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            (void)hipFree(nb);
+            h->err = std::string("HIP error ") + hipGetErrorString(e) + " growing the row store";
+            return KW_EHIP;
+        }
+    }
+    if (*buf) (void)hipFree(*buf);
+    *buf = nb;
+    *cap = want;
+    return KW_OK;
+}
+
+// exclusive scan of a[0, m) in place; *d_grand (device) receives the total.  chunk: SCAN_CHUNKS words of scratch
+static void scan_launch(unsigned long long *a, int64_t m, unsigned long long *chunk, unsigned long long *d_grand,
+                        hipStream_t st)
+{
+    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(SCAN_CHUNKS, (m + 4 * BLOCK - 1) / (4 * BLOCK)));
+    const int64_t per = std::max<int64_t>(1, (m + nchunk - 1) / nchunk);
+    hipLaunchKernelGGL(cx_scan_sums_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st, (const unsigned long long *)a, m,
+                       per, chunk);
+    hipLaunchKernelGGL(cx_scan_chunks_kernel, dim3(1), dim3(BLOCK), 0, st, chunk, (int)nchunk, d_grand);
+    hipLaunchKernelGGL(cx_scan_apply_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st, a, m, per,
+                       (const unsigned long long *)chunk);
+}
+
+static int grid_for(const kw_dedup *h, int64_t items)
+{
+    return (int)std::max<int64_t>(1, std::min<int64_t>((items + BLOCK - 1) / BLOCK, (int64_t)h->cus * 16));
+}
+
+// the line (the '\n' bytes before it) of byte position pos
+static int line_of(kw_dedup *h, const uint8_t *d_text, int64_t pos, unsigned long long *d_cnt, hipStream_t st,
+                   int64_t *line)
+{
+    unsigned long long c = 0;
+    DDCHK(h, hipMemsetAsync(d_cnt, 0, 8, st));
+    if (pos > 0) {
+        hipLaunchKernelGGL(cx_count_nl_kernel, dim3(grid_for(h, (pos + 15) / 16)), dim3(BLOCK), 0, st, d_text, pos, d_cnt);
+        DDCHK(h, hipGetLastError());
+    }
+    DDCHK(h, hipMemcpyAsync(&c, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    *line = (int64_t)c;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_tile_bytes(void) { return TILE; }
+
+extern "C" int kw_cdx_begin(kw_dedup *h)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    s->n = s->n_bytes = 0;
+    s->run_serial = 0;
+    s->csv_ready = false;
+    s->ms[0] = s->ms[1] = s->ms[2] = 0.f;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const kw_cdx_dialect *d,
+                             int64_t *n_rows, int32_t *verdict, int64_t *bad_line, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (!d || !n_rows || !verdict || !bad_line || n_bytes < 0 || (n_bytes > 0 && !d_text)) {
+        h->err = "kw_cdx_append: bad arguments";
+        return KW_EINVAL;
+    }
+    if (((uintptr_t)d_text & 15) != 0) { h->err = "kw_cdx_append: the text must be 16-byte aligned"; return KW_EINVAL; }
+    if ((d->delim != ' ' && d->delim != ',') || d->ts_col < 0 || d->url_col < 0 || d->ts_col == d->url_col ||
+        d->ts_col > 1023 || d->url_col > 1023 || d->skip_lines < 0 || d->skip_lines > 1 || d->exact_fields < 0 ||
+        (d->exact_fields && d->exact_fields <= std::max(d->ts_col, d->url_col))) {
+        h->err = "kw_cdx_append: unsupported dialect";
+        return KW_EINVAL;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    *n_rows = 0;
+    *verdict = KW_CDX_OK;
+    *bad_line = -1;
+    const Dialect D{(uint32_t)d->delim, d->ts_col, d->url_col, d->skip_lines, d->exact_fields};
+    if (n_bytes == 0) {
+        if (D.skip) { *verdict = KW_CDX_HEADER; *bad_line = 0; }
+        return KW_OK;
+    }
+    // ---- rows per tile, the byte conditions
+    const int64_t ntiles = (n_bytes + TILE - 1) / TILE;
+    rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, up256(8 * (size_t)ntiles) + up256(8 * SCAN_CHUNKS) + 256);
+    if (rc) return rc;
+    unsigned long long *tile_cnt = (unsigned long long *)s->d_tiles;
+    unsigned long long *chunk = (unsigned long long *)((uint8_t *)s->d_tiles + up256(8 * (size_t)ntiles));
+    unsigned long long *small = chunk + up256(8 * SCAN_CHUNKS) / 8;   // [0] a scan's total, [1] a line count, [4..8) Errs
+    Errs *errs = (Errs *)(small + 4);
+    DDCHK(h, hipMemsetAsync(small, 0xFF, 64, st));
+    DDCHK(h, hipEventRecord(s->ev[0], st));
+    const int tgrid = (int)std::min<int64_t>(ntiles, (int64_t)h->cus * 16);
+    hipLaunchKernelGGL(cx_lines_kernel<false>, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_cnt, errs,
+                       (int64_t *)nullptr);
+    scan_launch(tile_cnt, ntiles, chunk, small, st);
+    DDCHK(h, hipGetLastError());
+    unsigned long long hs[8];
+    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    const int64_t n_lines = (int64_t)hs[0];
+    for (int k = 0; k < 3; ++k) {
+        if (hs[4 + k] == NONE) continue;
+        *verdict = KW_CDX_QUOTE + k;
+        return line_of(h, d_text, (int64_t)hs[4 + k], small + 1, st, bad_line);
+    }
+    if (n_lines == 0) {
+        if (D.skip) { *verdict = KW_CDX_HEADER; *bad_line = 0; }
+        return KW_OK;
+    }
+    const int64_t n_new = n_lines - D.skip;
+    if (s->n + n_new >= ((int64_t)1 << 32)) { h->err = "kw_cdx_append: more than 2^32 - 1 rows"; return KW_EUNSUPPORTED; }
+    // ---- row starts, the rows parsed (timestamps straight into the store, past its rows)
+    {
+        size_t cap = s->rows_cap * 8, cap2 = s->rows_cap * 8;
+        const size_t need = 8 * ((size_t)(s->n + n_new) + 1);
+        rc = grow_keep(h, (void **)&s->off, &cap, need, 8 * ((size_t)s->n + 1), st);
+        if (!rc) rc = grow_keep(h, (void **)&s->ts, &cap2, cap, 8 * (size_t)s->n, st);
+        if (rc) return rc;
+        s->rows_cap = cap / 8;
+    }
+    rc = scratch_fit(h, &s->d_rows, &s->rows_bytes, 3 * up256(8 * ((size_t)n_lines + 1)));
+    if (rc) return rc;
+    int64_t *row_start = (int64_t *)s->d_rows;
+    int64_t *url_pos = (int64_t *)((uint8_t *)s->d_rows + up256(8 * ((size_t)n_lines + 1)));
+    unsigned long long *url_len = (unsigned long long *)((uint8_t *)s->d_rows + 2 * up256(8 * ((size_t)n_lines + 1)));
+    hipLaunchKernelGGL(cx_lines_kernel<true>, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_cnt, errs,
+                       row_start);
+    hipLaunchKernelGGL(cx_parse_kernel, dim3(grid_for(h, n_lines)), dim3(BLOCK), 0, st, d_text, n_bytes,
+                       (const int64_t *)row_start, n_lines, D, s->ts + s->n, url_pos, url_len, errs);
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipEventRecord(s->ev[1], st));
+    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    if (hs[7] != NONE) {
+        static const int32_t codes[5] = {KW_CDX_HEADER, KW_CDX_UTF8, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL};
+        *verdict = codes[std::min<unsigned long long>(hs[7] & 7, 4)];
+        return line_of(h, d_text, (int64_t)(hs[7] >> 3), small + 1, st, bad_line);
+    }
+    // ---- compaction: the URL lengths scanned, the offsets, the URL cells copied into the arena
+    int64_t total = 0;
+    if (n_new > 0) {
+        scan_launch(url_len, n_new, chunk, small, st);
+        DDCHK(h, hipGetLastError());
+        DDCHK(h, hipMemcpyAsync(hs, small, 8, hipMemcpyDeviceToHost, st));
+        DDCHK(h, hipStreamSynchronize(st));
+        total = (int64_t)hs[0];
+        rc = grow_keep(h, (void **)&s->arena, &s->arena_cap, (size_t)(s->n_bytes + total) + 64, (size_t)s->n_bytes, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(cx_off_kernel, dim3(grid_for(h, n_new + 1)), dim3(BLOCK), 0, st, s->off + s->n,
+                           (const unsigned long long *)url_len, (const unsigned long long *)small, n_new, s->n_bytes);
+        if (total > 0)
+            hipLaunchKernelGGL(cx_fill_kernel<ArenaGen>, dim3(grid_for(h, (total + 31) / 16)), dim3(BLOCK), 0, st, s->arena,
+                               (const int64_t *)(s->off + s->n), n_new, ArenaGen{d_text, url_pos});
+        DDCHK(h, hipGetLastError());
+    }
+    DDCHK(h, hipEventRecord(s->ev[2], st));
+    DDCHK(h, hipStreamSynchronize(st));
+    float a = 0.f, b = 0.f;
+    DDCHK(h, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+    DDCHK(h, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+    s->ms[0] += a;
+    s->ms[1] += b;
+    s->n += n_new;
+    s->n_bytes += total;
+    s->run_serial = 0;
+    s->csv_ready = false;
+    *n_rows = n_new;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_rows(kw_dedup *h, int64_t *n_rows, int64_t *n_bytes)
+{
+    if (!h || !n_rows || !n_bytes) return KW_EINVAL;
+    *n_rows = h->cdx ? h->cdx->n : 0;
+    *n_bytes = h->cdx ? h->cdx->n_bytes : 0;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_store_copy(kw_dedup *h, uint8_t *d_arena, int64_t *d_off, int64_t *d_ts, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    DDCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    kw_cdx_store *s = h->cdx;
+    if (!s || s->n == 0) {
+        if (d_off) DDCHK(h, hipMemsetAsync(d_off, 0, 8, st));
+        return KW_OK;
+    }
+    if (d_arena && s->n_bytes) DDCHK(h, hipMemcpyAsync(d_arena, s->arena, (size_t)s->n_bytes, hipMemcpyDeviceToDevice, st));
+    if (d_off) DDCHK(h, hipMemcpyAsync(d_off, s->off, 8 * ((size_t)s->n + 1), hipMemcpyDeviceToDevice, st));
+    if (d_ts) DDCHK(h, hipMemcpyAsync(d_ts, s->ts, 8 * (size_t)s->n, hipMemcpyDeviceToDevice, st));
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_run(kw_dedup *h, int32_t flags, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    DDCHK(h, hipSetDevice(h->device));
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    rc = scratch_fit(h, (void **)&s->code, &s->code_cap, (size_t)s->n + 64);
+    if (rc) return rc;
+    s->csv_ready = false;
+    s->run_serial = 0;
+    rc = kw_dedup_run(h, s->arena, s->off, s->n, flags, s->code, stream);
+    if (rc) return rc;
+    s->run_serial = h->run_serial;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_csv_size(kw_dedup *h, int64_t *n_bytes, void *stream)
+{
+    if (!h || !n_bytes) return KW_EINVAL;
+    kw_cdx_store *s = h->cdx;
+    if (!s || s->run_serial == 0 || s->run_serial != h->run_serial) {
+        h->err = "kw_cdx_csv_size: the last run was not kw_cdx_run over this store";
+        return KW_ESTATE;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    s->csv_kept = h->n_kept;
+    s->ms[2] = 0.f;
+    if (h->n_kept == 0) {
+        s->csv_bytes = HEADER_LEN;
+    } else {
+        const size_t nk = (size_t)h->n_kept;
+        int rc = scratch_fit(h, &s->d_csv, &s->csv_scratch, up256(8 * (nk + 2)) + up256(nk) + up256(8 * SCAN_CHUNKS) + 256);
+        if (rc) return rc;
+        unsigned long long *seg = (unsigned long long *)s->d_csv;
+        uint8_t *quoted = (uint8_t *)s->d_csv + up256(8 * (nk + 2));
+        unsigned long long *chunk = (unsigned long long *)(quoted + up256(nk));
+        unsigned long long *grand = chunk + up256(8 * SCAN_CHUNKS) / 8;
+        DDCHK(h, hipEventRecord(s->ev[3], st));
+        hipLaunchKernelGGL(cx_linelen_kernel, dim3(grid_for(h, h->n_kept)), dim3(BLOCK), 0, st, h->n_kept,
+                           (const int64_t *)s->ts, (const int64_t *)h->kept_row, (const int64_t *)h->kept_off,
+                           (const uint8_t *)h->kept_bytes, seg, quoted);
+        scan_launch(seg, h->n_kept + 1, chunk, grand, st);
+        DDCHK(h, hipGetLastError());
+        DDCHK(h, hipMemcpyAsync(seg + nk + 1, grand, 8, hipMemcpyDeviceToDevice, st));
+        unsigned long long tot = 0;
+        DDCHK(h, hipMemcpyAsync(&tot, grand, 8, hipMemcpyDeviceToHost, st));
+        DDCHK(h, hipEventRecord(s->ev[4], st));
+        DDCHK(h, hipStreamSynchronize(st));
+        DDCHK(h, hipEventElapsedTime(&s->ms[2], s->ev[3], s->ev[4]));
+        s->csv_bytes = (int64_t)tot;
+    }
+    s->csv_ready = true;
+    *n_bytes = s->csv_bytes;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_csv_copy(kw_dedup *h, uint8_t *d_out, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = h->cdx;
+    if (!s || !s->csv_ready || s->run_serial != h->run_serial) {
+        h->err = "kw_cdx_csv_copy: no kw_cdx_csv_size since the last kw_cdx_run";
+        return KW_ESTATE;
+    }
+    if (!d_out || ((uintptr_t)d_out & 15) != 0) { h->err = "kw_cdx_csv_copy: d_out must be 16-byte aligned"; return KW_EINVAL; }
+    DDCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (s->csv_kept == 0) {
+        DDCHK(h, hipMemcpyAsync(d_out, HEADER_HOST, HEADER_LEN, hipMemcpyHostToDevice, st));
+        DDCHK(h, hipStreamSynchronize(st));
+        return KW_OK;
+    }
+    const size_t nk = (size_t)s->csv_kept;
+    const uint8_t *quoted = (const uint8_t *)s->d_csv + up256(8 * (nk + 2));
+    DDCHK(h, hipEventRecord(s->ev[3], st));
+    hipLaunchKernelGGL(cx_fill_kernel<CsvGen>, dim3(grid_for(h, (s->csv_bytes + 31) / 16)), dim3(BLOCK), 0, st, d_out,
+                       (const int64_t *)s->d_csv, s->csv_kept + 1,
+                       CsvGen{(const int64_t *)s->ts, (const int64_t *)h->kept_row, (const int64_t *)h->kept_off,
+                              (const uint8_t *)h->kept_bytes, quoted});
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipEventRecord(s->ev[4], st));
+    DDCHK(h, hipStreamSynchronize(st));
+    float w = 0.f;
+    DDCHK(h, hipEventElapsedTime(&w, s->ev[3], s->ev[4]));
+    s->ms[2] += w;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_last_ms(kw_dedup *h, float *ms, int32_t k)
+{
+    if (!h || !ms || k < 0) return KW_EINVAL;
+    for (int i = 0; i < k && i < 3; ++i) ms[i] = h->cdx ? h->cdx->ms[i] : 0.f;
+    return KW_OK;
+}

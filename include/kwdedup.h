@@ -69,6 +69,74 @@ int kw_dedup_destroy(kw_dedup *h);
 /* One-shot form: d_keep_mask[i] = 1 iff row i is kept. */
 int dedup_urls(const uint8_t *d_arena, const int64_t *d_off, int64_t n, uint8_t *d_keep_mask, void *stream);
 
+/* ---- CDX listings parsed and the URL CSVs rendered on the device (csrc/cdx.hip) ----
+ *
+ * Raw listing bytes in, final CSV bytes out: the handle owns a row store (UTF-8 URL arena, int64 offsets, int64
+ * timestamps, in the layout kw_dedup_run takes); kw_cdx_append parses one device-resident text into it,
+ * kw_cdx_run is kw_dedup_run over the store, kw_cdx_csv_* render the kept rows as the bytes of pandas'
+ * DataFrame.to_csv(index=False) over columns date_time,url.
+ *
+ * A text is taken only where the parse provably equals pandas' ("CDX ingest"); otherwise the
+ * verdict names the first failed condition and nothing is appended. */
+typedef struct {
+    uint8_t delim;         /* the field delimiter: ' ' or ',' */
+    int32_t ts_col;        /* 0-based field of the timestamp */
+    int32_t url_col;       /* 0-based field of the URL */
+    int32_t skip_lines;    /* 0, or 1: the text starts with the line "date_time,url" */
+    int32_t exact_fields;  /* 0: at least max(ts_col, url_col) + 1 fields a line; else exactly this many */
+} kw_cdx_dialect;
+/* CDX listing:  {' ', 1, 2, 0, 0}   read_csv(delimiter=' ', header=None, usecols=[1, 2])   (:59)
+ * part CSV:     {',', 0, 1, 1, 2}   read_csv(part) under the header line "date_time,url"    (:164-167) */
+
+/* verdicts of kw_cdx_append, in the order they are tested: the three byte conditions over the whole text
+ * (bad_line: the line of the first such byte), the header, then the first offending line (within a line:
+ * UTF8, FIELDS, TS, URL).  Lines are counted from 0 by the '\n' bytes before them. */
+#define KW_CDX_OK 0
+#define KW_CDX_QUOTE 1    /* a '"' byte */
+#define KW_CDX_CR 2       /* a '\r' byte */
+#define KW_CDX_NUL 3      /* a NUL byte */
+#define KW_CDX_FIELDS 4   /* a non-blank line with too few (exact_fields: not exactly that many) fields */
+#define KW_CDX_TS 5       /* a timestamp cell that is not 1-18 ASCII digits */
+#define KW_CDX_URL 6      /* a URL cell without ':' */
+#define KW_CDX_UTF8 7     /* a line that is not valid UTF-8 */
+#define KW_CDX_HEADER 8   /* skip_lines = 1 and the text does not start with the line "date_time,url" */
+
+/* Empty the handle's row store (its buffers are kept). */
+int kw_cdx_begin(kw_dedup *h);
+
+/* Parse n_bytes of text at d_text (device memory, 16-byte aligned, readable up to the next multiple of 16 past
+ * its end) and append its rows to the store; rows of successive appends are numbered consecutively.  Blank
+ * lines are dropped; a final line needs no '\n'.  *verdict receives a KW_CDX_* code, *bad_line the offending
+ * line (-1 when OK), *n_rows the rows appended (0 unless OK).  Returns when the rows are in the store.
+ * KW_EUNSUPPORTED when the store would pass the 2^32 - 1 rows of kw_dedup_run. */
+int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const kw_cdx_dialect *d, int64_t *n_rows,
+                  int32_t *verdict, int64_t *bad_line, void *stream);
+
+/* Rows and URL bytes in the store. */
+int kw_cdx_rows(kw_dedup *h, int64_t *n_rows, int64_t *n_bytes);
+
+/* The store's rows into caller-owned device buffers (any may be NULL): d_arena (n_bytes), d_off (n_rows + 1),
+ * d_ts (n_rows). */
+int kw_cdx_store_copy(kw_dedup *h, uint8_t *d_arena, int64_t *d_off, int64_t *d_ts, void *stream);
+
+/* kw_dedup_run over the store (flags: KW_DEDUP_NORMALIZE); kw_dedup_counts / kept_size / kept_copy then
+ * describe this run. */
+int kw_cdx_run(kw_dedup *h, int32_t flags, void *stream);
+
+/* The CSV of the last kw_cdx_run's kept rows, in row order: "date_time,url\n", then per row decimal(timestamp),
+ * ',', the normalised URL (wrapped in '"' when it contains ','), '\n'.  kw_cdx_csv_size computes the line
+ * lengths (on `stream`) and gives the size; kw_cdx_csv_copy writes the bytes to d_out (16-byte aligned, n_bytes
+ * of kw_cdx_csv_size) and returns when they are written. */
+int kw_cdx_csv_size(kw_dedup *h, int64_t *n_bytes, void *stream);
+int kw_cdx_csv_copy(kw_dedup *h, uint8_t *d_out, void *stream);
+
+/* Device times (ms): [0] parse and [1] compaction into the store, both summed over the appends since
+ * kw_cdx_begin, [2] the last render (kw_cdx_csv_size + kw_cdx_csv_copy); k <= 3 values. */
+int kw_cdx_last_ms(kw_dedup *h, float *ms, int32_t k);
+
+/* The parser's tile: bytes of text a block classifies at once. */
+int kw_cdx_tile_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif
