@@ -5,6 +5,7 @@ Modules:
   matcher        arena packing, the libkwmatch GPU handle, result assembly
   match_keywords the drop-in replacement of the reference script
   dedup          CDX URL keep-first dedup on the GPU
+  resume         the scraper's resume filter (links not yet scraped) on the GPU
   dist           multi-GPU sharding + RCCL gather of hit records
   synth          seeded synthetic corpus (bench/test data)
 """

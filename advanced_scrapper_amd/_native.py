@@ -47,7 +47,9 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_dedup_create', 'kw_dedup_run', 'kw_dedup_counts', 'kw_dedup_kept_size', 'kw_dedup_kept_copy',
            'kw_dedup_last_ms', 'kw_dedup_last_error', 'kw_dedup_destroy', 'dedup_urls',
            'kw_cdx_begin', 'kw_cdx_append', 'kw_cdx_rows', 'kw_cdx_store_copy', 'kw_cdx_run', 'kw_cdx_csv_size',
-           'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes')
+           'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes',
+           'kw_csv_append', 'kw_cdx_run_exclude', 'kw_cdx_exclude_codes', 'kw_cdx_exclude_counts',
+           'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -61,6 +63,10 @@ class CdxDialect(ctypes.Structure):
 
 # KW_URL_* row codes (include/kwdedup.h)
 KW_URL_NO_HTML, KW_URL_KEPT, KW_URL_FILTERED, KW_URL_DUPLICATE = 0, 1, 2, 3
+KW_URL_SEEN = 5   # a link row of kw_cdx_run_exclude whose string is among the exclude rows
+# KW_CSV_* verdicts of kw_csv_append (include/kwdedup.h), in the order they are tested
+(KW_CSV_OK, KW_CSV_NUL, KW_CSV_UTF8, KW_CSV_HEADER, KW_CSV_QUOTE, KW_CSV_CR, KW_CSV_ROWS, KW_CSV_FIELDS,
+ KW_CSV_URL) = range(9)
 KW_DEDUP_NORMALIZE = 1
 KW_N_STATS = 21
 # KW_RESCAN_* bits of stats[20] (include/kwmatch.h)
@@ -115,6 +121,17 @@ def lib() -> ctypes.CDLL:
     L.kw_cdx_tile_bytes.argtypes = []
     for f in ('kw_cdx_begin', 'kw_cdx_append', 'kw_cdx_rows', 'kw_cdx_store_copy', 'kw_cdx_run', 'kw_cdx_csv_size',
               'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes'):
+        getattr(L, f).restype = ctypes.c_int
+    L.kw_csv_append.argtypes = [vp, vp, i64, ctypes.c_char_p, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                ctypes.POINTER(i64), vp]
+    L.kw_cdx_run_exclude.argtypes = [vp, i64, vp]
+    L.kw_cdx_exclude_codes.argtypes = [vp, vp, vp]
+    L.kw_cdx_exclude_counts.argtypes = [vp, vp]
+    L.kw_cdx_remaining_size.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.kw_cdx_remaining_copy.argtypes = [vp, vp, vp, vp, vp]
+    L.kw_cdx_exclude_last_ms.argtypes = [vp, vp, i32]
+    for f in ('kw_csv_append', 'kw_cdx_run_exclude', 'kw_cdx_exclude_codes', 'kw_cdx_exclude_counts',
+              'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_compile.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)]
     L.kw_compile.restype = ctypes.c_int

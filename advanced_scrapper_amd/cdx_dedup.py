@@ -211,6 +211,63 @@ class GpuUrlDedup:
     def cdx_tile_bytes() -> int:
         return int(_native.lib().kw_cdx_tile_bytes())
 
+    # ---- the scraper's resume filter (include/kwdedup.h kw_csv_append, kw_cdx_run_exclude; resume.py)
+    def csv_append(self, data, header: str, url_col: int) -> Tuple[int, int, int]:
+        """Parse one quoted CSV text (pandas' default dialect) on the device and append the cells of column
+        `url_col` to the store: (verdict KW_CSV_*, the first offender's byte position or -1, rows appended).
+        `header` is the file's first line.  Nothing is appended unless the verdict is KW_CSV_OK."""
+        t = self.torch
+        d_text, n = self.cdx_text_device(data)
+        rows, verdict, bad = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+        st = t.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_csv_append(self.h, _native.ptr(d_text), n, header.encode('utf-8'), int(url_col),
+                                                header.count(',') + 1, ctypes.byref(rows), ctypes.byref(verdict),
+                                                ctypes.byref(bad), ctypes.c_void_p(st.cuda_stream)))
+        return int(verdict.value), int(bad.value), int(rows.value)
+
+    def run_exclude(self, n_exclude: int) -> Tuple[int, int, int]:
+        """The set difference over the store, whose first `n_exclude` rows are the exclude rows and the rest the
+        link rows: (link rows, those whose string is among the exclude rows, those remaining)."""
+        st = self.torch.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_run_exclude(self.h, int(n_exclude), ctypes.c_void_p(st.cuda_stream)))
+        c = np.zeros(3, dtype=np.int64)
+        self._check(_native.lib().kw_cdx_exclude_counts(self.h, _native.ptr(c)))
+        return int(c[0]), int(c[1]), int(c[2])
+
+    def exclude_codes(self) -> np.ndarray:
+        """The link rows' codes (KW_URL_KEPT / KW_URL_SEEN) of the last run_exclude."""
+        t = self.torch
+        c = np.zeros(3, dtype=np.int64)
+        self._check(_native.lib().kw_cdx_exclude_counts(self.h, _native.ptr(c)))
+        code = t.empty(max(int(c[0]), 1), dtype=t.uint8, device=t.device('cuda', self.device))
+        st = t.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_exclude_codes(self.h, _native.ptr(code), ctypes.c_void_p(st.cuda_stream)))
+        st.synchronize()
+        return code[:int(c[0])].cpu().numpy()
+
+    def remaining(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The last run_exclude's remaining link rows, dense and in row order, on the host: (bytes, offsets
+        [n + 1], indices among the link rows [n])."""
+        t = self.torch
+        nk, nb = ctypes.c_int64(), ctypes.c_int64()
+        self._check(_native.lib().kw_cdx_remaining_size(self.h, ctypes.byref(nk), ctypes.byref(nb)))
+        dev = t.device('cuda', self.device)
+        b = t.empty(max(nb.value, 1), dtype=t.uint8, device=dev)
+        o = t.zeros(nk.value + 1, dtype=t.int64, device=dev)
+        r = t.empty(max(nk.value, 1), dtype=t.int64, device=dev)
+        st = t.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_remaining_copy(self.h, _native.ptr(b), _native.ptr(o), _native.ptr(r),
+                                                        ctypes.c_void_p(st.cuda_stream)))
+        st.synchronize()
+        return b[:nb.value].cpu().numpy(), o.cpu().numpy(), r[:nk.value].cpu().numpy()
+
+    def exclude_last_ms(self) -> List[float]:
+        """Device times (ms) of the last run_exclude: the keep-first run, the set-difference pass, the remaining
+        rows' compaction."""
+        v = np.zeros(3, dtype=np.float32)
+        self._check(_native.lib().kw_cdx_exclude_last_ms(self.h, _native.ptr(v), 3))
+        return [float(x) for x in v]
+
     def dedup_strings(self, urls: Sequence[str], normalize: bool = True) -> Tuple[np.ndarray, List[str]]:
         """Pack, upload, classify: (kept row indices, their normalised URLs)."""
         arena, off = pack_urls(urls)

@@ -1,5 +1,5 @@
-// libkwmatch: CDX listings parsed into the dedup's row store and the kept rows rendered as CSV, on the device
-// (include/kwdedup.h, kw_cdx_*).
+// libkwmatch: CDX listings and quoted CSV files parsed into the dedup's row store and the kept rows rendered as CSV,
+// on the device (include/kwdedup.h, kw_cdx_* and kw_csv_append).
 //
 // Reference: yahoo_links_selenium.py:59 (read_csv of a listing), :82 / :176 (to_csv), :164-167 (read_csv of the
 // part CSVs); the rule under which a text is taken at all is restated in tests/cdx_rule.py.
@@ -23,6 +23,10 @@
 //                           URL cells into the arena, with CsvGen it writes the CSV.
 //   cx_linelen_kernel       lane = kept row: decimal digits of the timestamp, the URL's length, whether it holds
 //                           a ',' (then it is quoted).
+//
+//   cv_*                    quoted CSV, one column out (kw_csv_append, the scraper's resume filter:
+//                           constant_rate_scrapper.py:312-360; the rule is restated in tests/resume_rule.py): the
+//                           same tiles and masks with quote state carried across them; described above the kernels.
 //
 // Kernels hand data to each other only across launches.  All byte work: the roofline is HBM bandwidth.
 #include <hip/hip_runtime.h>
@@ -467,6 +471,247 @@ __global__ __launch_bounds__(BLOCK) void cx_linelen_kernel(int64_t n_kept, const
     if (blockIdx.x == 0 && threadIdx.x == 0) seglen[0] = HEADER_LEN;
 }
 
+// ---- quoted CSV, one column out (kw_csv_append; the rule: DESIGN.md §7, tests/resume_rule.py)
+//
+//   cv_quotes_kernel    a tile's '"' bytes counted (their exclusive scan over the tiles carries the quote parity
+//                       into every tile, however many tiles a quoted cell spans); the first NUL; UTF-8 validated by
+//                       the lanes whose 16 bytes hold a byte >= 0x80 (from the code point boundary before them).
+//   cv_tile_kernel<M>   the tile's masks again with the carried parity: a lane's in-quote mask is the prefix xor of
+//                       its '"' mask on the parity before it (a block scan of the lanes' '"' counts).  Outside quotes
+//                       a '\n' ends a record, a ',' ends a field; a record of no bytes but its terminator is
+//                       skipped.  COUNT: record ends, delimiters and record starts per tile, the quote discipline
+//                       and the '\r' rule.  ENDS (after the scans): every record's start, its end and the delimiters
+//                       before its end, at the record's rank.  CELLS: a delimiter's rank within its record from the
+//                       count at the end of the record before it; the two that bound the column give the cell.
+//   cv_rows_kernel      lane = record: the field count from the two delimiter counts, the cell without its outer
+//                       quotes, ':' looked for and '"' / '\n' / '\r' refused 8 bytes a step.
+//   then cx_scan_*, cx_off_kernel and cx_fill_kernel<ArenaGen> as kw_cdx_append.
+enum { CV_COUNT = 0, CV_ENDS = 1, CV_CELLS = 2 };
+
+// positions of the first offenders (NONE), in the words after a parse's four totals
+struct CsvErrs {
+    unsigned long long nul, utf8, quote, cr, fields, url;
+};
+
+// The first byte in [q0, ...) a strict UTF-8 decoder stops at, looking at the code points that start in
+// [p, p + 16): from the code point boundary at or before p (a continuation byte at p belongs to a lead at most 3
+// bytes back; four continuation bytes in a row hold an error at or before p, which its own lane reports).
+__device__ unsigned long long cv_utf8_lane(const uint8_t *__restrict__ text, int64_t n, int64_t p)
+{
+    int64_t q = p;
+    if ((text[p] & 0xC0u) == 0x80u) {
+        int back = 1;
+        while (back <= 3 && p - back >= 0 && (text[p - back] & 0xC0u) == 0x80u) ++back;
+        if (back > 3 || p - back < 0) return (unsigned long long)p;
+        q = p - back;
+    }
+    const int64_t stop = p + 16 < n ? p + 16 : n;
+    while (q < stop) {
+        const uint32_t c = text[q];
+        if (c < 0x80u) { ++q; continue; }
+        int need;
+        uint32_t lo = 0x80u, hi = 0xBFu;
+        if (c >= 0xC2u && c <= 0xDFu) need = 1;
+        else if (c == 0xE0u) { need = 2; lo = 0xA0u; }
+        else if (c == 0xEDu) { need = 2; hi = 0x9Fu; }
+        else if (c >= 0xE1u && c <= 0xEFu) need = 2;
+        else if (c == 0xF0u) { need = 3; lo = 0x90u; }
+        else if (c >= 0xF1u && c <= 0xF3u) need = 3;
+        else if (c == 0xF4u) { need = 3; hi = 0x8Fu; }
+        else return (unsigned long long)q;
+        for (int k = 1; k <= need; ++k) {
+            if (q + k >= n) return (unsigned long long)q;
+            const uint32_t b = text[q + k];
+            if (b < lo || b > hi) return (unsigned long long)q;
+            lo = 0x80u; hi = 0xBFu;
+        }
+        q += need + 1;
+    }
+    return NONE;
+}
+
+__global__ __launch_bounds__(BLOCK) void cv_quotes_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t ntiles,
+                                                          unsigned long long *__restrict__ tile_q,
+                                                          CsvErrs *__restrict__ errs)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t p = tile * TILE + (int64_t)threadIdx.x * 16;
+        uint32_t q = 0;
+        unsigned long long ez = NONE, e8 = NONE;
+        if (p < n) {
+            const uint4 v = *(const uint4 *)(text + p);
+            const uint32_t valid = n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u;
+            q = mask16(v, 0x22u) & valid;
+            const uint32_t z = mask16(v, 0u) & valid;
+            const uint32_t hb = (bits4(v.x & 0x80808080u) | (bits4(v.y & 0x80808080u) << 4) |
+                                 (bits4(v.z & 0x80808080u) << 8) | (bits4(v.w & 0x80808080u) << 12)) & valid;
+            if (z) ez = (unsigned long long)p + __builtin_ctz(z);
+            if (hb) e8 = cv_utf8_lane(text, n, p);
+        }
+        if (__any((ez & e8) != NONE)) {
+            ez = wave_min(ez);
+            e8 = wave_min(e8);
+            if ((threadIdx.x & 63) == 0) {
+                if (ez != NONE) atomicMin(&errs->nul, ez);
+                if (e8 != NONE) atomicMin(&errs->utf8, e8);
+            }
+        }
+        unsigned long long total;
+        (void)block_scan((unsigned long long)__popc(q), ws, &total);
+        if (threadIdx.x == 0) tile_q[tile] = total;
+    }
+}
+
+struct CsvArgs {
+    const uint8_t *text;
+    int64_t n, ntiles;
+    unsigned long long *tile_q, *tile_e, *tile_d;   // per tile: '"' bytes, record ends, delimiters (scanned)
+    unsigned long long *n_starts;                   // COUNT: the records that are not zero-length
+    CsvErrs *errs;
+    int64_t *rec_start, *end_pos, *end_dcnt, *cell_start, *cell_end;
+    int64_t cap;                                    // entries of the per-record arrays
+    int url_col;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void cv_tile_kernel(CsvArgs A)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    const uint8_t *__restrict__ text = A.text;
+    const int64_t n = A.n;
+    for (int64_t tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
+        const int64_t p = tile * TILE + (int64_t)threadIdx.x * 16;
+        uint32_t valid = 0, q = 0, cm = 0, nl = 0, cr = 0;
+        // the bytes around the lane's 16: the text is preceded by (virtual) line ends, 0x100 stands for its end
+        uint32_t prev1 = 0x0Au, prev2 = 0x0Au, next = 0x100u;
+        if (p < n) {
+            const uint4 v = *(const uint4 *)(text + p);
+            valid = n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u;
+            q = mask16(v, 0x22u) & valid;
+            cm = mask16(v, 0x2Cu) & valid;
+            nl = mask16(v, 0x0Au) & valid;
+            cr = mask16(v, 0x0Du) & valid;
+            if (p > 0) { prev1 = text[p - 1]; prev2 = text[p - 2]; }
+            if (p + 16 < n) next = text[p + 16];
+        }
+        unsigned long long total;
+        const unsigned long long qb = block_scan((unsigned long long)__popc(q), ws, &total);
+        const uint32_t inpar = (uint32_t)((A.tile_q[tile] + qb) & 1ull);
+        uint32_t incl = q;   // bit k: the parity of the '"' bytes in bits 0..k
+        incl ^= incl << 1;
+        incl ^= incl << 2;
+        incl ^= incl << 4;
+        incl ^= incl << 8;
+        const uint32_t sb = ((incl << 1) ^ (inpar ? 0xFFFFu : 0u)) & valid;   // bit k: byte k lies inside quotes
+        const uint32_t pnl = ((nl << 1) | (prev1 == 0x0Au ? 1u : 0u)) & 0xFFFFu;   // the byte before is '\n'
+        const uint32_t pcr = ((cr << 1) | (prev1 == 0x0Du ? 1u : 0u)) & 0xFFFFu;
+        const uint32_t pn2 = ((nl << 2) | (prev1 == 0x0Au ? 2u : 0u) | (prev2 == 0x0Au ? 1u : 0u)) & 0xFFFFu;
+        // a record end that is not zero-length, a record start, a delimiter
+        const uint32_t E = nl & ~sb & ~(pnl | (pcr & pn2));
+        const uint32_t ST = valid & ~sb & pnl & ~nl & ~cr;
+        const uint32_t DL = cm & ~sb;
+        if (MODE == CV_COUNT) {
+            const uint32_t pcm = ((cm << 1) | (prev1 == 0x2Cu ? 1u : 0u)) & 0xFFFFu;
+            const uint32_t pq = ((q << 1) | (prev1 == 0x22u ? 1u : 0u)) & 0xFFFFu;
+            const uint32_t top = 0x8000u;
+            const uint32_t ncm = (cm >> 1) | (next == 0x2Cu ? top : 0u), nnl = (nl >> 1) | (next == 0x0Au ? top : 0u);
+            const uint32_t ncr = (cr >> 1) | (next == 0x0Du ? top : 0u), nq = (q >> 1) | (next == 0x22u ? top : 0u);
+            const uint32_t eot = (p < n && n - p <= 16) ? 1u << (int)(n - p - 1) : 0u;   // the text's last byte
+            const uint32_t bad_q = ((q & ~sb) & ~(pcm | pnl | pq)) | ((q & sb) & ~(ncm | nnl | ncr | nq | eot));
+            const uint32_t bad_c = cr & ~sb & ~nnl;
+            unsigned long long eq = NONE, ec = NONE;
+            if (bad_q) eq = (unsigned long long)p + __builtin_ctz(bad_q);
+            if (bad_c) ec = (unsigned long long)p + __builtin_ctz(bad_c);
+            if (__any((eq & ec) != NONE)) {
+                eq = wave_min(eq);
+                ec = wave_min(ec);
+                if ((threadIdx.x & 63) == 0) {
+                    if (eq != NONE) atomicMin(&A.errs->quote, eq);
+                    if (ec != NONE) atomicMin(&A.errs->cr, ec);
+                }
+            }
+            (void)block_scan((unsigned long long)__popc(E) | ((unsigned long long)__popc(DL) << 16) |
+                                 ((unsigned long long)__popc(ST) << 32),
+                             ws, &total);
+            if (threadIdx.x == 0) {
+                A.tile_e[tile] = total & 0xFFFFull;
+                A.tile_d[tile] = (total >> 16) & 0xFFFFull;
+                if (total >> 32) atomicAdd(A.n_starts, total >> 32);
+            }
+        } else {
+            const unsigned long long before =
+                block_scan((unsigned long long)__popc(E) | ((unsigned long long)__popc(DL) << 32), ws, &total);
+            const int64_t ce = (int64_t)(A.tile_e[tile] + (before & 0xFFFFFFFFull));   // record ends before the lane
+            const int64_t cd = (int64_t)(A.tile_d[tile] + (before >> 32));             // delimiters before it
+            uint32_t todo = MODE == CV_ENDS ? (E | ST) : DL;
+            while (todo) {
+                const int k = __builtin_ctz(todo);
+                todo &= todo - 1u;
+                const uint32_t below = (1u << k) - 1u;
+                const int64_t r = ce + __popc(E & below);   // the record the byte belongs to
+                if (r >= A.cap) continue;                   // (cannot happen in a text that passed COUNT)
+                if (MODE == CV_ENDS) {
+                    if ((E >> k) & 1u) {
+                        A.end_pos[r] = p + k;
+                        A.end_dcnt[r] = cd + __popc(DL & below);
+                    } else {
+                        A.rec_start[r] = p + k;
+                    }
+                } else if (r >= 1) {
+                    const int64_t f = cd + __popc(DL & below) - A.end_dcnt[r - 1];   // the delimiter ends field f
+                    if (f == A.url_col - 1) A.cell_start[r] = p + k + 1;
+                    if (f == A.url_col) A.cell_end[r] = p + k;
+                }
+            }
+        }
+    }
+}
+
+// Record r >= 1 (record 0 is the header): [rec_start[r], its end); the records past n_ends end with the text.
+// The cell's position and length go to cell_start[r] / cell_end[r] (their own lane's entries).
+__global__ __launch_bounds__(BLOCK) void cv_rows_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t n_rec,
+                                                        int64_t n_ends, int64_t n_delims, int n_fields, int url_col,
+                                                        const int64_t *__restrict__ rec_start,
+                                                        const int64_t *__restrict__ end_pos,
+                                                        const int64_t *__restrict__ end_dcnt, int64_t *cell_start,
+                                                        int64_t *cell_end, CsvErrs *__restrict__ errs)
+{
+    constexpr uint64_t ONES = 0x0101010101010101ull;
+    for (int64_t r = 1 + (int64_t)blockIdx.x * BLOCK + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * BLOCK) {
+        const int64_t s = rec_start[r];
+        int64_t e = n, dc = n_delims;
+        if (r < n_ends) {
+            e = end_pos[r];
+            dc = end_dcnt[r];
+            if (e > s && text[e - 1] == 0x0Du) --e;   // "\r\n"
+        }
+        if (dc - end_dcnt[r - 1] + 1 != (int64_t)n_fields) {
+            atomicMin(&errs->fields, (unsigned long long)s);
+            continue;
+        }
+        int64_t b = url_col == 0 ? s : cell_start[r];
+        int64_t c = url_col == n_fields - 1 ? e : cell_end[r];
+        if (c - b >= 2 && text[b] == 0x22u) { ++b; --c; }   // (a quoted cell ends with its closing quote)
+        bool colon = false, bad = false;
+        // (aligned 8 bytes under [b, c), c <= n: inside the text's readable 16-byte granule)
+        for (int64_t w = b & ~(int64_t)7; w < c; w += 8) {
+            const uint64_t v = *(const uint64_t *)(text + w);
+            const int b0 = w < b ? (int)(b - w) : 0;
+            const int b1 = c - w >= 8 ? 8 : (int)(c - w);
+            const uint64_t in = ~((1ull << (8 * b0)) - 1ull) & (b1 == 8 ? ~0ull : (1ull << (8 * b1)) - 1ull);
+            colon |= (eq8(v, 0x3Aull * ONES) & in) != 0;
+            bad |= ((eq8(v, 0x22ull * ONES) | eq8(v, 0x0Aull * ONES) | eq8(v, 0x0Dull * ONES)) & in) != 0;
+        }
+        if (bad || !colon) {
+            atomicMin(&errs->url, (unsigned long long)s);
+            continue;
+        }
+        cell_start[r] = b;
+        cell_end[r] = c - b;
+    }
+}
+
 }  // namespace cx
 
 using namespace cx;
@@ -721,6 +966,194 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     s->run_serial = 0;
     s->csv_ready = false;
     *n_rows = n_new;
+    return KW_OK;
+}
+
+extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const char *header_line,
+                             int32_t url_col, int32_t n_fields, int64_t *n_rows, int32_t *verdict, int64_t *bad_pos,
+                             void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (!header_line || !n_rows || !verdict || !bad_pos || n_bytes < 0 || (n_bytes > 0 && !d_text)) {
+        h->err = "kw_csv_append: bad arguments";
+        return KW_EINVAL;
+    }
+    if (((uintptr_t)d_text & 15) != 0) { h->err = "kw_csv_append: the text must be 16-byte aligned"; return KW_EINVAL; }
+    const size_t hl = strlen(header_line);
+    int commas = 0;
+    bool plain = hl >= 1 && hl <= 255;
+    for (size_t k = 0; k < hl && plain; ++k) {
+        const char c = header_line[k];
+        commas += c == ',';
+        plain = c != '"' && c != '\n' && c != '\r';
+    }
+    if (!plain || n_fields != commas + 1 || url_col < 0 || url_col >= n_fields) {
+        h->err = "kw_csv_append: unsupported header line or column";
+        return KW_EINVAL;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    *n_rows = 0;
+    *verdict = KW_CSV_OK;
+    *bad_pos = -1;
+    auto refuse = [&](int32_t v, int64_t pos) { *verdict = v; *bad_pos = pos; return KW_OK; };
+    if (n_bytes == 0) return refuse(KW_CSV_HEADER, 0);
+    // ---- '"' bytes per tile, the byte conditions
+    const int64_t ntiles = (n_bytes + TILE - 1) / TILE;
+    const size_t tw = up256(8 * (size_t)ntiles);
+    rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, 3 * tw + up256(8 * SCAN_CHUNKS) + 256);
+    if (rc) return rc;
+    unsigned long long *tile_q = (unsigned long long *)s->d_tiles;
+    unsigned long long *tile_e = (unsigned long long *)((uint8_t *)s->d_tiles + tw);
+    unsigned long long *tile_d = (unsigned long long *)((uint8_t *)s->d_tiles + 2 * tw);
+    unsigned long long *chunk = (unsigned long long *)((uint8_t *)s->d_tiles + 3 * tw);
+    // small: the totals [0] '"' bytes, [1] record ends, [2] delimiters, [3] record starts, then CsvErrs; [12] a
+    // scan's total
+    unsigned long long *small = chunk + up256(8 * SCAN_CHUNKS) / 8;
+    CsvErrs *errs = (CsvErrs *)(small + 4);
+    DDCHK(h, hipMemsetAsync(small, 0, 32, st));
+    DDCHK(h, hipMemsetAsync(small + 4, 0xFF, sizeof(CsvErrs), st));
+    DDCHK(h, hipEventRecord(s->ev[0], st));
+    const int tgrid = (int)std::min<int64_t>(ntiles, (int64_t)h->cus * 16);
+    hipLaunchKernelGGL(cv_quotes_kernel, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_q, errs);
+    scan_launch(tile_q, ntiles, chunk, small, st);
+    DDCHK(h, hipGetLastError());
+    unsigned long long hs[10];
+    uint8_t head[260] = {0};
+    const size_t hn = (size_t)std::min<int64_t>(n_bytes, (int64_t)hl + 2);
+    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipMemcpyAsync(head, d_text, hn, hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    if (hs[4] != NONE) return refuse(KW_CSV_NUL, (int64_t)hs[4]);
+    if (hs[5] != NONE) return refuse(KW_CSV_UTF8, (int64_t)hs[5]);
+    if (!(hn > hl && memcmp(head, header_line, hl) == 0 &&
+          (head[hl] == '\n' || (head[hl] == '\r' && hn > hl + 1 && head[hl + 1] == '\n'))))
+        return refuse(KW_CSV_HEADER, 0);
+    const bool ends_quoted = (hs[0] & 1ull) != 0;
+    // ---- record ends, delimiters and record starts per tile; the quote discipline, the '\r' rule
+    CsvArgs A{};
+    A.text = d_text;
+    A.n = n_bytes;
+    A.ntiles = ntiles;
+    A.tile_q = tile_q;
+    A.tile_e = tile_e;
+    A.tile_d = tile_d;
+    A.n_starts = small + 3;
+    A.errs = errs;
+    A.url_col = url_col;
+    hipLaunchKernelGGL(cv_tile_kernel<CV_COUNT>, dim3(tgrid), dim3(BLOCK), 0, st, A);
+    scan_launch(tile_e, ntiles, chunk, small + 1, st);
+    scan_launch(tile_d, ntiles, chunk, small + 2, st);
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    if (hs[6] != NONE || ends_quoted) return refuse(KW_CSV_QUOTE, hs[6] != NONE ? (int64_t)hs[6] : n_bytes);
+    if (hs[7] != NONE) return refuse(KW_CSV_CR, (int64_t)hs[7]);
+    const int64_t n_ends = (int64_t)hs[1], n_delims = (int64_t)hs[2], n_rec = (int64_t)hs[3];
+    if (n_rec < 1 || n_ends > n_rec || n_ends < n_rec - 1) {   // (the header is a record; the last may end with the text)
+        h->err = "kw_csv_append: record starts and ends do not pair up";
+        return KW_ESTATE;
+    }
+    const int64_t n_new = n_rec - 1;
+    if (n_new == 0 || s->n + n_new >= ((int64_t)1 << 32)) return refuse(KW_CSV_ROWS, n_bytes);
+    // ---- the records located, their cells checked
+    const size_t rw = up256(8 * ((size_t)n_rec + 1));
+    rc = scratch_fit(h, &s->d_rows, &s->rows_bytes, 5 * rw);
+    if (rc) return rc;
+    A.rec_start = (int64_t *)s->d_rows;
+    A.end_pos = (int64_t *)((uint8_t *)s->d_rows + rw);
+    A.end_dcnt = (int64_t *)((uint8_t *)s->d_rows + 2 * rw);
+    A.cell_start = (int64_t *)((uint8_t *)s->d_rows + 3 * rw);
+    A.cell_end = (int64_t *)((uint8_t *)s->d_rows + 4 * rw);
+    A.cap = n_rec + 1;
+    DDCHK(h, hipMemsetAsync(s->d_rows, 0, 5 * rw, st));   // (an entry nobody wrote is an empty cell at 0, not a wild one)
+    hipLaunchKernelGGL(cv_tile_kernel<CV_ENDS>, dim3(tgrid), dim3(BLOCK), 0, st, A);
+    hipLaunchKernelGGL(cv_tile_kernel<CV_CELLS>, dim3(tgrid), dim3(BLOCK), 0, st, A);
+    hipLaunchKernelGGL(cv_rows_kernel, dim3(grid_for(h, n_new)), dim3(BLOCK), 0, st, d_text, n_bytes, n_rec, n_ends,
+                       n_delims, (int)n_fields, (int)url_col, (const int64_t *)A.rec_start, (const int64_t *)A.end_pos,
+                       (const int64_t *)A.end_dcnt, A.cell_start, A.cell_end, errs);
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipEventRecord(s->ev[1], st));
+    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    if (hs[8] != NONE) return refuse(KW_CSV_FIELDS, (int64_t)hs[8]);
+    if (hs[9] != NONE) return refuse(KW_CSV_URL, (int64_t)hs[9]);
+    // ---- compaction (as kw_cdx_append): the cell lengths scanned, the offsets, the cells copied into the arena
+    {
+        size_t cap = s->rows_cap * 8, cap2 = s->rows_cap * 8;
+        const size_t need = 8 * ((size_t)(s->n + n_new) + 1);
+        rc = grow_keep(h, (void **)&s->off, &cap, need, 8 * ((size_t)s->n + 1), st);
+        if (!rc) rc = grow_keep(h, (void **)&s->ts, &cap2, cap, 8 * (size_t)s->n, st);
+        if (rc) return rc;
+        s->rows_cap = cap / 8;
+    }
+    const int64_t *url_pos = A.cell_start + 1;
+    unsigned long long *url_len = (unsigned long long *)(A.cell_end + 1);
+    unsigned long long *grand = small + 12;
+    DDCHK(h, hipMemsetAsync(s->ts + s->n, 0, 8 * (size_t)n_new, st));
+    scan_launch(url_len, n_new, chunk, grand, st);
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipMemcpyAsync(hs, grand, 8, hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    const int64_t total = (int64_t)hs[0];
+    rc = grow_keep(h, (void **)&s->arena, &s->arena_cap, (size_t)(s->n_bytes + total) + 64, (size_t)s->n_bytes, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cx_off_kernel, dim3(grid_for(h, n_new + 1)), dim3(BLOCK), 0, st, s->off + s->n,
+                       (const unsigned long long *)url_len, (const unsigned long long *)grand, n_new, s->n_bytes);
+    hipLaunchKernelGGL(cx_fill_kernel<ArenaGen>, dim3(grid_for(h, (total + 31) / 16)), dim3(BLOCK), 0, st, s->arena,
+                       (const int64_t *)(s->off + s->n), n_new, ArenaGen{d_text, url_pos});
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipEventRecord(s->ev[2], st));
+    DDCHK(h, hipStreamSynchronize(st));
+    float a = 0.f, b = 0.f;
+    DDCHK(h, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+    DDCHK(h, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+    s->ms[0] += a;
+    s->ms[1] += b;
+    s->n += n_new;
+    s->n_bytes += total;
+    s->run_serial = 0;
+    s->csv_ready = false;
+    *n_rows = n_new;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_run_exclude(kw_dedup *h, int64_t n_exclude, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    DDCHK(h, hipSetDevice(h->device));
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    if (n_exclude < 0 || n_exclude > s->n) { h->err = "kw_cdx_run_exclude: n_exclude outside the store"; return KW_EINVAL; }
+    rc = scratch_fit(h, (void **)&s->code, &s->code_cap, (size_t)s->n + 64);
+    if (rc) return rc;
+    s->csv_ready = false;
+    s->run_serial = 0;   // (the kept-rows buffers will hold the remaining rows: nothing for kw_cdx_csv_* to render)
+    h->no_compact = true;   // (the run's own kept rows would be thrown away: the pass compacts the link rows)
+    rc = kw_dedup_run(h, s->arena, s->off, s->n, 0, s->code, stream);
+    h->no_compact = false;
+    if (rc) return rc;
+    return kw_dedup_exclude_pass(h, s->arena, n_exclude, s->code, (hipStream_t)stream);
+}
+
+extern "C" int kw_cdx_exclude_codes(kw_dedup *h, uint8_t *d_code, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = h->cdx;
+    if (!s || h->ex_serial == 0 || h->ex_serial != h->run_serial) {
+        h->err = "kw_cdx_exclude_codes: the last run was not kw_cdx_run_exclude";
+        return KW_ESTATE;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    if (h->ex_links > 0) {
+        if (!d_code) { h->err = "kw_cdx_exclude_codes: bad arguments"; return KW_EINVAL; }
+        DDCHK(h, hipMemcpyAsync(d_code, s->code + (s->n - h->ex_links), (size_t)h->ex_links, hipMemcpyDeviceToDevice,
+                                (hipStream_t)stream));
+    }
     return KW_OK;
 }
 

@@ -38,6 +38,11 @@
 //                        raw span staged by LDS-DMA, words regenerated from
 //                        LDS into an output stage, aligned 16-byte stores).
 //
+//   dd_exclude_kernel    the set difference of kw_cdx_run_exclude: after a raw
+//                        run over exclude rows followed by link rows, a duplicate
+//                        link row is dropped iff its tag's first row in the table
+//                        holds its bytes and is an exclude row.
+//
 // All byte/integer work: the roofline is HBM bandwidth; the table's random
 // atomics bound the insert.
 #include <hip/hip_runtime.h>
@@ -47,7 +52,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <unordered_set>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/kwmatch.h"
@@ -1552,6 +1557,48 @@ __global__ __launch_bounds__(BLOCK) void dd_materialize_kernel(const uint8_t *__
     }
 }
 
+// ---- set difference (kw_cdx_run_exclude): after a raw keep-first run over m exclude rows followed by the link
+// rows, a link row is dropped iff the first row holding its bytes is an exclude row.  A link row coded KEPT is
+// its bytes' first row and stays.  A link row coded DUPLICATE (lane = row) hashes its bytes again and reads its
+// tag's final holder from the table, the tag's first row (what dd_recheck_kernel compares with): equal bytes ->
+// that row is the first holder, KW_URL_SEEN when it is an exclude row, else KW_URL_KEPT (isin does not
+// deduplicate).  Differing bytes: the tag is shared with another URL, whose earlier row holds the slot; the row is
+// listed (CODE_COLLIDE) and the host looks its bytes up among the URLs of the run's exact pass (the first row of
+// every URL that is not the holder's is always one of that pass's rows; the listed row itself need not be: it may
+// have been paired with a holder of its own URL that the other URL's earlier row displaced afterwards).
+// Without exclude rows (m == 0) nothing can be seen and nothing is hashed.  cnt[11]: rows listed, cnt[12]: rows seen.
+__global__ __launch_bounds__(BLOCK) void dd_exclude_kernel(const uint8_t *__restrict__ arena, uint8_t *__restrict__ code,
+                                                           Scratch S, int64_t m, int64_t n)
+{
+    uint32_t n_seen = 0;
+    for (int64_t i = m + (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        if (code[i] != KW_URL_DUPLICATE) continue;
+        if (m == 0) { code[i] = (uint8_t)KW_URL_KEPT; continue; }
+        const RowGen gi = row_gen(S, arena, i);
+        const uint64_t h = row_hash(S, gi);
+        uint64_t slot = (h ^ (h >> 29)) & S.mask;
+        unsigned long long cur;
+        const uint32_t want = (uint32_t)((h >> 40) << 8) | S.epoch;
+        for (;;) {   // (the row's own insert found or left its tag on this probe path)
+            cur = S.table[slot];
+            if ((uint32_t)(cur >> 32) == want) break;
+            slot = (slot + 1) & S.mask;
+        }
+        const uint32_t r0 = (uint32_t)cur - 1u;
+        if (r0 != (uint32_t)i && same_url(gi, row_gen(S, arena, r0))) {
+            const bool seen = (int64_t)r0 < m;
+            code[i] = seen ? (uint8_t)KW_URL_SEEN : (uint8_t)KW_URL_KEPT;
+            n_seen += seen;
+        } else {
+            code[i] = CODE_COLLIDE;
+            const unsigned long long k = atomicAdd(&S.cnt[11], 1ull);   // (rare)
+            if (k < COLLIDE_CAP) S.collide[k] = (uint32_t)i;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) n_seen += __shfl_xor(n_seen, d, 64);
+    if ((threadIdx.x & 63) == 0 && n_seen) atomicAdd(&S.cnt[12], (unsigned long long)n_seen);
+}
+
 }  // namespace dd
 
 using namespace dd;
@@ -1579,6 +1626,50 @@ extern "C" int kw_dedup_create(int32_t device, kw_dedup **out)
 }
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The normalised bytes of the listed rows on the host, regenerated on the device: row rows[q] is
+// buf[boff[q], boff[q] + len[q]) (8-aligned slots).
+static int fetch_rows(kw_dedup *h, const uint8_t *d_arena, const int64_t *d_off, const std::vector<uint32_t> &rows,
+                      hipStream_t st, std::vector<uint32_t> &len, std::vector<uint64_t> &boff, std::vector<uint8_t> &buf)
+{
+    const uint32_t k = (uint32_t)rows.size();
+    uint32_t *d_rows = nullptr, *d_len = nullptr;
+    uint64_t *d_boff = nullptr;
+    uint8_t *d_buf = nullptr;
+    len.assign(k, 0);
+    boff.assign((size_t)k + 1, 0);
+    int rc = KW_OK;
+    auto fail = [&](hipError_t e, const char *what) {
+        h->err = std::string("HIP error ") + hipGetErrorString(e) + " at " + what;
+        rc = KW_EHIP;
+    };
+    hipError_t e;
+    if ((e = hipMalloc(&d_rows, 4 * (size_t)k)) != hipSuccess) fail(e, "collide rows");
+    if (!rc && (e = hipMalloc(&d_len, 4 * (size_t)k)) != hipSuccess) fail(e, "collide lengths");
+    if (!rc && (e = hipMemcpy(d_rows, rows.data(), 4 * (size_t)k, hipMemcpyHostToDevice)) != hipSuccess) fail(e, "rows");
+    const int g2 = (int)std::min<uint32_t>((k + BLOCK - 1) / BLOCK, 1024u);
+    if (!rc) {
+        hipLaunchKernelGGL(dd_gather_len_kernel, dim3(g2), dim3(BLOCK), 0, st, (const uint32_t *)d_rows, k, h->S, d_len);
+        if ((e = hipMemcpyAsync(len.data(), d_len, 4 * (size_t)k, hipMemcpyDeviceToHost, st)) != hipSuccess) fail(e, "lengths");
+        if (!rc && (e = hipStreamSynchronize(st)) != hipSuccess) fail(e, "sync");
+    }
+    for (uint32_t q = 0; q < k; ++q) boff[q + 1] = boff[q] + ((len[q] + 7) & ~7u);
+    if (!rc && (e = hipMalloc(&d_boff, 8 * ((size_t)k + 1))) != hipSuccess) fail(e, "offsets");
+    if (!rc && (e = hipMalloc(&d_buf, boff[k] + 8)) != hipSuccess) fail(e, "bytes");
+    buf.assign(boff[k] + 8, 0);
+    if (!rc && (e = hipMemcpy(d_boff, boff.data(), 8 * ((size_t)k + 1), hipMemcpyHostToDevice)) != hipSuccess) fail(e, "boff");
+    if (!rc) {
+        hipLaunchKernelGGL(dd_materialize_kernel, dim3(g2), dim3(BLOCK), 0, st, d_arena, d_off, h->S,
+                           (const uint32_t *)d_rows, k, (const uint64_t *)d_boff, d_buf);
+        if ((e = hipMemcpyAsync(buf.data(), d_buf, boff[k], hipMemcpyDeviceToHost, st)) != hipSuccess) fail(e, "bytes back");
+        if (!rc && (e = hipStreamSynchronize(st)) != hipSuccess) fail(e, "sync");
+    }
+    if (d_rows) (void)hipFree(d_rows);
+    if (d_len) (void)hipFree(d_len);
+    if (d_boff) (void)hipFree(d_boff);
+    if (d_buf) (void)hipFree(d_buf);
+    return rc;
+}
 
 // exact keep-first over the rows that share a hash tag with a different URL (in row order): their normalised
 // bytes regenerated on the device, compared on the host
@@ -1610,53 +1701,74 @@ static int resolve_collisions(kw_dedup *h, const uint8_t *d_arena, const int64_t
     }
     const uint32_t k = (uint32_t)rows.size();
     if (k == 0) return KW_OK;
-    uint32_t *d_rows = nullptr, *d_len = nullptr;
-    uint64_t *d_boff = nullptr;
-    uint8_t *d_buf = nullptr;
-    std::vector<uint32_t> len(k);
-    std::vector<uint64_t> boff(k + 1, 0);
-    int rc = KW_OK;
-    auto fail = [&](hipError_t e, const char *what) {
-        h->err = std::string("HIP error ") + hipGetErrorString(e) + " at " + what;
-        rc = KW_EHIP;
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&d_rows, 4 * (size_t)k)) != hipSuccess) fail(e, "collide rows");
-    if (!rc && (e = hipMalloc(&d_len, 4 * (size_t)k)) != hipSuccess) fail(e, "collide lengths");
-    if (!rc && (e = hipMemcpy(d_rows, rows.data(), 4 * (size_t)k, hipMemcpyHostToDevice)) != hipSuccess) fail(e, "rows");
-    const int g2 = (int)std::min<uint32_t>((k + BLOCK - 1) / BLOCK, 1024u);
-    if (!rc) {
-        hipLaunchKernelGGL(dd_gather_len_kernel, dim3(g2), dim3(BLOCK), 0, st, (const uint32_t *)d_rows, k, h->S, d_len);
-        if ((e = hipMemcpyAsync(len.data(), d_len, 4 * (size_t)k, hipMemcpyDeviceToHost, st)) != hipSuccess) fail(e, "lengths");
-        if (!rc && (e = hipStreamSynchronize(st)) != hipSuccess) fail(e, "sync");
-    }
-    for (uint32_t q = 0; q < k; ++q) boff[q + 1] = boff[q] + ((len[q] + 7) & ~7u);
-    if (!rc && (e = hipMalloc(&d_boff, 8 * ((size_t)k + 1))) != hipSuccess) fail(e, "offsets");
-    if (!rc && (e = hipMalloc(&d_buf, boff[k] + 8)) != hipSuccess) fail(e, "bytes");
-    std::vector<uint8_t> buf(boff[k] + 8);
-    if (!rc && (e = hipMemcpy(d_boff, boff.data(), 8 * ((size_t)k + 1), hipMemcpyHostToDevice)) != hipSuccess) fail(e, "boff");
-    if (!rc) {
-        hipLaunchKernelGGL(dd_materialize_kernel, dim3(g2), dim3(BLOCK), 0, st, d_arena, d_off, h->S,
-                           (const uint32_t *)d_rows, k, (const uint64_t *)d_boff, d_buf);
-        if ((e = hipMemcpyAsync(buf.data(), d_buf, boff[k], hipMemcpyDeviceToHost, st)) != hipSuccess) fail(e, "bytes back");
-        if (!rc && (e = hipStreamSynchronize(st)) != hipSuccess) fail(e, "sync");
-    }
+    std::vector<uint32_t> len;
+    std::vector<uint64_t> boff;
+    std::vector<uint8_t> buf;
+    int rc = fetch_rows(h, d_arena, d_off, rows, st, len, boff, buf);
+    if (rc) return rc;
+    // (the first row of every URL among them is remembered: kw_cdx_run_exclude asks for it)
+    std::unordered_map<std::string, uint32_t> &seen = h->collide_first;
     std::vector<uint8_t> codes(k);
-    if (!rc) {
-        std::unordered_set<std::string> seen;
-        for (uint32_t q = 0; q < k; ++q) {
-            const std::string s((const char *)buf.data() + boff[q], len[q]);
-            codes[q] = seen.insert(s).second ? (uint8_t)KW_URL_KEPT : (uint8_t)KW_URL_DUPLICATE;
-            ++h->counts[codes[q]];
-        }
-        for (uint32_t q = 0; q < k && !rc; ++q)
-            if ((e = hipMemcpy(d_code + rows[q], &codes[q], 1, hipMemcpyHostToDevice)) != hipSuccess) fail(e, "code");
+    for (uint32_t q = 0; q < k; ++q) {
+        const auto ins = seen.emplace(std::string((const char *)buf.data() + boff[q], len[q]), rows[q]);
+        codes[q] = ins.second ? (uint8_t)KW_URL_KEPT : (uint8_t)KW_URL_DUPLICATE;
+        ++h->counts[codes[q]];
     }
-    if (d_rows) (void)hipFree(d_rows);
-    if (d_len) (void)hipFree(d_len);
-    if (d_boff) (void)hipFree(d_boff);
-    if (d_buf) (void)hipFree(d_buf);
-    return rc;
+    for (uint32_t q = 0; q < k; ++q) DDCHK(h, hipMemcpy(d_code + rows[q], &codes[q], 1, hipMemcpyHostToDevice));
+    return KW_OK;
+}
+
+// The rows of code[0, n) coded KW_URL_KEPT, dense and in row order: offsets, source rows and bytes into the
+// handle's kept buffers (sized by the last run's rows); h->n_kept and h->n_kept_bytes describe them.  S: the
+// run's scratch, its per-row arrays starting at the row code[0] belongs to.
+static int compact_kept(kw_dedup *h, const uint8_t *d_arena, const uint8_t *d_code, int64_t n, const Scratch &S,
+                        hipStream_t st)
+{
+    const int64_t ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    hipLaunchKernelGGL(dd_count_kernel, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, (const uint8_t *)d_code, n, S,
+                       h->tile_cnt, h->tile_bytes);
+    {   // the tiles' exclusive scan in two levels: chunk sums, their scan (one block), each chunk from its prefix
+        const int64_t nchunk = std::min<int64_t>(SCAN_CHUNKS, ntiles);
+        const int64_t per = (ntiles + nchunk - 1) / nchunk;
+        hipLaunchKernelGGL(dd_tile_sums_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st,
+                           (const unsigned long long *)h->tile_cnt, (const unsigned long long *)h->tile_bytes, ntiles,
+                           per, h->chunk_cnt, h->chunk_bytes);
+        hipLaunchKernelGGL(dd_scan_tiles_kernel, dim3(1), dim3(1024), 0, st, h->chunk_cnt, h->chunk_bytes, nchunk,
+                           h->totals, nchunk, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr);
+        hipLaunchKernelGGL(dd_scan_tiles_kernel, dim3((unsigned)nchunk), dim3(1024), 0, st, h->tile_cnt, h->tile_bytes,
+                           ntiles, (unsigned long long *)nullptr, per, (const unsigned long long *)h->chunk_cnt,
+                           (const unsigned long long *)h->chunk_bytes);
+    }
+    hipLaunchKernelGGL(dd_place_kernel, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, (const uint8_t *)d_code, n, S,
+                       h->tile_cnt, h->tile_bytes, h->kept_off, h->kept_row);
+    DDCHK(h, hipGetLastError());
+    unsigned long long tot[2];
+    DDCHK(h, hipMemcpyAsync(tot, h->totals, sizeof(tot), hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipStreamSynchronize(st));
+    h->n_kept = (int64_t)tot[0];
+    h->n_kept_bytes = (int64_t)tot[1];
+    DDCHK(h, hipMemcpyAsync(h->kept_off + h->n_kept, &h->n_kept_bytes, 8, hipMemcpyHostToDevice, st));
+    if ((size_t)h->n_kept_bytes + 64 > h->kept_bytes_cap) {
+        if (h->d_kept) (void)hipFree(h->d_kept);
+        h->d_kept = nullptr;
+        h->kept_bytes_cap = 0;
+        DDCHK(h, hipMalloc(&h->d_kept, (size_t)h->n_kept_bytes + 64));
+        h->kept_bytes_cap = (size_t)h->n_kept_bytes + 64;
+    }
+    h->kept_bytes = (uint8_t *)h->d_kept;
+    if (h->n_kept > 0) {
+        const int cgrid = (int)std::min<int64_t>((h->n_kept + 63) / 64 * 64 / BLOCK + 1, (int64_t)h->cus * 8);
+        if (kw_env("KW_DEDUP_COPY_LANE_ROW"))   // (A/B: the lane-per-row copy from global memory)
+            hipLaunchKernelGGL(dd_copy_kernel, dim3(cgrid), dim3(BLOCK), 0, st, h->n_kept, (const int64_t *)h->kept_off,
+                               (const int64_t *)h->kept_row, d_arena, S, h->kept_bytes);
+        else
+            hipLaunchKernelGGL(dd_copy_staged_kernel, dim3((int)std::min<int64_t>((h->n_kept + CPS_ROWS - 1) / CPS_ROWS,
+                                                                                (int64_t)h->cus * h->copys_bpc)),
+                               dim3(64), 0, st, h->n_kept, (const int64_t *)h->kept_off, (const int64_t *)h->kept_row,
+                               d_arena, S, h->kept_bytes);
+        DDCHK(h, hipGetLastError());
+    }
+    return KW_OK;
 }
 
 extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *d_off, int64_t n, int32_t flags,
@@ -1673,6 +1785,8 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
     ++h->run_serial;
     for (int k = 0; k < 4; ++k) h->counts[k] = 0;
     h->n_kept = h->n_kept_bytes = 0;
+    h->collide_first.clear();
+    h->ex_serial = 0;
     if (n == 0) return KW_OK;
     // ---- scratch (grown on demand)
     uint64_t tsize = 1024;
@@ -1776,48 +1890,9 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
         if (rc) return rc;
     }
     DDCHK(h, hipEventRecord(h->ev[3], st));
-    hipLaunchKernelGGL(dd_count_kernel, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, (const uint8_t *)d_code, n, S,
-                       h->tile_cnt, h->tile_bytes);
-    {   // the tiles' exclusive scan in two levels: chunk sums, their scan (one block), each chunk from its prefix
-        const int64_t nchunk = std::min<int64_t>(SCAN_CHUNKS, ntiles);
-        const int64_t per = (ntiles + nchunk - 1) / nchunk;
-        hipLaunchKernelGGL(dd_tile_sums_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st,
-                           (const unsigned long long *)h->tile_cnt, (const unsigned long long *)h->tile_bytes, ntiles,
-                           per, h->chunk_cnt, h->chunk_bytes);
-        hipLaunchKernelGGL(dd_scan_tiles_kernel, dim3(1), dim3(1024), 0, st, h->chunk_cnt, h->chunk_bytes, nchunk,
-                           h->totals, nchunk, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr);
-        hipLaunchKernelGGL(dd_scan_tiles_kernel, dim3((unsigned)nchunk), dim3(1024), 0, st, h->tile_cnt, h->tile_bytes,
-                           ntiles, (unsigned long long *)nullptr, per, (const unsigned long long *)h->chunk_cnt,
-                           (const unsigned long long *)h->chunk_bytes);
-    }
-    hipLaunchKernelGGL(dd_place_kernel, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, (const uint8_t *)d_code, n, S,
-                       h->tile_cnt, h->tile_bytes, h->kept_off, h->kept_row);
-    DDCHK(h, hipGetLastError());
-    unsigned long long tot[2];
-    DDCHK(h, hipMemcpyAsync(tot, h->totals, sizeof(tot), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
-    h->n_kept = (int64_t)tot[0];
-    h->n_kept_bytes = (int64_t)tot[1];
-    DDCHK(h, hipMemcpyAsync(h->kept_off + h->n_kept, &h->n_kept_bytes, 8, hipMemcpyHostToDevice, st));
-    if ((size_t)h->n_kept_bytes + 64 > h->kept_bytes_cap) {
-        if (h->d_kept) (void)hipFree(h->d_kept);
-        h->d_kept = nullptr;
-        h->kept_bytes_cap = 0;
-        DDCHK(h, hipMalloc(&h->d_kept, (size_t)h->n_kept_bytes + 64));
-        h->kept_bytes_cap = (size_t)h->n_kept_bytes + 64;
-    }
-    h->kept_bytes = (uint8_t *)h->d_kept;
-    if (h->n_kept > 0) {
-        const int cgrid = (int)std::min<int64_t>((h->n_kept + 63) / 64 * 64 / BLOCK + 1, (int64_t)h->cus * 8);
-        if (kw_env("KW_DEDUP_COPY_LANE_ROW"))   // (A/B: the lane-per-row copy from global memory)
-            hipLaunchKernelGGL(dd_copy_kernel, dim3(cgrid), dim3(BLOCK), 0, st, h->n_kept, (const int64_t *)h->kept_off,
-                               (const int64_t *)h->kept_row, d_arena, S, h->kept_bytes);
-        else
-            hipLaunchKernelGGL(dd_copy_staged_kernel, dim3((int)std::min<int64_t>((h->n_kept + CPS_ROWS - 1) / CPS_ROWS,
-                                                                                (int64_t)h->cus * h->copys_bpc)),
-                               dim3(64), 0, st, h->n_kept, (const int64_t *)h->kept_off, (const int64_t *)h->kept_row,
-                               d_arena, S, h->kept_bytes);
-        DDCHK(h, hipGetLastError());
+    if (!h->no_compact) {   // (kw_cdx_run_exclude compacts the link rows after its pass instead)
+        int rc = compact_kept(h, d_arena, d_code, n, S, st);
+        if (rc) return rc;
     }
     DDCHK(h, hipEventRecord(h->ev[4], st));
     DDCHK(h, hipStreamSynchronize(st));
@@ -1858,6 +1933,116 @@ extern "C" int kw_dedup_kept_copy(kw_dedup *h, uint8_t *d_bytes, int64_t *d_off,
     return KW_OK;
 }
 
+int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, hipStream_t st)
+{
+    const int64_t n = h->n;
+    Scratch &S = h->S;
+    h->ex_links = n - m;
+    h->ex_seen = 0;
+    h->n_kept = h->n_kept_bytes = 0;
+    for (auto &e : h->ex_ev)
+        if (!e) DDCHK(h, hipEventCreate(&e));
+    DDCHK(h, hipEventRecord(h->ex_ev[0], st));
+    if (n > m) {
+        // (without exclude rows every link row stays, the duplicates among them too: no holder is below m)
+        const int grid = (int)std::min<int64_t>((n - m + BLOCK - 1) / BLOCK, (int64_t)h->cus * 8);
+        hipLaunchKernelGGL(dd_exclude_kernel, dim3(grid), dim3(BLOCK), 0, st, d_arena, d_code, S, m, n);
+        DDCHK(h, hipGetLastError());
+        unsigned long long cnt[2];
+        DDCHK(h, hipMemcpyAsync(cnt, S.cnt + 11, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        DDCHK(h, hipStreamSynchronize(st));
+        h->ex_seen = (int64_t)cnt[1];
+        if (cnt[0]) {
+            // the listed rows: their first holders from the host's exact pass of the run
+            std::vector<uint32_t> rows;
+            if (cnt[0] <= COLLIDE_CAP) {
+                rows.resize(cnt[0]);
+                DDCHK(h, hipMemcpy(rows.data(), S.collide, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost));
+            } else {
+                std::vector<uint8_t> code((size_t)(n - m));
+                DDCHK(h, hipMemcpy(code.data(), d_code + m, (size_t)(n - m), hipMemcpyDeviceToHost));
+                for (int64_t i = 0; i < n - m; ++i)
+                    if (code[i] == CODE_COLLIDE) rows.push_back((uint32_t)(m + i));
+            }
+            // (by their bytes, not by row: a listed row need not be one the exact pass saw, when the holder it was
+            // paired with, of its own URL, was displaced by the other URL's earlier row after the pairing; the first
+            // row of its URL always is)
+            std::sort(rows.begin(), rows.end());
+            std::vector<uint32_t> len;
+            std::vector<uint64_t> boff;
+            std::vector<uint8_t> buf;
+            int rc = fetch_rows(h, d_arena, nullptr, rows, st, len, boff, buf);
+            if (rc) return rc;
+            for (size_t q = 0; q < rows.size(); ++q) {
+                const auto it = h->collide_first.find(std::string((const char *)buf.data() + boff[q], len[q]));
+                if (it == h->collide_first.end()) {
+                    h->err = "kw_cdx_run_exclude: a row without a first holder";
+                    return KW_ESTATE;
+                }
+                const bool seen = (int64_t)it->second < m;
+                const uint8_t c = seen ? (uint8_t)KW_URL_SEEN : (uint8_t)KW_URL_KEPT;
+                h->ex_seen += seen;
+                DDCHK(h, hipMemcpy(d_code + rows[q], &c, 1, hipMemcpyHostToDevice));
+            }
+        }
+    }
+    DDCHK(h, hipEventRecord(h->ex_ev[1], st));
+    if (n > m) {
+        // the remaining rows, dense: the run's compaction over the link rows (row indices from the first link row)
+        Scratch L = S;
+        L.rowd += m;
+        L.len3 += m;
+        int rc = compact_kept(h, d_arena, d_code + m, n - m, L, st);
+        if (rc) return rc;
+    }
+    DDCHK(h, hipEventRecord(h->ex_ev[2], st));
+    DDCHK(h, hipStreamSynchronize(st));
+    h->ex_serial = h->run_serial;
+    return KW_OK;
+}
+
+static int exclude_state(kw_dedup *h, const char *who)
+{
+    if (h->ex_serial != 0 && h->ex_serial == h->run_serial) return KW_OK;
+    h->err = std::string(who) + ": the last run was not kw_cdx_run_exclude";
+    return KW_ESTATE;
+}
+
+extern "C" int kw_cdx_exclude_counts(kw_dedup *h, int64_t *counts)
+{
+    if (!h || !counts) return KW_EINVAL;
+    if (int rc = exclude_state(h, "kw_cdx_exclude_counts")) return rc;
+    counts[0] = h->ex_links;
+    counts[1] = h->ex_seen;
+    counts[2] = h->ex_links - h->ex_seen;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_remaining_size(kw_dedup *h, int64_t *n_rows, int64_t *n_bytes)
+{
+    if (!h || !n_rows || !n_bytes) return KW_EINVAL;
+    if (int rc = exclude_state(h, "kw_cdx_remaining_size")) return rc;
+    return kw_dedup_kept_size(h, n_rows, n_bytes);
+}
+
+extern "C" int kw_cdx_remaining_copy(kw_dedup *h, uint8_t *d_bytes, int64_t *d_off, int64_t *d_rows, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (int rc = exclude_state(h, "kw_cdx_remaining_copy")) return rc;
+    return kw_dedup_kept_copy(h, d_bytes, d_off, d_rows, stream);
+}
+
+extern "C" int kw_cdx_exclude_last_ms(kw_dedup *h, float *ms, int32_t k)
+{
+    if (!h || !ms || k < 0) return KW_EINVAL;
+    if (int rc = exclude_state(h, "kw_cdx_exclude_last_ms")) return rc;
+    for (int i = 0; i < k && i < 3; ++i) ms[i] = 0.f;
+    if (h->n == 0) return KW_OK;
+    if (k > 0) DDCHK(h, hipEventElapsedTime(&ms[0], h->ev[0], h->ev[4]));
+    for (int i = 1; i < k && i < 3; ++i) DDCHK(h, hipEventElapsedTime(&ms[i], h->ex_ev[i - 1], h->ex_ev[i]));
+    return KW_OK;
+}
+
 extern "C" int kw_dedup_last_ms(kw_dedup *h, float *ms, int32_t k)
 {
     if (!h || !ms) return KW_EINVAL;
@@ -1879,6 +2064,8 @@ extern "C" int kw_dedup_destroy(kw_dedup *h)
     if (h->d_collide) (void)hipFree(h->d_collide);
     if (h->d_sarena) (void)hipFree(h->d_sarena);
     for (auto &e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->ex_ev)
         if (e) (void)hipEventDestroy(e);
     delete h;
     return KW_OK;

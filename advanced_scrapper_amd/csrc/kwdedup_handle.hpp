@@ -1,10 +1,12 @@
 // libkwmatch: the kw_dedup handle (include/kwdedup.h), shared by dedup.hip (the keep-first run and its kept-rows
-// machinery) and cdx.hip (the CDX parser's row store and the CSV renderer, which reads the last run's kept rows).
+// machinery, the set-difference pass) and cdx.hip (the CDX and CSV parsers' row store and the CSV renderer, which
+// reads the last run's kept rows).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <unordered_map>
 
 #include "../../include/kwmatch.h"
 #include "../../include/kwdedup.h"
@@ -28,7 +30,8 @@ struct Scratch {
     uint32_t epoch;          // this run's table epoch (1..255): a slot of another epoch is empty, so the table is
                              //   cleared only when it moves, grows or the epoch wraps (the memset cost 1.4 ms a run)
     unsigned long long *cnt;   // [0], [2], [3], [4]: rows per code but KEPT; [5] differing pairs;
-                               // [7] the transform's next group of 64 rows; [9] CODE_COLLIDE rows listed
+                               // [7] the transform's next group of 64 rows; [9] CODE_COLLIDE rows listed;
+                               // the set-difference pass: [11] rows listed for the host, [12] rows seen
     unsigned long long *gnext;   // &cnt[7]
     int weak;                // tests: hash h1 down to 4 bits (forces the collision path)
     int stats;               // KW_DEDUP_STATS: print the differing pairs (rows looked up in the table)
@@ -70,7 +73,19 @@ struct kw_dedup {
     bool have_run = false;
     uint64_t run_serial = 0;       // kw_dedup_run calls so far (the renderer checks the kept rows are its run's)
     kw_cdx_store *cdx = nullptr;   // kw_cdx_* (cdx.hip)
+    // the URLs the host's exact pass of the last run saw (normalised bytes) and the first row holding each
+    std::unordered_map<std::string, uint32_t> collide_first;
+    // kw_cdx_run_exclude: the run it belongs to (0: none), link rows, rows seen; then the kept buffers hold the
+    // remaining rows
+    bool no_compact = false;       // set around kw_cdx_run_exclude's kw_dedup_run: no kept rows wanted of it
+    uint64_t ex_serial = 0;
+    int64_t ex_links = 0, ex_seen = 0;
+    hipEvent_t ex_ev[3] = {nullptr, nullptr, nullptr};
 };
+
+// dedup.hip: the set-difference pass over the last kw_dedup_run's rows (a raw run over the same arena, offsets and
+// codes): the first m rows are the exclude rows
+int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, hipStream_t st);
 
 #define DDCHK(h, x)                                                                    \
     do {                                                                               \

@@ -137,6 +137,72 @@ int kw_cdx_last_ms(kw_dedup *h, float *ms, int32_t k);
 /* The parser's tile: bytes of text a block classifies at once. */
 int kw_cdx_tile_bytes(void);
 
+/* ---- the scraper's resume filter (constant_rate_scrapper.py:312-360): quoted CSV in, the links not yet scraped out
+ *
+ *   scraped  = set(success["url"]) | set(failed["url"])
+ *   df_links = df_links[~df_links["url"].isin(scraped)]
+ *
+ * kw_csv_append parses one device-resident CSV text in pandas' default dialect (',' delimiter, '"' quotes that
+ * may hold delimiters, "" pairs and raw line breaks, records ended by '\n' or "\r\n") and appends the cells of one
+ * column to the row store of kw_cdx_*.  The success and failed files are appended first, the links file last;
+ * kw_cdx_run_exclude then drops every link row whose string is among the rows before it.
+ *
+ * A text is taken only where the parse provably equals pd.read_csv(text)[column].astype(str) ("Resume
+ * filter"; restated in tests/resume_rule.py); otherwise the verdict names the first failed condition, *bad_pos is
+ * the byte position of its first offender, and nothing is appended.  The conditions are tested in the order of the
+ * codes below, each over the whole text (the numbers in the comments are those of DESIGN.md's list).  Quote state
+ * is the parity of the '"' bytes before a byte. */
+#define KW_CSV_OK 0
+#define KW_CSV_NUL 1      /* 1. a NUL byte (its position) */
+#define KW_CSV_UTF8 2     /* 1. the text is not valid UTF-8 (the first byte a strict decoder stops at) */
+#define KW_CSV_HEADER 3   /* 2. the text does not start with header_line followed by '\n' or "\r\n" (position 0) */
+#define KW_CSV_QUOTE 4    /* 3. an opening '"' that neither starts a field nor follows a '"'; a closing '"' not
+                                followed by ',', '\n', '\r', '"' or the end of the text (the quote's position); a text
+                                that ends inside quotes (position n_bytes) */
+#define KW_CSV_CR 5       /* 4. a '\r' outside quotes that is not followed by '\n' (its position) */
+#define KW_CSV_ROWS 6     /* 5. no record after the header, or the store would pass the 2^32 - 1 rows of
+                                kw_dedup_run (position n_bytes) */
+#define KW_CSV_FIELDS 7   /* 6. a record that is not zero-length and has not exactly n_fields fields (the position
+                                of its first byte); records of no bytes but the terminator are skipped */
+#define KW_CSV_URL 8      /* 7. a cell of the column that, outer quotes removed, holds no ':', or holds a '"', '\n'
+                                or '\r' (the position of its record's first byte) */
+
+/* Parse n_bytes of text at d_text (as kw_cdx_append: 16-byte aligned, readable up to the next multiple of 16 past
+ * its end) and append the cells of column url_col (0-based, of n_fields) to the store, outer quotes removed; the
+ * rows' timestamps are 0.  header_line: the file's first line without its terminator, NUL-terminated (n_fields
+ * names separated by ','; no '"').  *verdict receives a KW_CSV_* code, *bad_pos the offender's byte position (-1 when
+ * OK), *n_rows the rows appended (0 unless OK).  Returns when the rows are in the store.  kw_cdx_last_ms [0] and
+ * [1] include these appends (event spans that hold the call's host round trips, not kernel time alone). */
+int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const char *header_line, int32_t url_col,
+                  int32_t n_fields, int64_t *n_rows, int32_t *verdict, int64_t *bad_pos, void *stream);
+
+/* per-row code of a link row of kw_cdx_run_exclude whose string is among the exclude rows (KW_URL_* above are
+ * 0..3; libkwmatch keeps 4 for itself) */
+#define KW_URL_SEEN 5
+
+/* The set difference over the store: its first n_exclude rows are the exclude rows, the rest the link rows.  Runs
+ * kw_dedup_run over the raw strings (no KW_DEDUP_NORMALIZE), then codes every link row KW_URL_SEEN when the first
+ * row holding its bytes is an exclude row, else KW_URL_KEPT: a link row whose first holder is another link row is
+ * kept, as isin does not deduplicate.  kw_dedup_counts keeps describing the keep-first run; the kept-rows buffers
+ * of the handle then hold the remaining link rows (kw_dedup_kept_size / kw_dedup_kept_copy give the same as
+ * kw_cdx_remaining_*), and kw_cdx_csv_* need a new kw_cdx_run. */
+int kw_cdx_run_exclude(kw_dedup *h, int64_t n_exclude, void *stream);
+
+/* The link rows' codes of the last kw_cdx_run_exclude into d_code (caller-owned, n_links bytes). */
+int kw_cdx_exclude_codes(kw_dedup *h, uint8_t *d_code, void *stream);
+
+/* counts[0..3) of the last kw_cdx_run_exclude: link rows, those seen, those remaining. */
+int kw_cdx_exclude_counts(kw_dedup *h, int64_t *counts);
+
+/* The remaining link rows, dense and in row order, as kw_dedup_kept_size / kw_dedup_kept_copy give the kept rows:
+ * d_bytes (n_bytes), d_off (n_rows + 1 offsets into d_bytes), d_rows (n_rows indices among the link rows, from 0). */
+int kw_cdx_remaining_size(kw_dedup *h, int64_t *n_rows, int64_t *n_bytes);
+int kw_cdx_remaining_copy(kw_dedup *h, uint8_t *d_bytes, int64_t *d_off, int64_t *d_rows, void *stream);
+
+/* Device times (ms) of the last kw_cdx_run_exclude: [0] the keep-first run, [1] the set-difference pass, [2] the
+ * remaining rows' compaction; k <= 3 values. */
+int kw_cdx_exclude_last_ms(kw_dedup *h, float *ms, int32_t k);
+
 #ifdef __cplusplus
 }
 #endif

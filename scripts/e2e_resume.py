@@ -1,0 +1,147 @@
+"""End-to-end timing of the resume filter's ``resume.remaining_urls``: the device route against the pandas route.
+
+Writes one synthetic ``yfin_urls.csv`` (--rows links, a tenth of them repeated) and, with the csv module as the
+scraper does, a success file (multi-line article cells) and a failed file that together cover about half of the
+links, then times ``remaining_urls()`` in a fresh child process per run (one warm-up, then the median of 5; a child
+initialises the GPU and creates the dedup handle before its clock starts, and nothing is exec'd after that).  Two
+configurations of this tree:
+
+    native   the device route (the default)
+    pandas   KW_RESUME_NATIVE=0: the reference's lines (constant_rate_scrapper.py:312-360), the baseline, as the
+             step has no counterpart at the parent commit
+
+Both must give the same counts and the same URLs.  Per run two clocks: the call alone (counts and the remaining
+rows as arrays), and the call plus ``urls()`` (the reference's ``list[str]``; on the pandas route the list exists
+when the call returns).  The result goes to --out (profiles/e2e_resume.json) and, as one JSON line, to stdout: per
+configuration the median, min and max seconds; for the device route the device times of the new kernels (parse +
+compaction of kw_csv_append, the keep-first run, the set-difference pass, the remaining rows' compaction) and the
+CSV bytes over the parse + compaction time.
+
+    python scripts/e2e_resume.py [--rows 1000000] [--out profiles/e2e_resume.json]
+"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+CHILD = r'''
+import hashlib, json, os, sys, time
+tree, folder = sys.argv[1:3]
+sys.path.insert(0, tree)
+os.chdir(folder)
+import torch
+from advanced_scrapper_amd import cdx_dedup, resume
+torch.cuda.init()
+g = cdx_dedup._dedup()
+torch.cuda.synchronize()
+sys.stdout = open(os.devnull, 'w')
+t0 = time.perf_counter()
+r = resume.remaining_urls()
+t1 = time.perf_counter()
+urls = r.urls()
+t2 = time.perf_counter()
+sys.stdout = sys.__stdout__
+res = {'seconds': t1 - t0, 'seconds_with_urls': t2 - t0, 'route': r.route,
+       'counts': [r.initial_total, r.scraped_success, r.scraped_fails, r.remaining],
+       'sha256': hashlib.sha256('\n'.join(urls).encode('utf-8')).hexdigest()}
+if r.route == 'device':
+    res['cdx_last_ms'] = g.cdx_last_ms()
+    res['exclude_last_ms'] = g.exclude_last_ms()
+print('E2E_RESUME ' + json.dumps(res))
+'''
+
+ARTICLE = ('{k} Shares of the company rose, then fell.\n"We expect a better quarter," the chief executive said, '
+           '"and a calmer one."\r\n\r\nAnalysts, on average, had expected {k} cents a share.\n') * 3
+
+
+def write_workload(folder, rows, seed):
+    import random
+    rng = random.Random(seed)
+    urls = ['https://finance.yahoo.com/news/%s-%d.html' % (rng.choice(['earnings', 'markets', 'why-shares, fell', 'é']), k)
+            for k in range(rows - rows // 10)]
+    links = urls + [rng.choice(urls) for _ in range(rows // 10)]
+    rng.shuffle(links)
+    with open(os.path.join(folder, 'yfin_urls.csv'), 'w', newline='', encoding='utf-8') as fh:
+        w = csv.writer(fh, lineterminator='\n')   # (what DataFrame.to_csv wrote)
+        w.writerow(['date_time', 'url'])
+        w.writerows((20200101000000 + k, u) for k, u in enumerate(links))
+    done = rng.sample(urls, len(urls) // 2)
+    n_ok = len(done) * 3 // 5
+    with open(os.path.join(folder, 'success_articles_yfin.csv'), 'w', newline='', encoding='utf-8') as fh:
+        w = csv.writer(fh)
+        w.writerow(["url", "datetime", "ticker_symbols", "author", "source", "source_url", "title", "article"])
+        w.writerows((u, '2024-01-02 03:04:05', 'AAPL, MSFT', 'A. Writer', 'Wire', 'https://wire/', 'A "title", quoted',
+                     ARTICLE.format(k=k)) for k, u in enumerate(done[:n_ok]))
+    with open(os.path.join(folder, 'failed_articles_yfin.csv'), 'w', newline='', encoding='utf-8') as fh:
+        w = csv.writer(fh)
+        w.writerow(["url", "error"])
+        w.writerows((u, 'HTTP 404, "gone"') for u in done[n_ok:])
+    return sum(os.path.getsize(os.path.join(folder, f)) for f in os.listdir(folder))
+
+
+def run_config(folder, env_extra, runs):
+    env = dict(os.environ)
+    env.pop('KW_RESUME_NATIVE', None)
+    env.update(env_extra)
+    got = []
+    for _ in range(runs + 1):   # the first is the warm-up
+        p = subprocess.run([sys.executable, '-c', CHILD, REPO, folder], env=env, cwd=REPO, capture_output=True,
+                           text=True, timeout=900)
+        if p.returncode != 0:
+            raise RuntimeError(f"child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith('E2E_RESUME ')][-1]
+        got.append(json.loads(line[len('E2E_RESUME '):]))
+    timed = got[1:]
+    assert len({r['sha256'] for r in got}) == 1, 'runs of one configuration gave different URLs'
+    res = {'env': env_extra, 'route': timed[-1]['route'], 'counts': timed[-1]['counts'], 'sha256': timed[-1]['sha256']}
+    for key in ('seconds', 'seconds_with_urls'):
+        v = [r[key] for r in timed]
+        res[key] = {'runs': v, 'median_s': statistics.median(v), 'min_s': min(v), 'max_s': max(v)}
+    if 'cdx_last_ms' in timed[-1]:
+        by_run = sorted(timed, key=lambda r: r['seconds'])[len(timed) // 2]   # the median run's device times
+        res['device_ms'] = dict(zip(('parse', 'parse_compaction'), by_run['cdx_last_ms'][:2]))
+        res['device_ms'].update(zip(('keep_first_run', 'set_difference_pass', 'remaining_compaction'),
+                                    by_run['exclude_last_ms']))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--rows', type=int, default=1_000_000)
+    ap.add_argument('--seed', type=int, default=20240229)
+    ap.add_argument('--runs', type=int, default=5)
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'e2e_resume.json'))
+    args = ap.parse_args()
+    with tempfile.TemporaryDirectory(prefix='e2e_resume_') as tmp:
+        n_bytes = write_workload(tmp, args.rows, args.seed)
+        res = {'rows': args.rows, 'seed': args.seed, 'csv_bytes': n_bytes, 'runs_per_config': args.runs,
+               'timed': 'resume.remaining_urls() in a fresh child per run, GPU initialised and handle created before '
+                        'the clock; 1 warm-up + the median of the runs; seconds_with_urls adds urls()'}
+        res['native'] = run_config(tmp, {}, args.runs)
+        res['pandas'] = run_config(tmp, {'KW_RESUME_NATIVE': '0'}, args.runs)
+    assert res['native']['route'] == 'device', 'the device route did not run'
+    ms = res['native']['device_ms']
+    res['parse_compaction_GBps'] = n_bytes / ((ms['parse'] + ms['parse_compaction']) / 1e3) / 1e9
+    res['set_difference_ms'] = ms['keep_first_run'] + ms['set_difference_pass'] + ms['remaining_compaction']
+    res['same_result'] = (res['native']['sha256'] == res['pandas']['sha256'] and
+                          res['native']['counts'] == res['pandas']['counts'])
+    res['baseline'] = 'pandas'
+    res['speedup_call'] = res['pandas']['seconds']['median_s'] / res['native']['seconds']['median_s']
+    res['speedup_with_urls'] = res['pandas']['seconds_with_urls']['median_s'] / res['native']['seconds_with_urls']['median_s']
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res))
+    if not res['same_result']:
+        sys.exit('the two routes gave different results')
+
+
+if __name__ == '__main__':
+    main()
