@@ -79,6 +79,8 @@ struct __attribute__((aligned(16))) FilterLds {
     uint2 sent[FS_WAVES][2 * WAVE];           // stage 2: the queue of entries {group-relative byte of the lane's
                                               // position 0, transposed survivor mask} (a ring)
     uint32_t spos[FS_WAVES][WAVE];            // a round's survivors' group-relative positions
+    uint2 eidx[FS_WAVES][WAVE];               // edge prefilter: lane 2 k + f's bit indices of document k's field f in
+                                              // FastTables::edge_pre / edge_suf (~0: the field is too short)
 };
 
 // the group document holding group-relative byte r (dstart[0] = 0 <= r < dstart[nd])
@@ -204,7 +206,8 @@ __device__ __forceinline__ void fk_stage1(const FastTables &FT, const FilterLds 
 // (1 KiB tiles, 16 bytes per lane, the next tiles' loads in flight): no per-document tile shapes or
 // set-up.  Keys that run over a field or document end are kept (a superset): the probe checks every
 // anchor against its field.  Non-ASCII bytes mark their field in dflags (rare: an LDS lookup of the
-// document, one atomic per field).
+// document, one atomic per field).  The edge prefilter's bits of each field (its first / last eight bytes
+// against the one-deletion prefix / suffix bitmaps) go there too: the epilogue kernels read them.
 template <int SH>
 __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds &L, const uint8_t *__restrict__ arena,
                                                  const int64_t *__restrict__ off, int64_t n_docs, const FastScratch &S,
@@ -233,6 +236,27 @@ __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds
         if (lane <= nd) dstart[lane] = (uint32_t)(o0 - gb);
         if (lane < nd) dtitle[lane] = (uint32_t)(o1 - gb);
         wave_sync();
+        // Edge prefilter (DH_EDGE0 / DH_EDGE1, for the epilogue): lane 2 k + f takes the first and the last eight
+        // bytes of document k's field f when it has at least EDGE_MIN_M + 1 bytes, as three aligned words each.  The
+        // loads go out ahead of the tile stream, which reads the same lines; the keys are hashed once the
+        // tiles' loads are out too, and the bitmaps are tested after the tile loop.
+        bool eact = false;
+        uint32_t ep[3] = {0u, 0u, 0u}, es[3] = {0u, 0u, 0u}, esh = 0;
+        {
+            const int k = lane >> 1, f = lane & 1;
+            if (k < nd) {
+                const uint32_t fb = f ? dtitle[k] : dstart[k], fe = f ? dstart[k + 1] : dtitle[k];
+                if (fe - fb >= EDGE_MIN_M + 1u && fe >= fb) {
+                    eact = true;
+                    const int64_t ap = gb + (int64_t)fb, as = gb + (int64_t)fe - 8;
+                    const uint32_t *pp = (const uint32_t *)(arena + (ap & ~(int64_t)3));
+                    const uint32_t *ps = (const uint32_t *)(arena + (as & ~(int64_t)3));
+                    esh = (uint32_t)(ap & 3) | ((uint32_t)(as & 3) << 2);
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) { ep[q] = pp[q]; es[q] = ps[q]; }
+                }
+            }
+        }
         // byte offsets below are 32-bit, from the group's first 16-byte block gbase (groups are < 2^31 bytes):
         // the loads take the SGPR base and a VGPR offset, no 64-bit address arithmetic per tile
         const uint8_t *gbase = arena + (gb & ~(int64_t)15);
@@ -343,10 +367,9 @@ __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds
             W[1] = v.y;
             W[2] = v.z;
             W[3] = v.w;
-            {
-                const uint32_t nx = (uint32_t)__shfl_down((int)v.x, 1, WAVE);
-                W[4] = lane == WAVE - 1 ? w4 : nx;
-            }
+            // the next lane's first word by a DPP move (wave_shl:1; lane 63 has no source lane and keeps `old`, the
+            // word after the tile): no LDS permute and no wait for it ahead of the hash
+            W[4] = (uint32_t)__builtin_amdgcn_update_dpp((int)w4, (int)v.x, 0x130, 0xf, 0xf, false);
             uint32_t valid = 0xFFFFu;
             if (tb < g0 || tb + 1024u > gl) {   // (uniform: only a group's first and last tiles)
                 const int32_t rlo = (int32_t)(g0 - lp), rhi = (int32_t)(gl - lp);
@@ -399,6 +422,18 @@ __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds
             load(v[k], w[k], blk + 1024 * k);
             __builtin_amdgcn_sched_barrier(0);
         }
+        {   // the edge keys' bit indices wait in LDS (no registers held across the tile loop)
+            uint2 ei = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+            if (eact) {
+                const uint32_t sp = esh & 3u, ss = esh >> 2;
+                const uint64_t kp = (uint64_t)__builtin_amdgcn_alignbyte(ep[1], ep[0], sp) |
+                                    ((uint64_t)__builtin_amdgcn_alignbyte(ep[2], ep[1], sp) << 32);
+                const uint64_t ks = (uint64_t)__builtin_amdgcn_alignbyte(es[1], es[0], ss) |
+                                    ((uint64_t)__builtin_amdgcn_alignbyte(es[2], es[1], ss) << 32);
+                ei = make_uint2(fk_edge_index(kp), fk_edge_index(ks));
+            }
+            L.eidx[wib][lane] = ei;
+        }
         for (bool more = true; more;) {
 #pragma unroll
             for (int k = 0; k < FS_AHEAD; ++k) {   // (unrolled: each tile in flight keeps its own registers)
@@ -408,8 +443,18 @@ __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds
                 blk += 1024;
             }
         }
+        // the edge bitmaps' words (global, 2 x 128 KB: L2) load while the group's last rounds run
+        const uint2 ei = L.eidx[wib][lane];
+        const bool etest = ei.x != 0xFFFFFFFFu;
+        uint32_t ewp = 0, ews = 0;
+        if (etest) {
+            ewp = FT.edge_pre[ei.x >> 5];
+            ews = FT.edge_suf[ei.y >> 5];
+        }
         while (en) round();   // the group's last survivors
         if (qn) round_at(qn, qr, __builtin_amdgcn_alignbyte(qx1, qx0, (uint32_t)(gb + qr) & 3u));
+        if (etest && (((ewp >> (ei.x & 31u)) | (ews >> (ei.y & 31u))) & 1u))   // (rare: one atomic per flagged field)
+            atomicOr(&S.dflags[d0 + (lane >> 1)], (lane & 1) ? DH_EDGE1 : DH_EDGE0);
     }
 }
 
@@ -735,39 +780,6 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void kw_probe_kernel(FastTables 
     if (lane == 0) atomicAdd(&S.stats[1], a);
 }
 
-// the edge-prefilter flags of a document: first / last eight bytes of each field (lanes 0..3) against
-// the global one-deletion prefix / suffix bitmaps
-__device__ __forceinline__ uint32_t fk_edge_flags(const FastTables &FT, const FastDoc &D)
-{
-    const int lane = lane_id();
-    const int f = lane >> 1;
-    const int64_t fb = f ? D.t1 : D.t0, fe = f ? D.t2 : D.t1;
-    bool e = false;
-    if (lane < 4 && fe - fb >= (int64_t)EDGE_MIN_M + 1) {
-        const int64_t a = (lane & 1) ? fe - 8 : fb;
-        const uint64_t k = (uint64_t)ld_u32_unaligned(D.arena, a) | ((uint64_t)ld_u32_unaligned(D.arena, a + 4) << 32);
-        const uint32_t idx = fk_edge_index(k);
-        e = (((lane & 1) ? FT.edge_suf : FT.edge_pre)[idx >> 5] >> (idx & 31u)) & 1u;
-    }
-    const uint64_t em = __ballot(e);
-    return ((em & 3ull) ? DH_EDGE0 : 0u) | ((em & 12ull) ? DH_EDGE1 : 0u);
-}
-
-// fk_edge_flags with the keys already loaded (lanes 0..3: epi_prefetch)
-__device__ __forceinline__ uint32_t fk_edge_flags_key(const FastTables &FT, const FastDoc &D, uint64_t k)
-{
-    const int lane = lane_id();
-    const int f = lane >> 1;
-    const int64_t fb = f ? D.t1 : D.t0, fe = f ? D.t2 : D.t1;
-    bool e = false;
-    if (lane < 4 && fe - fb >= (int64_t)EDGE_MIN_M + 1) {
-        const uint32_t idx = fk_edge_index(k);
-        e = (((lane & 1) ? FT.edge_suf : FT.edge_pre)[idx >> 5] >> (idx & 31u)) & 1u;
-    }
-    const uint64_t em = __ballot(e);
-    return ((em & 3ull) ? DH_EDGE0 : 0u) | ((em & 12ull) ? DH_EDGE1 : 0u);
-}
-
 // ---------------------------------------------------------------- transcoded view of non-ASCII documents
 // A document with a non-ASCII field is rewritten to one byte per code point (ASCII as is, the non-ASCII code
 // points of the fuzzy names as their markers 0x81..0xFF, any other code point 0x80) in S.tarena by
@@ -834,8 +846,7 @@ __device__ uint32_t tx_field(const uint32_t *txk, const uint32_t *txv, const uin
         if (blk + 1024 < fe) ld(blk + 1024, vn, wn);
         uint32_t W[5];
         W[0] = v.x; W[1] = v.y; W[2] = v.z; W[3] = v.w;
-        W[4] = (uint32_t)__shfl_down((int)W[0], 1, WAVE);
-        if (lane == WAVE - 1) W[4] = w4;
+        W[4] = (uint32_t)__builtin_amdgcn_update_dpp((int)w4, (int)W[0], 0x130, 0xf, 0xf, false);   // wave_shl:1; lane 63: w4
         const int64_t r0 = fb - lp, r2 = fe - lp;
         const int jlo = r0 <= 0 ? 0 : (r0 >= 16 ? 16 : (int)r0);
         const int jhi = r2 <= 0 ? 0 : (r2 >= 16 ? 16 : (int)r2);
@@ -1131,10 +1142,9 @@ uint32_t epi_big_doc(const FastTables &FT, const FastScratch &S, const DevScratc
     D.l2 = (int32_t)(D.t2 - D.t0);
     const uint32_t ibeg = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 3);
     const uint32_t dfl = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 5);
-    uint32_t flags = dfl & ~DH_DEFER;
+    const uint32_t flags = dfl & ~DH_DEFER;   // (with the filter's edge-prefilter bits)
     const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 4);
     const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 4);
-    flags |= fk_edge_flags(FT, D);
     const uint64_t *src = S.items + ibeg;
     bool view = true;
     if (tx) {
@@ -1215,22 +1225,15 @@ __device__ __forceinline__ void epi_meta(const FastScratch &S, const int64_t *__
     hv = lane == 3 ? S.hdr[d] : (lane == 4 ? S.ncnt[d] : (lane == 5 ? make_uint2(0u, S.dflags[d]) : make_uint2(0u, 0u)));
 }
 
-// the loads that depend on epi_meta's: lanes 0..3 the edge keys (first / last eight bytes of each field),
-// lanes < n0 + n1 the document's first 64 items (all-ASCII documents the epilogue will finish only)
-__device__ __forceinline__ void epi_prefetch(const uint8_t *__restrict__ arena, const FastScratch &S, int64_t ov,
-                                             uint2 hv, uint64_t &ek, uint64_t &itp)
+// the loads that depend on epi_meta's: lanes < n0 + n1 the document's first 64 items (all-ASCII documents the
+// epilogue will finish only)
+__device__ __forceinline__ void epi_prefetch(const FastScratch &S, int64_t ov, uint2 hv, uint64_t &itp)
 {
     const int lane = lane_id();
     const int64_t t0 = rdlane64(ov, 0), t1 = rdlane64(ov, 1), t2 = rdlane64(ov, 2);
     const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 5);
     if (fl & (DH_NA0 | DH_NA1 | DH_DEFER)) return;
     if (t1 - t0 > MAX_FIELD_BYTES || t2 - t1 > MAX_FIELD_BYTES) return;
-    const int f = lane >> 1;
-    const int64_t fb = f ? t1 : t0, fe = f ? t2 : t1;
-    if (lane < 4 && fe - fb >= (int64_t)EDGE_MIN_M + 1) {
-        const int64_t a = (lane & 1) ? fe - 8 : fb;
-        ek = (uint64_t)ld_u32_unaligned(arena, a) | ((uint64_t)ld_u32_unaligned(arena, a + 4) << 32);
-    }
     const uint32_t ibeg = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 3);
     const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 4) + (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 4);
     if ((uint32_t)lane < n) itp = S.items[ibeg + (uint32_t)lane];
@@ -1260,14 +1263,15 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
     O.n = 0;
     TaskCounts TC = {0u, 0u, 0u, 0u};
     // Software pipeline over the wave's documents: the next document's offsets / header / counts / flags
-    // are in flight while the current one is processed, and its edge keys and first 64 items are loaded
-    // right after, so a document starts with only the edge-bitmap and name-table round trips ahead of it.
+    // are in flight while the current one is processed, and its first 64 items are loaded right after, so a
+    // document starts with only the name-table round trips ahead of it (its edge-prefilter bits are the filter's,
+    // in its flags).
     int64_t ov = 0;
     uint2 hv = make_uint2(0u, 0u);
-    uint64_t ek = 0, itp = 0;
+    uint64_t itp = 0;
     if (wave < n_docs) {
         epi_meta(S, off, wave, ov, hv);
-        epi_prefetch(arena, S, ov, hv, ek, itp);
+        epi_prefetch(S, ov, hv, itp);
     }
     unsigned long long ekt[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     EK_T0(tk0);
@@ -1291,7 +1295,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
             // a non-ASCII field: the transcoded view, or the resolve kernel
             const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 4);
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 4);
-            const uint32_t fl = flags | fk_edge_flags(FT, D);
+            const uint32_t fl = flags;
             bool done = false;
             if (FK_TX && epi_tx_doc(FT, S, GS, D, S.vrec[d], ibeg, n0, n1, fl, items, wave, O, TC, &done)) {
                 ++ntx;
@@ -1324,9 +1328,6 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
             const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 4);
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 4);
             EK_TACC(ekt[5], td0);
-            EK_T0(td1);
-            flags |= fk_edge_flags_key(FT, D, ek);
-            EK_TACC(ekt[6], td1);
             bool defer = (flags & DH_DEFER) != 0 || D.t1 - D.t0 > MAX_FIELD_BYTES || D.t2 - D.t1 > MAX_FIELD_BYTES;
             if (defer && lane == 0) atomicAdd(&S.stats[15], 1ull);   // (rare: counted where they happen)
             bool queued = false;
@@ -1393,9 +1394,8 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
             }
         }
         EK_T0(td3);
-        ek = 0;
         itp = 0;
-        if (dn < n_docs) epi_prefetch(arena, S, ovn, hvn, ek, itp);
+        if (dn < n_docs) epi_prefetch(S, ovn, hvn, itp);
         ov = ovn;
         hv = hvn;
         EK_TACC(ekt[8], td3);
@@ -1441,8 +1441,8 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
 // The same decisions as kw_epi_kernel, but a wave takes a filter group (32 consecutive documents) at a time
 // and works the items of its plain documents (all-ASCII, not deferred, <= 64 items per field) 64 at a time
 // across documents: lane = item, a batch is a run of whole (document, field) segments, sorted by (segment,
-// name, position), the name groups are (segment, name) runs.  Document-level work (edge prefilter, short-field
-// tasks, headers, view records) is lane = document.  Edge windows of flagged documents and the other
+// name, position), the name groups are (segment, name) runs.  Document-level work (short-field tasks,
+// headers, view records) is lane = document.  Edge windows of the documents the filter flagged and the other
 // documents (non-ASCII, big, deferred) take the per-document code after the batches.
 __device__ __forceinline__ uint32_t ep_n(const uint32_t (&v)[2], uint32_t f) { return f ? v[1] : v[0]; }
 
@@ -1476,26 +1476,14 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
     for (int64_t g = wave; g < n_groups; g += n_waves) {
         const int64_t d0 = g * FG_DOCS;
         const int nd = (int)(n_docs - d0 < FG_DOCS ? n_docs - d0 : FG_DOCS);
-        // ---- lane = document: offsets, header, counts, flags, the edge prefilter
+        // ---- lane = document: offsets, header, counts, flags
         const bool act = lane < nd;
         const int64_t d = d0 + (act ? lane : 0);
         const int64_t t0 = act ? off[2 * d] : 0, t1 = act ? off[2 * d + 1] : 0, t2 = act ? off[2 * d + 2] : 0;
         const uint2 hd = act ? S.hdr[d] : make_uint2(0u, 0u);
         const uint2 nc = act ? S.ncnt[d] : make_uint2(0u, 0u);
         const uint32_t fl = act ? S.dflags[d] : 0u;
-        uint32_t ef = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int f = k >> 1;
-            const int64_t fb = f ? t1 : t0, fe = f ? t2 : t1;
-            if (act && fe - fb >= (int64_t)EDGE_MIN_M + 1) {
-                const int64_t a = (k & 1) ? fe - 8 : fb;
-                const uint64_t key8 = (uint64_t)ld_u32_unaligned(arena, a) | ((uint64_t)ld_u32_unaligned(arena, a + 4) << 32);
-                const uint32_t idx = fk_edge_index(key8);
-                if ((((k & 1) ? FT.edge_suf : FT.edge_pre)[idx >> 5] >> (idx & 31u)) & 1u) ef |= f ? DH_EDGE1 : DH_EDGE0;
-            }
-        }
-        const uint32_t flags = fl | ef;
+        const uint32_t flags = fl;   // (the edge prefilter's bits are the filter's: no key or bitmap loads here)
         const int64_t l0 = t1 - t0, l1 = t2 - t1;
         // TXB: a document with a non-ASCII field joins the batches on its transcoded view (the transcoding
         // kernel's record V: the view's place, the fields' code point counts; its items' positions become code
@@ -1679,7 +1667,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
                     const uint32_t sh0 = (uint32_t)(fb - a0);
                     // the field's <= 67 bytes as dwords loaded six at a time (three round trips, not one per dword;
                     // the arena is padded; more at once spills the epilogue's registers), then the names'
-                    // signatures four at a time
+                    // signatures one at a time (an LDS copy of them per workgroup was measured: no faster)
                     uint64_t fsig = 0;
                     for (uint32_t w0 = 0; 4 * w0 < n + sh0; w0 += 6) {
                         uint32_t xw[6];
@@ -1710,7 +1698,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
             }
         }
         // edge windows of the flagged plain documents (after all their items: the decided set is complete)
-        uint64_t edm = __ballot(flat && (ef & (DH_EDGE0 | DH_EDGE1)));
+        uint64_t edm = __ballot(flat && (fl & (DH_EDGE0 | DH_EDGE1)));
         while (edm) {
             const int l = __builtin_ctzll(edm);
             edm &= edm - 1;
