@@ -37,7 +37,7 @@ KW_NOPOS = 0xFFFFFFFF
 
 HIT_DTYPE = np.dtype([('doc', '<u4'), ('pattern', '<u4'), ('pos', '<u4'), ('field', '<u4')])
 
-# every symbol include/kwmatch.h and include/kwdedup.h declare
+# every symbol include/kwmatch.h, include/kwdedup.h and include/kwrows.h declare
 EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_last_kernel_ms',
            'kw_last_kernel_times', 'kw_doc_routes', 'kw_last_error', 'kw_destroy',
            'kw_scan_host', 'kw_hits_host', 'kw_device_count', 'kw_device_init',
@@ -49,7 +49,9 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_cdx_begin', 'kw_cdx_append', 'kw_cdx_rows', 'kw_cdx_store_copy', 'kw_cdx_run', 'kw_cdx_csv_size',
            'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes',
            'kw_csv_append', 'kw_cdx_run_exclude', 'kw_cdx_exclude_codes', 'kw_cdx_exclude_counts',
-           'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms')
+           'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms',
+           'kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_last_error',
+           'kw_rows_destroy')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -68,6 +70,7 @@ KW_URL_SEEN = 5   # a link row of kw_cdx_run_exclude whose string is among the e
 (KW_CSV_OK, KW_CSV_NUL, KW_CSV_UTF8, KW_CSV_HEADER, KW_CSV_QUOTE, KW_CSV_CR, KW_CSV_ROWS, KW_CSV_FIELDS,
  KW_CSV_URL) = range(9)
 KW_DEDUP_NORMALIZE = 1
+KW_ROWS_OK, KW_ROWS_INVALID_REGEX = 0, 1   # verdicts of kw_rows_run (include/kwrows.h)
 KW_N_STATS = 21
 # KW_RESCAN_* bits of stats[20] (include/kwmatch.h)
 KW_RESCAN_GENERIC_ITEMS, KW_RESCAN_RESULTS, KW_RESCAN_GENERIC_CPS = 1, 2, 4
@@ -133,6 +136,16 @@ def lib() -> ctypes.CDLL:
     for f in ('kw_csv_append', 'kw_cdx_run_exclude', 'kw_cdx_exclude_codes', 'kw_cdx_exclude_counts',
               'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms'):
         getattr(L, f).restype = ctypes.c_int
+    L.kw_rows_create.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(vp)]
+    L.kw_rows_run.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                              ctypes.POINTER(i32), vp]
+    L.kw_rows_copy.argtypes = [vp, vp, vp, vp, vp]
+    L.kw_rows_last_ms.argtypes = [vp, vp, i32]
+    L.kw_rows_destroy.argtypes = [vp]
+    for f in ('kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_destroy'):
+        getattr(L, f).restype = ctypes.c_int
+    L.kw_rows_last_error.argtypes = [vp]
+    L.kw_rows_last_error.restype = ctypes.c_char_p
     L.kw_compile.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)]
     L.kw_compile.restype = ctypes.c_int
     L.kw_scan.argtypes = [vp, vp, vp, i64, vp]

@@ -36,7 +36,7 @@ from .ingest import NativeChunk, ShardChunk
 from .dates import parse_date
 from .kb import (ATTRIBUTES, compile_kb, extract_time_periods, is_within_period,  # noqa: F401 (re-export)
                  process_json_data, read_and_process_json_files)
-from .rows import assemble_json_raw, assemble_json_rows
+from .rows import assemble_json_device, assemble_json_raw, assemble_json_rows
 from .matcher import (GpuMatcher, assemble_ticker_matches, background_sample, field_str, group_hits,  # noqa: F401
                       pack_fields, records_from_tensor, resolve_host_positions)
 
@@ -290,13 +290,35 @@ def _hit_rows(chunk, matcher, hits, dates, error):
     return by_ticker, None, None
 
 
+def _rows_on_device(matcher, hits, dates) -> bool:
+    """The JSON cells of ``hits`` can come from the records in device memory (rows.assemble_json_device): the
+    matcher offers that route, ``hits`` is unchanged what its last fetch returned (so the device holds these
+    very records: not gathered from other ranks, no host-resolved positions filled in), no name is
+    host-resolved (its KW_NOPOS record would be ambiguous), and periods and dates have integer forms.
+    ``KW_ROWS_DEVICE=0`` keeps the host route."""
+    if os.environ.get('KW_ROWS_DEVICE', '1') == '0':
+        return False
+    same = getattr(matcher, 'fetched_is', None)
+    if same is None or not same(hits) or any(matcher.ckb.host_regex):
+        return False
+    return matcher.ckb.occurrences_us() is not None   # (dates without one: both routes answer None)
+
+
+def _json_raw(matcher, hits, dates):
+    """rows.assemble_json_raw's arrays of a chunk's records: built on the device when :func:`_rows_on_device`
+    allows it, by libkwrows on the host otherwise."""
+    if _rows_on_device(matcher, hits, dates):
+        return assemble_json_device(matcher, dates)
+    return assemble_json_raw(matcher.ckb, hits, dates)
+
+
 def _native_rows(chunk, matcher, hits, dates, error):
-    """The rows of a native chunk rendered in C (egress.render_native: JSON cells from rows.assemble_json_raw,
+    """The rows of a native chunk rendered in C (egress.render_native: JSON cells from :func:`_json_raw`,
     the other cells straight from the tokenized chunk), up to its first failing article, with that article's
     exception and row (as :func:`_hit_rows`); ``None`` when only the Python path can answer."""
     if not isinstance(chunk, NativeChunk) or hits is None:
         return None
-    raw = assemble_json_raw(matcher.ckb, hits, dates)
+    raw = _json_raw(matcher, hits, dates)
     if raw is None:
         return None
     row_doc = raw[0]

@@ -94,6 +94,8 @@ class GpuMatcher:
             raise _native.KwError(rc, msg.decode() if msg else '')
         self.h = h
         self._keep = None
+        self._rows = None         # rows.DeviceRows of this KB, made on first use
+        self._fetched = None      # the array the last fetch_host() / fetch() returned
 
     @property
     def torch(self):
@@ -105,6 +107,9 @@ class GpuMatcher:
         return cls(compile_kb(processed_data), device, background)
 
     def close(self):
+        if getattr(self, '_rows', None) is not None:
+            self._rows.close()
+            self._rows = None
         if getattr(self, 'h', None) is not None and self.h.value:
             _native.lib().kw_destroy(self.h)
             self.h = None
@@ -127,6 +132,7 @@ class GpuMatcher:
             stream = self.torch.cuda.current_stream(self.device)
         sp = ctypes.c_void_p(stream.cuda_stream) if hasattr(stream, 'cuda_stream') else ctypes.c_void_p(stream)
         self._keep = (d_arena, d_off)
+        self._fetched = None
         _native.check(_native.lib().kw_scan(self.h, _native.ptr(d_arena), _native.ptr(d_off), int(n_docs), sp), self.h)
 
     def n_hits(self) -> int:
@@ -158,7 +164,8 @@ class GpuMatcher:
 
     def fetch(self) -> np.ndarray:
         """Records of the last scan on the host (structured HIT_DTYPE array)."""
-        return records_from_tensor(self.hits_device())
+        self._fetched = records_from_tensor(self.hits_device())
+        return self._fetched
 
     def doc_routes(self, n_docs: int) -> np.ndarray:
         """Per document of the last scan: which kernel finished it (_native.KW_ROUTE_*)."""
@@ -203,6 +210,7 @@ class GpuMatcher:
         arena = np.ascontiguousarray(arena, dtype=np.uint8)
         off = np.ascontiguousarray(off[:2 * int(n_docs) + 1], dtype=np.int64)
         self._keep = (arena, off)
+        self._fetched = None
         _native.check(_native.lib().kw_scan_host(self.h, _native.ptr(arena), int(arena.size), _native.ptr(off),
                                                  int(n_docs)), self.h)
 
@@ -212,7 +220,35 @@ class GpuMatcher:
         out = np.empty(max(n, 1), dtype=_native.HIT_DTYPE)
         cnt = ctypes.c_int64()
         _native.check(_native.lib().kw_hits_host(self.h, _native.ptr(out), n, ctypes.byref(cnt)), self.h)
-        return out[:cnt.value]
+        self._fetched = out[:cnt.value]
+        return self._fetched
+
+    # -- the per-ticker match cells from the records in HBM (include/kwrows.h)
+    def fetched_is(self, hits) -> bool:
+        """``hits`` is, unchanged in identity, what the last :meth:`fetch_host` / :meth:`fetch` returned: the
+        records of the last scan still in device memory are then these."""
+        return hits is not None and hits is self._fetched
+
+    def rows_handle(self):
+        """The KB's ``kw_rows`` handle (rows.DeviceRows), or ``None`` when its periods have no integer form."""
+        if self._rows is None:
+            from . import rows
+            tables = rows._kb_tables(self.ckb)
+            if tables is None:
+                return None
+            self._rows = rows.DeviceRows(self.device, tables, len(self.ckb.tickers))
+        return self._rows
+
+    def rows_device(self, date_us: np.ndarray, date_ok: np.ndarray):
+        """rows.assemble_json_raw's arrays of the last scan's records, built on the device (``None``: an
+        in-period name whose regex does not compile, or no integer periods)."""
+        handle = self.rows_handle()
+        if handle is None:
+            return None
+        n = ctypes.c_int64()
+        p = ctypes.c_void_p()
+        _native.check(_native.lib().kw_hits(self.h, ctypes.byref(n), ctypes.byref(p)), self.h)
+        return handle.run(p, int(n.value), date_us, date_ok)
 
     def match_device(self, texts: Sequence[str], titles: Sequence[str]):
         """Pack, upload and scan; the records as a device tensor [n, 4] (int32 view of kw_hit)."""

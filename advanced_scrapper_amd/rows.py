@@ -7,6 +7,9 @@ C routine (csrc/kwrows.c, ``lib/libkwrows.so``) applies the period filter on int
 (``kb.period_us``) and writes the JSON text exactly as ``json.dumps`` does.  It returns ``None`` when only
 the Python path can answer: a date or period bound without a UTC offset, or an in-period name whose regex
 does not compile (the Python path raises the reference's ``re.error``).
+
+``assemble_json_device`` builds the same arrays on the GPU from the records the scan left in HBM
+(csrc/kwrows.hip, include/kwrows.h); the host route above stays the fallback.
 """
 from __future__ import annotations
 
@@ -86,6 +89,107 @@ def assemble_json_rows(ckb: CompiledKB, hits: np.ndarray, dates: Sequence) -> Op
             for r in range(n)]
 
 
+def _empty():
+    return (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(1, np.int64))
+
+
+def date_arrays(dates: Sequence):
+    """Per document the article date as epoch microseconds (int64) and whether it exists (uint8), or ``None``
+    when a date has no integer form (no UTC offset)."""
+    try:
+        if hasattr(dates, 'epoch_us_arrays'):            # dates.Dates: integer forms without datetimes
+            return dates.epoch_us_arrays()
+        n_docs = len(dates)
+        date_us = np.zeros(n_docs, dtype=np.int64)
+        date_ok = np.zeros(n_docs, dtype=np.uint8)
+        for i, d in enumerate(dates):
+            if d is not None:
+                date_us[i] = epoch_us(d)
+                date_ok[i] = 1
+        return date_us, date_ok
+    except TypeError:
+        return None
+
+
+def assemble_json_device(matcher, dates: Sequence):
+    """:func:`assemble_json_raw` of the records of ``matcher``'s last scan, built on the device from the
+    records in HBM (csrc/kwrows.hip, ``kw_rows_run`` on ``kw_hits``' pointer): the same four arrays, byte for
+    byte.  ``None`` as :func:`assemble_json_raw` (no integer periods or dates, an in-period name whose regex
+    does not compile)."""
+    tables = _kb_tables(matcher.ckb)
+    if tables is None:
+        return None
+    if len(dates) == 0:
+        return _empty()
+    prepared = date_arrays(dates)
+    if prepared is None:
+        return None
+    return matcher.rows_device(prepared[0], prepared[1])
+
+
+class DeviceRows:
+    """One KB's occurrence tables on one GPU (a ``kw_rows`` handle, include/kwrows.h)."""
+
+    def __init__(self, device: int, tables, n_tickers: int):
+        off, ti, rank, lo, hi, invalid, key_buf, key_off = tables
+        self.h = None
+        h = ctypes.c_void_p()
+        L = _native.lib()
+        rc = L.kw_rows_create(int(device), _ptr(off), _ptr(ti), _ptr(rank), _ptr(lo), _ptr(hi), _ptr(invalid),
+                              _ptr(key_buf), _ptr(key_off), len(off) - 1, int(n_tickers), ctypes.byref(h))
+        if rc != _native.KW_OK:
+            msg = L.kw_rows_last_error(h)
+            if h.value:
+                L.kw_rows_destroy(h)
+            raise _native.KwError(rc, msg.decode() if msg else '')
+        self.h = h
+
+    def _check(self, rc: int) -> None:
+        if rc != _native.KW_OK:
+            msg = _native.lib().kw_rows_last_error(self.h)
+            raise _native.KwError(rc, msg.decode('utf-8', 'replace') if msg else '')
+
+    def run(self, d_hits, n_hits: int, date_us: np.ndarray, date_ok: np.ndarray, stream=None):
+        """The four arrays of :func:`assemble_json_raw` for ``n_hits`` device records at ``d_hits`` (a raw
+        pointer, or a tensor), or ``None`` on the verdict KW_ROWS_INVALID_REGEX."""
+        date_us = np.ascontiguousarray(date_us, dtype=np.int64)
+        date_ok = np.ascontiguousarray(date_ok, dtype=np.uint8)
+        if len(date_ok) != len(date_us):
+            raise ValueError('date_us and date_ok differ in length')
+        if not isinstance(d_hits, (int, ctypes.c_void_p)):
+            d_hits = _native.ptr(d_hits)
+        n_rows, n_bytes, verdict = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        L = _native.lib()
+        self._check(L.kw_rows_run(self.h, d_hits, int(n_hits), _ptr(date_us), _ptr(date_ok), len(date_us),
+                                  ctypes.byref(n_rows), ctypes.byref(n_bytes), ctypes.byref(verdict), stream))
+        if verdict.value == _native.KW_ROWS_INVALID_REGEX:
+            return None
+        n = int(n_rows.value)
+        row_doc = np.empty(n, dtype=np.int32)
+        row_ti = np.empty(n, dtype=np.int32)
+        out = np.empty(int(n_bytes.value), dtype=np.uint8)
+        out_off = np.empty(2 * n + 1, dtype=np.int64)
+        self._check(L.kw_rows_copy(self.h, _ptr(row_doc), _ptr(row_ti), _ptr(out), _ptr(out_off)))
+        return row_doc, row_ti, out, out_off
+
+    def last_ms(self):
+        """Device times (ms) of the last run: order, expand, render, total."""
+        v = np.zeros(4, dtype=np.float32)
+        self._check(_native.lib().kw_rows_last_ms(self.h, _ptr(v), 4))
+        return dict(zip(('order', 'expand', 'render', 'total'), (float(x) for x in v)))
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            _native.lib().kw_rows_destroy(self.h)
+        self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def assemble_json_raw(ckb: CompiledKB, hits: np.ndarray, dates: Sequence):
     """The rows of :func:`assemble_json_rows` as arrays: (row_doc int32[n], row_ti int32[n] (KB ticker
     index), JSON bytes uint8, offsets int64[2n + 1]: row r's text_matches then title_matches), or ``None``."""
@@ -94,19 +198,11 @@ def assemble_json_raw(ckb: CompiledKB, hits: np.ndarray, dates: Sequence):
         return None
     n_docs = len(dates)
     if len(hits) == 0 or n_docs == 0:
-        return (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(1, np.int64))
-    try:
-        if hasattr(dates, 'epoch_us_arrays'):            # dates.Dates: integer forms without datetimes
-            date_us, date_ok = dates.epoch_us_arrays()
-        else:
-            date_us = np.zeros(n_docs, dtype=np.int64)
-            date_ok = np.zeros(n_docs, dtype=np.uint8)
-            for i, d in enumerate(dates):
-                if d is not None:
-                    date_us[i] = epoch_us(d)
-                    date_ok[i] = 1
-    except TypeError:
+        return _empty()
+    prepared = date_arrays(dates)
+    if prepared is None:
         return None
+    date_us, date_ok = prepared
     h = np.ascontiguousarray(hits[np.lexsort((hits['pos'], hits['pattern'], hits['field'], hits['doc']))])
     assert h.dtype == _native.HIT_DTYPE
     off, ti, rank, lo, hi, invalid, key_buf, key_off = tables

@@ -1,0 +1,75 @@
+/*
+ * kwrows.h — C-ABI of the per-ticker match cells built on the GPU (libkwmatch.so,
+ * advanced_scrapper_amd/csrc/kwrows.hip).
+ *
+ * What it replaces.  The reference assembles, per article, the dict
+ *     ticker_matches[ticker] = {'text': {name: [pos, ...]}, 'title': {...}}   match_keywords.py:159-187
+ * and writes json.dumps of the two inner dicts into the ticker's CSV (:137-138).
+ * kw_rows_run turns hit records that are already in device memory (kw_hits'
+ * pointer, or any caller buffer of kw_hit) into those rows: one row per
+ * (article, ticker) in article order then KB ticker order, each with its
+ * text_matches and title_matches JSON text exactly as json.dumps writes it.
+ *
+ * Rules: a (document, field, pattern) group matches ticker t iff one of the
+ * pattern's occurrences for t has lo <= date <= hi (both inclusive); the name's
+ * place inside t's dict is the rank of the first such occurrence in table order;
+ * names stand in rank order, positions ascending; a record with pos == KW_NOPOS
+ * adds no number (a group of only such records prints "[]").  Documents with
+ * date_ok == 0 and records with doc >= n_docs give nothing.
+ *
+ * Conventions as kwmatch.h: 0 or a negative KW_E* code; kw_rows_last_error gives
+ * the message; one handle per device and host thread.
+ */
+#ifndef KWROWS_H
+#define KWROWS_H
+
+#include <stdint.h>
+
+#include "kwmatch.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct kw_rows kw_rows;
+
+/* verdicts of kw_rows_run */
+#define KW_ROWS_OK 0
+#define KW_ROWS_INVALID_REGEX 1   /* an in-period match of a pattern with invalid_rx set: the run has no
+                                     rows (the reference's re.finditer raises re.error there, :178/:180) */
+
+/* Upload one knowledge base's tables to `device` (host arrays, copied).
+ *   occ_off[n_patterns + 1]  CSR over patterns of the occurrence table, in the reference's traversal order
+ *   occ_ti / occ_rank        per occurrence: KB ticker index (0 <= ti < n_tickers), traversal rank
+ *   occ_lo / occ_hi          per occurrence: period bounds in epoch microseconds, open = INT64_MIN / INT64_MAX
+ *   invalid_rx[n_patterns]   1: the name's regex does not compile
+ *   keys / key_off           json.dumps(name) of pattern p = keys[key_off[p]:key_off[p + 1]] (quotes included) */
+int kw_rows_create(int32_t device, const int64_t *occ_off, const int32_t *occ_ti, const int32_t *occ_rank,
+                   const int64_t *occ_lo, const int64_t *occ_hi, const uint8_t *invalid_rx, const uint8_t *keys,
+                   const int64_t *key_off, int32_t n_patterns, int32_t n_tickers, kw_rows **out);
+
+/* Build the rows of n_hits device records (any order; n_hits < 2^31; d_hits 16-byte aligned, as kw_hits'
+ * pointer and any device allocation are) over n_docs documents.  date_us /
+ * date_ok: host arrays, per document the article date in epoch microseconds and whether it exists.
+ * Returns after the device finished: *n_rows rows and *n_bytes of JSON text are then held by the handle
+ * (both 0 when *verdict is KW_ROWS_INVALID_REGEX).  stream: a hipStream_t (NULL = default stream); the
+ * records must be complete on it.  A pattern index >= n_patterns in a counted record is KW_EINVAL. */
+int kw_rows_run(kw_rows *r, const kw_hit *d_hits, int64_t n_hits, const int64_t *date_us, const uint8_t *date_ok,
+                int64_t n_docs, int64_t *n_rows, int64_t *n_bytes, int32_t *verdict, void *stream);
+
+/* Copy the last run's result into host buffers: row_doc[n_rows], row_ti[n_rows] (KB ticker index),
+ * json[n_bytes], json_off[2 * n_rows + 1] (row r: text_matches = json[off[2r]:off[2r+1]], title_matches =
+ * json[off[2r+1]:off[2r+2]]; json_off[0] = 0 also for an empty result). */
+int kw_rows_copy(kw_rows *r, int32_t *row_doc, int32_t *row_ti, uint8_t *json, int64_t *json_off);
+
+/* Device times (ms) of the last run, up to 4 values: [0] order (count, scan, scatter and sort of the
+ * records), [1] expand (groups -> entries and their order), [2] render (byte lengths, scans, fill), [3] all. */
+int kw_rows_last_ms(kw_rows *r, float *ms, int32_t n);
+
+const char *kw_rows_last_error(kw_rows *r);
+int kw_rows_destroy(kw_rows *r);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

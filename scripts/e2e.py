@@ -10,6 +10,13 @@ one by one (read, dates, arena, GPU, render, write, sort) for the split; both pa
 bytes.  One JSON line: end-to-end articles/s of main(), the split, the host threads.
 
     python scripts/e2e.py [--docs 200000] [--chunksize 20000]
+
+``--rows-ab OUT.json`` compares the routes of the JSON cells (step a10) instead: ``main()`` over the same CSV in a
+fresh child process per run (one warm-up, then the median of 5), on this tree with the device route
+(csrc/kwrows.hip), on this tree with ``KW_ROWS_DEVICE=0`` (the lexsort + libkwrows on the host) and, with
+``--parent-tree DIR`` (a built checkout of the parent commit), on that tree.  Every configuration must write the
+same bytes.  OUT.json gets the three medians, the device route's ``kw_rows_last_ms`` split summed over the
+chunks (order, expand, render) and the wall time either route spent building the cells.
 """
 import argparse
 import contextlib
@@ -74,14 +81,128 @@ def phases(args, csv_path, processed):
     return {k: round(v, 3) for k, v in t.items()}
 
 
+ROWS_CHILD = r'''
+import contextlib, hashlib, io, json, os, sys, tempfile, time
+tree, info_dir, csv_path, chunksize = sys.argv[1:5]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import match_keywords as mk
+span = {'device_s': 0.0, 'host_s': 0.0, 'device_calls': 0, 'host_calls': 0, 'order': 0.0, 'expand': 0.0, 'render': 0.0}
+host = mk.assemble_json_raw
+def timed_host(ckb, hits, dates):
+    t = time.perf_counter()
+    out = host(ckb, hits, dates)
+    span['host_s'] += time.perf_counter() - t
+    span['host_calls'] += 1
+    return out
+mk.assemble_json_raw = timed_host
+device = getattr(mk, 'assemble_json_device', None)      # (the parent tree has none)
+if device is not None:
+    def timed_device(matcher, dates):
+        t = time.perf_counter()
+        out = device(matcher, dates)
+        span['device_s'] += time.perf_counter() - t
+        span['device_calls'] += 1
+        for k, v in matcher.rows_handle().last_ms().items():
+            if k in span:
+                span[k] += v
+        return out
+    mk.assemble_json_device = timed_device
+work = tempfile.mkdtemp(prefix='e2e_rows_')
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()):
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0
+h = hashlib.sha256()
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+import shutil
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
+def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs):
+    """main() in a fresh child per run on ``tree``: one warm-up, then ``runs`` timed runs."""
+    import statistics
+    import subprocess
+    env = dict(os.environ)
+    env.pop('KW_ROWS_DEVICE', None)
+    env.update(env_extra)
+    got = []
+    for _ in range(runs + 1):
+        p = subprocess.run([sys.executable, '-c', ROWS_CHILD, tree, info_dir, csv_path, str(chunksize)], env=env,
+                           cwd=tree, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            raise RuntimeError(f"child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith('E2E_ROWS ')][-1]
+        got.append(json.loads(line[len('E2E_ROWS '):]))
+    timed = got[1:]
+    assert len({r['sha256'] for r in got}) == 1, 'runs of one configuration wrote different bytes'
+    v = [r['seconds'] for r in timed]
+    mid = sorted(timed, key=lambda r: r['seconds'])[len(timed) // 2]      # the median run's spans
+    return {'env': env_extra, 'sha256': mid['sha256'], 'runs': v, 'median_s': statistics.median(v), 'min_s': min(v),
+            'max_s': max(v), 'cells': mid['span']}
+
+
+def rows_ab(args):
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=0)
+    csv_path = os.path.join(work, 'articles.csv')
+    synth.to_dataframe(corpus).to_csv(csv_path, index=False)
+    del corpus
+    res = {'docs': args.docs, 'chunksize': args.chunksize, 'csv_bytes': os.path.getsize(csv_path),
+           'runs_per_config': args.runs,
+           'timed': 'match_keywords.main() wall time in a fresh child per run; 1 warm-up + the median of the runs; '
+                    'cells: the median run\'s wall time inside the route that built the JSON cells (host: the '
+                    'lexsort + kwrows_assemble_mt; device: kw_rows_run + kw_rows_copy) and the device times (ms) '
+                    'of kw_rows_last_ms summed over the chunks'}
+    try:
+        res['device'] = rows_config(REPO, {'KW_ROWS_DEVICE': '1'}, info_dir, csv_path, args.chunksize, args.runs)
+        res['host'] = rows_config(REPO, {'KW_ROWS_DEVICE': '0'}, info_dir, csv_path, args.chunksize, args.runs)
+        if args.parent_tree:
+            res['parent'] = rows_config(os.path.abspath(args.parent_tree), {}, info_dir, csv_path, args.chunksize,
+                                        args.runs)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    assert res['device']['cells']['device_calls'] > 0 and res['device']['cells']['host_calls'] == 0
+    assert res['host']['cells']['device_calls'] == 0 and res['host']['cells']['host_calls'] > 0
+    res['same_bytes'] = len({res[k]['sha256'] for k in ('device', 'host', 'parent') if k in res}) == 1
+    res['device_not_slower'] = res['device']['median_s'] <= res['host']['median_s']
+    with open(args.rows_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['same_bytes'], 'the configurations wrote different bytes'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--rows-ab', metavar='OUT.json', help='compare the JSON cells\' routes (see the module doc)')
+    ap.add_argument('--parent-tree', help='--rows-ab: a built checkout of the parent commit')
+    ap.add_argument('--runs', type=int, default=5, help='--rows-ab: timed runs per configuration')
     ap.add_argument('--docs', type=int, default=200000)
     ap.add_argument('--chunksize', type=int, default=20000)
     ap.add_argument('--profile', action='store_true', help='cProfile main() (top functions by cumulative time)')
     args = ap.parse_args()
     os.environ.setdefault('TZ', 'UTC')
     time.tzset()
+    if args.rows_ab:
+        args.rows_ab = os.path.abspath(args.rows_ab)
+        return rows_ab(args)
     import bench
     from advanced_scrapper_amd import ingest, match_keywords as mk, synth
     from advanced_scrapper_amd.kb import compile_kb
