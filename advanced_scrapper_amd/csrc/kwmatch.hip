@@ -29,6 +29,19 @@ using namespace kw;
 #define RX_SPLIT_MAX_PAT 16384
 #endif
 
+// A regex name none of whose literal windows keys an anchor takes its rarest one as a new anchor (an RXM use, so
+// its fields are not searched) when the background sample holds that 4-gram, outside the name's own occurrences,
+// at most RXM_FALLBACK_MAX times per 4 MiB (0: never, every such name is searched) and at most
+// RXM_FALLBACK_PER_NAME times per occurrence of the name (build_fast).  The S&P KB's left-over names have 0-7
+// such occurrences, "DXC.technology" 1406 (0.77M more filter candidates a step); a 52k-name KB's mostly have
+// windows far commoner than the name, which would cost candidates for a handful of searches: DESIGN.md §6 round 8.
+#ifndef RXM_FALLBACK_MAX
+#define RXM_FALLBACK_MAX 16
+#endif
+#ifndef RXM_FALLBACK_PER_NAME
+#define RXM_FALLBACK_PER_NAME 4
+#endif
+
 // Scratch sizes of one launch configuration (every field only grows over a handle's life).
 struct ScratchCaps {
     int nk = 0, nr = 0, ng = 0;            // epilogue, resolve and generic waves (task waves = nk)
@@ -195,6 +208,12 @@ uint32_t dmax_h(uint32_t m)
 struct QStats {
     std::unordered_map<uint32_t, uint32_t> c4;
     bool have = false;
+    int64_t len = 0;                 // bytes of the sample
+    uint32_t raw(const uint8_t *p) const   // occurrences in the sample
+    {
+        auto it = c4.find((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+        return it == c4.end() ? 0u : it->second;
+    }
     uint32_t count(const uint8_t *p) const
     {
         const uint32_t k = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
@@ -512,33 +531,93 @@ int build_fast(FastBuild &B, const QStats &Q, int n_pat, const uint8_t *pat_byte
         }
     }
     // ---- RXM uses: anchored at a window of literals whose first four bytes already key another anchor (the
-    // filters pass nothing new; the probe checks one more use there), the rarest such window
+    // filters pass nothing new; the probe checks one more use there), the rarest such window.  A name left
+    // without one (its raw name's anchor holds the '.', so no literal window of its program is an anchor: "D.R.
+    // Horton", the "First M. Last" names) then takes its rarest window of literals as a new anchor, so that its
+    // field searches (one wave each) go away, when a background sample prices the window: the filters pass that
+    // 4-gram's occurrences as new candidates, and those outside the name itself (the window's count in the
+    // sample less the name's, which is the smallest count of the raw name's 4-grams) buy nothing.  They may
+    // number at most RXM_FALLBACK_MAX per 4 MiB and RXM_FALLBACK_PER_NAME per occurrence of the name.  Such a
+    // window counts as shared for the names after it.  A name without a window, or with windows too common for
+    // it (or any left-over name of a matcher built without a sample), keeps the regex tasks' search.
     {
+        uint64_t fb_max = RXM_FALLBACK_MAX, fb_per = RXM_FALLBACK_PER_NAME;
+        if (const char *e = kw_env("KW_RXM_FALLBACK_MAX")) fb_max = (uint64_t)std::max(0ll, atoll(e));   // (0: off)
+        if (const char *e = kw_env("KW_RXM_FALLBACK_PER_NAME")) fb_per = (uint64_t)std::max(0ll, atoll(e));
+        const bool fallback = Q.have && fb_max > 0;
         std::unordered_map<uint32_t, int> pre4;
         for (const auto &st : astr)
             if (st.size() >= 4) pre4[*(const uint32_t *)st.data()] = 1;
-        for (const auto &t : rxm_todo) {
-            size_t best = SIZE_MAX;
-            uint32_t bc = 0xFFFFFFFFu;
-            for (size_t w = 0; w + 4 <= t.L && w <= 255; ++w) {
-                if ((t.wild >> w) & 0xFull) continue;
-                if (!pre4.count(*(const uint32_t *)(t.rs.data() + w))) continue;
-                const uint32_t c = Q.count((const uint8_t *)t.rs.data() + w);
-                if (c < bc) { bc = c; best = w; }
+        std::vector<const RxmTodo *> left;
+        uint32_t n_shared = 0, n_fallback = 0, n_refused = 0, n_none = 0;
+        const bool dbg = kw_env("KW_DEBUG_RXM") != nullptr;   // (developer aid) how the names got their windows
+        for (int pass = 0; pass < 2; ++pass) {
+            const size_t n_todo = pass == 0 ? rxm_todo.size() : left.size();
+            for (size_t q = 0; q < n_todo; ++q) {
+                const RxmTodo &t = pass == 0 ? rxm_todo[q] : *left[q];
+                const int nlen = (int)(pat_off[t.pat + 1] - pat_off[t.pat]);
+                const uint8_t *name = pat_bytes + pat_off[t.pat];
+                uint64_t occ = 0;   // the name's occurrences in the sample, at most
+                if (pass == 1 && fallback && nlen >= 4) {
+                    occ = ~0ull;
+                    for (int w = 0; w + 4 <= nlen; ++w) occ = std::min<uint64_t>(occ, Q.raw(name + w));
+                }
+                size_t best = SIZE_MAX, fbest = SIZE_MAX;
+                uint32_t bc = 0xFFFFFFFFu, fc = 0xFFFFFFFFu;
+                uint64_t fbg = 0;
+                bool literal = false;
+                for (size_t w = 0; w + 4 <= t.L && w <= 255; ++w) {
+                    if ((t.wild >> w) & 0xFull) continue;
+                    const uint8_t *p = (const uint8_t *)t.rs.data() + w;
+                    const uint32_t c = Q.count(p);
+                    if (pre4.count(*(const uint32_t *)p)) {
+                        if (c < bc) { bc = c; best = w; }
+                        continue;
+                    }
+                    literal = true;
+                    if (pass == 0 || !fallback) continue;
+                    // the window's background occurrences: as a rate (per sample byte against fb_max per 4 MiB),
+                    // and against the name's own
+                    const uint64_t raw = Q.raw(p), bg = raw > occ ? raw - occ : 0;
+                    if ((bg << 22) > fb_max * (uint64_t)Q.len || bg > fb_per * occ) continue;
+                    if (c < fc) { fc = c; fbest = w; fbg = bg; }
+                }
+                if (best == SIZE_MAX && pass == 0) { left.push_back(&t); continue; }
+                const bool shared = best != SIZE_MAX;
+                if (!shared) best = fbest;
+                if (best == SIZE_MAX) {   // (its positions come from the regex tasks' search)
+                    ++(literal ? n_refused : n_none);
+                    if (dbg)
+                        fprintf(stderr, "kw rxm: pattern %u \"%.*s\" keeps its search (%s; the name %llu times in the "
+                                "sample)\n", t.pat, nlen, (const char *)name,
+                                !literal ? "no window of four literals"
+                                         : fallback ? "every window too common" : "no fallback windows",
+                                (unsigned long long)occ);
+                    continue;
+                }
+                ++(shared ? n_shared : n_fallback);
+                if (dbg && !shared)
+                    fprintf(stderr, "kw rxm: pattern %u \"%.*s\" fallback window \"%.4s\" at %zu: background %llu, the "
+                            "name %llu times in the sample\n", t.pat, nlen, (const char *)name, t.rs.data() + best, best,
+                            (unsigned long long)fbg, (unsigned long long)occ);
+                size_t al = 4;
+                while (al < 8 && best + al < t.L && !((t.wild >> (best + al)) & 1ull)) ++al;
+                Use u;
+                u.pat = t.pat;
+                u.i0 = FU_RXM | ((uint32_t)best << 8);
+                u.i1 = t.L;
+                u.rxs = (uint32_t)B.rx_bytes.size();
+                u.wild = t.wild;
+                B.rx_bytes.insert(B.rx_bytes.end(), t.rs.begin(), t.rs.end());
+                B.rxl[t.pat] = t.L;
+                add(t.rs.substr(best, al), u);
+                pre4[*(const uint32_t *)(t.rs.data() + best)] = 1;
             }
-            if (best == SIZE_MAX) continue;   // (its positions come from the regex tasks' search)
-            size_t al = 4;
-            while (al < 8 && best + al < t.L && !((t.wild >> (best + al)) & 1ull)) ++al;
-            Use u;
-            u.pat = t.pat;
-            u.i0 = FU_RXM | ((uint32_t)best << 8);
-            u.i1 = t.L;
-            u.rxs = (uint32_t)B.rx_bytes.size();
-            u.wild = t.wild;
-            B.rx_bytes.insert(B.rx_bytes.end(), t.rs.begin(), t.rs.end());
-            B.rxl[t.pat] = t.L;
-            add(t.rs.substr(best, al), u);
         }
+        if (dbg)
+            fprintf(stderr, "kw rxm: %zu names; window shared %u, fallback %u (background at most %llu per 4 MiB and "
+                    "%llu per occurrence of the name), refused %u, no window %u\n", rxm_todo.size(), n_shared, n_fallback,
+                    (unsigned long long)fb_max, (unsigned long long)fb_per, n_refused, n_none);
     }
     // ---- anchors, uses
     const uint32_t na = (uint32_t)astr.size();
@@ -1043,6 +1122,7 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
     QStats Q;
     if (bg && bg_len >= 4) {
         Q.have = true;
+        Q.len = bg_len;
         Q.c4.reserve((size_t)std::min<int64_t>(bg_len, 1 << 22));
         for (int64_t i = 0; i + 4 <= bg_len; ++i) {
             const uint32_t k = (uint32_t)bg[i] | ((uint32_t)bg[i + 1] << 8) | ((uint32_t)bg[i + 2] << 16) |
