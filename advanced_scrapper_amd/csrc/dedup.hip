@@ -502,9 +502,6 @@ __device__ __forceinline__ int64_t transform_row(const Src &src, int64_t b, int6
 }
 
 constexpr int STAGE_BYTES = 8192;   // per-wave LDS copy of the wave's 64 rows
-#ifndef DD_STEP8
-#define DD_STEP8 1                  // transform_row_lds's scan: 8 bytes a step (0: 4)
-#endif
 
 // A wave's 16-byte chunks [0, nch) of src into its LDS stage by LDS-DMA (global_load_lds_dwordx4: 64 chunks
 // an instruction, every instruction issued before the one wait; no VGPRs).  A loop of load-then-store waited
@@ -560,7 +557,6 @@ __device__ __forceinline__ int64_t transform_row_lds(const LdsRow &R, int L, int
         if ((w4 & 0xFFu) == 0x3Au && !(L >= 7 && (w4 & 0xFFFFFFu) == 0x30383Au)) { scheme_http = true; excl = 0x80u; }
         if (L >= 6 && (w4 & 0xFFFFu) == 0x3A73u && !(L >= 8 && (w4 >> 8) == 0x30383Au)) excl = 0x8000u;
     }
-#if DD_STEP8
     // 8 bytes a step (x = bytes [t, t + 4), x2 = [t + 4, t + 8), y = [t + 8, t + 12)): the loop's control, its
     // branches' tests and the dword reads (two a step, read a step ahead) are paid once per 8 bytes.  The scan
     // stops at any "html" at q in [t, t + 8); the candidates are validated out of the loop (q >= 1, q + 4 <= L,
@@ -640,63 +636,6 @@ __device__ __forceinline__ int64_t transform_row_lds(const LdsRow &R, int L, int
         t += 8;
         k += 2;
     }
-#else
-    // the scan stops at any "html" at q in [t, t + 4); the candidates are validated out of the loop (q >= 1,
-    // q + 4 <= L, no '\n' before q), and a step without a valid one resumes the scan
-    // (d1, d2: the aligned dwords k - 1, k under y; dword k + 1 is read a step ahead)
-    uint32_t d1 = R.dw(1), d2 = R.dw(2);
-    uint32_t x = __builtin_amdgcn_alignbyte(d1, R.dw(0), R.s), xp = 0, y = 0;
-    int t = 0, k = 2;
-    for (;;) {
-        for (; t < L; t += 4, ++k) {
-            const uint32_t dn = R.dw(k + 1);
-            y = __builtin_amdgcn_alignbyte(d2, d1, R.s);
-            d1 = d2;
-            d2 = dn;
-            uint32_t cm = eq_bytes(x, 0x3A3A3A3Au);
-            if (t == 4) cm &= ~excl;
-            if (cm) {
-                const uint32_t cm1 = cm & (cm - 1u);
-                const int c0 = t + (__builtin_ctz(cm) >> 3);
-                const int c1 = cm1 ? t + (__builtin_ctz(cm1) >> 3) : NONE;
-                ec2 = ec == NONE ? c1 : (ec2 == NONE ? c0 : ec2);
-                ec = ec == NONE ? c0 : ec;
-            }
-            uint32_t pm = eq_bytes(x | 0x02020202u, 0x27272727u);
-            while (pm) {
-                const int p = t + (__builtin_ctz(pm) >> 3);
-                pm &= pm - 1u;
-                if (p >= 5 && p < kf && R.ld32(p - 5) == NEWS4 && (R.ld32(p - 1) & 0xFFu) == 0x2Fu) kf = p;
-            }
-            if ((x == HTML4) | (__builtin_amdgcn_alignbyte(y, x, 1) == HTML4) |
-                (__builtin_amdgcn_alignbyte(y, x, 2) == HTML4) | (__builtin_amdgcn_alignbyte(y, x, 3) == HTML4))
-                break;
-            xp = x;
-            x = y;
-        }
-        if (t >= L) break;   // no cut
-        uint32_t hm = (x == HTML4 ? 0x80u : 0u) | (__builtin_amdgcn_alignbyte(y, x, 1) == HTML4 ? 0x8000u : 0u) |
-                      (__builtin_amdgcn_alignbyte(y, x, 2) == HTML4 ? 0x800000u : 0u) |
-                      (__builtin_amdgcn_alignbyte(y, x, 3) == HTML4 ? 0x80000000u : 0u);
-        const int r3 = L - t - 3;   // candidates q = t + k with q + 4 <= L
-        hm &= r3 >= 4 ? 0x80808080u : (r3 <= 0 ? 0u : 0x80808080u & ((1u << (8 * r3)) - 1u));
-        hm &= ~eq_bytes(__builtin_amdgcn_alignbyte(x, xp, 3), 0x0A0A0A0Au);
-        if (t == 0) hm &= ~0x80u;
-        if (hm) {
-            const int q = t + (__builtin_ctz(hm) >> 3);
-            int sp = q - 1;
-            if ((R.ld32(sp) & 0xFFu) >= 0x80u) {
-                while (sp > 0 && (R.ld32(sp) & 0xC0u) == 0x80u && q - sp < 4) --sp;
-            }
-            j = sp;
-            break;
-        }
-        xp = x;   // no valid candidate in this step: on with the next
-        x = y;
-        t += 4;
-        ++k;
-    }
-#endif
     if (j < 0) {
         code[i] = KW_URL_NO_HTML;
         S.len3[i] = 0;

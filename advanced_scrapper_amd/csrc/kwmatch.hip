@@ -1578,7 +1578,7 @@ static int launch_scan(kw_handle *h)
         static const bool flat = !kw_env("KW_EPI_FLAT") || atoi(kw_env("KW_EPI_FLAT")) != 0;
         // its transcoded documents in the batches too when no name is PI_TXUNSAFE (KW_TEST_EPI_TXB=0, read per
         // scan: one at a time, as with such names)
-        const bool txb = EF_TX_FLAT && (!kw_env("KW_TEST_EPI_TXB") || atoi(kw_env("KW_TEST_EPI_TXB")) != 0);
+        const bool txb = !kw_env("KW_TEST_EPI_TXB") || atoi(kw_env("KW_TEST_EPI_TXB")) != 0;
         if (flat && txb && h->FT.n_txu == 0)
             hipLaunchKernelGGL(kw_epi_flat_kernel<true>, dim3(neb), dim3(EK_BLOCK), 0, st, h->FT, h->arena,
                                h->doc_off, n_docs, h->FS, h->S);
@@ -1849,12 +1849,6 @@ static int finish(kw_handle *h)
         {   // the transcoded view: documents it took / left to the resolve kernel; the next scan's capacity
             const unsigned long long used = small[48];
             if (used > h->caps.tx_cap && !kw_env("KW_TEST_TX_CAP")) h->tx_need = used + used / 8;
-        }
-        if (kw_env("KW_DUMP_TIMING")) {   // FK_TIMING builds: resolve-kernel cycles summed over waves
-            fprintf(stderr, "KW_TIMING resolve decode %llu edge %llu items %llu short %llu regex %llu all %llu\n", fst[21],
-                    fst[22], fst[23], fst[24], fst[25], fst[26]);
-            fprintf(stderr, "KW_TASKS verify %llu edge %llu short %llu regex %llu edge_docs %llu\n", fst[27], fst[28], fst[29],
-                    fst[30], fst[31]);
         }
         h->n_hits = (int64_t)tot;
         h->fetched = true;

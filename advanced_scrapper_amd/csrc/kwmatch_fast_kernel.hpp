@@ -13,22 +13,10 @@
 #include "kwmatch_fast.hpp"
 #include "kwmatch_kernels.hpp"
 
-#ifndef EPI_SHORT_PREF   // the group epilogue's signature test of short fields before their tasks
-#define EPI_SHORT_PREF 1
-#endif
-#ifndef SHORT_TB   // short kernel: every name on lanes (one-byte code points, 256-entry match vectors)
-#define SHORT_TB 1
-#endif
-#ifndef SHORT_BG   // short kernel: the bigram-signature filter after the character signature
-#define SHORT_BG 1
-#endif
 #ifndef VK_U   // verify jobs: name match-vector loads in flight
 #define VK_U 8
 #endif
 // task kernels' minimum waves per SIMD (register budget: 4 -> 128 VGPRs, 5 -> 102, 6 -> 84, 8 -> 64)
-#ifndef VK_PRETEST
-#define VK_PRETEST 1   // the verify kernel's band-test pretest with a queue of the tasks it cannot rule out
-#endif
 #ifndef VK_MINW
 #define VK_MINW 4
 #endif
@@ -38,31 +26,7 @@
 #ifndef RX_MINW
 #define RX_MINW 4   // <= 128 VGPRs (the prefetched task records stay in LDS)
 #endif
-#ifndef SHORT_COUNT
-#define SHORT_COUNT 0
-#endif
 // waves per SIMD the resolve kernel is compiled for (register budget)
-#ifndef FK_TIMING   // developer aid: per-phase cycle counters of the resolve kernel (KW_DUMP_TIMING)
-#define FK_TIMING 0
-#endif
-#define FK_T0(v) const unsigned long long v = FK_TIMING ? __builtin_amdgcn_s_memtime() : 0ull
-#define FK_TACC(acc, v) do { if (FK_TIMING) acc += __builtin_amdgcn_s_memtime() - (v); } while (0)
-#ifndef EK_TIMING   // developer aid: per-phase cycle counters of the epilogue kernel (KW_DUMP_TIMING, stats 21..31)
-#define EK_TIMING 0
-#endif
-#define EK_T0(v) const unsigned long long v = EK_TIMING ? __builtin_amdgcn_s_memtime() : 0ull
-#define EK_TACC(acc, v) do { if (EK_TIMING) (acc) += __builtin_amdgcn_s_memtime() - (v); } while (0)
-
-
-
-#ifndef FK_EPI_EDGE   // developer aid: 3 = edge windows in the epilogue; 1 = code present, never run; 0 = absent
-#define FK_EPI_EDGE 3
-#endif
-
-#ifndef FK_SHORT_LANES   // 1: lane-parallel short-field windows in the short task kernel; 0: wave-serial
-#define FK_SHORT_LANES 1
-#endif
-
 #ifndef RK_OCC
 #define RK_OCC 4
 #endif
@@ -386,16 +350,8 @@ __device__ bool fk_short_decide(uint32_t fc, uint32_t n, uint32_t nmr, uint32_t 
 // name needs an exact occurrence, which the FULL use finds).  Lanes 0..19 take
 // (side, L = m-1): hash the window, look it up among the one-deletion variants,
 // verify exactly and append an EDGE item.  Returns the number of items added.
-#ifndef RK_EDGE_NOINLINE   // 1: fk_edge_items as a called function (its registers stay out of the resolve loop)
-#define RK_EDGE_NOINLINE 0
-#endif
 template <uint32_t ICAP>
-#if RK_EDGE_NOINLINE
-__device__ __attribute__((noinline))
-#else
-__device__
-#endif
-uint32_t fk_edge_items(const FastTables &FT, const FieldCtx &F, uint64_t *items, uint32_t *icnt_f,
+__device__ uint32_t fk_edge_items(const FastTables &FT, const FieldCtx &F, uint64_t *items, uint32_t *icnt_f,
                                   uint32_t *dflag)
 {
     const int lane = lane_id();
@@ -519,9 +475,6 @@ __device__ uint32_t fk_rx_fixed_positions(const FastTables &FT, const DevScratch
     wave_sync();
     const int64_t n = F.n;
     if (n < (int64_t)L) return 0;
-#if defined(RX_TIMING_SKIP) && RX_TIMING_SKIP == 4
-    return 0;
-#endif
     // the program's literal head: each of its first min(4, L) positions whose matching bytes are exactly one
     // ASCII byte c (hv byte i = c, hm byte i = 0xFF).  With two or more such bytes a lane tests its 32 starts'
     // 4-byte windows against the head (SWAR, no per-byte lookup chain) and confirms only the candidates
@@ -580,11 +533,7 @@ __device__ uint32_t fk_rx_fixed_positions(const FastTables &FT, const DevScratch
         }
         const int64_t s_lo = r0 + (int64_t)lane * 32;
         uint32_t mask = 0;
-#if defined(RX_TIMING_SKIP) && RX_TIMING_SKIP == 3
-        if (false) {
-#else
         if (s_lo < nstarts) {
-#endif
             const int64_t s_hi = s_lo + 32 < nstarts ? s_lo + 32 : nstarts;
             const int c_cnt = (int)(s_hi + L - 1 - s_lo);
             uint64_t D = 0;
@@ -864,7 +813,7 @@ __device__ int fk_resolve_field(const FastTables &FT, const DevTables &T, const 
                                  uint64_t *items_lds, uint32_t *icnt_f, uint32_t *dflag, uint32_t *cps,
                                  uint32_t *blkcnt, uint64_t *rxtab, RxQueue &RQ, bool maybe_nonascii, bool edge,
                                  unsigned long long &nver,
-                                 unsigned long long &nwin, unsigned long long &nedge, unsigned long long *tacc)
+                                 unsigned long long &nwin, unsigned long long &nedge)
 {
     const int lane = lane_id();
     // ---- field facts (code points, ASCII) on demand
@@ -872,15 +821,12 @@ __device__ int fk_resolve_field(const FastTables &FT, const DevTables &T, const 
     // the scan's non-ASCII flags are exact per field
     F.ascii = !maybe_nonascii;
     F.n = (uint32_t)flen;
-    FK_T0(tr0);
     if (!F.ascii) {
         if (flen > (int64_t)FK_CP_CAP) return 1;
         F.n = decode_field_fast(F.arena, F.fb, F.fe, cps, blkcnt, FK_CP_CAP);
         F.cps = cps;
         F.blkcnt = blkcnt;
     }
-    FK_TACC(tacc[0], tr0);
-    FK_T0(tr1);
     const bool is_short = F.n <= (uint32_t)MAXM;
     // ---- one-deletion edge windows of the 11..20-code-point names (prefiltered by the scan)
     if (edge && F.n >= EDGE_MIN_M + 1) {
@@ -893,8 +839,6 @@ __device__ int fk_resolve_field(const FastTables &FT, const DevTables &T, const 
         }
     }
     wave_sync();
-    FK_TACC(tacc[1], tr1);
-    FK_T0(tr2);
     const uint32_t N = __builtin_amdgcn_readfirstlane(*icnt_f);
     if (N == 0 && !is_short) return 0;
     if (N > (uint32_t)WAVE) {
@@ -1006,11 +950,8 @@ __device__ int fk_resolve_field(const FastTables &FT, const DevTables &T, const 
             fk_regex_enqueue(GS, F, (uint32_t)__shfl((int)pat, l, WAVE), RQ);
         }
     }
-    FK_TACC(tacc[2], tr2);
     // ---- short field: the field is the needle, the longer names are the haystacks
-    FK_T0(tr3);
     if (is_short) fk_short_field(FT, FT.pat_cps, GS, F, O, nver, nwin, [&](uint32_t P) { fk_regex_enqueue(GS, F, P, RQ); });
-    FK_TACC(tacc[3], tr3);
     return 0;
 }
 
@@ -1116,7 +1057,7 @@ __device__ __forceinline__ void fk_epi_edge(const FastTables &FT, const FastScra
     const int lane = lane_id();
     // ---- one-deletion edge windows of the 11..20-code-point names, both fields at once:
     // lane 20 f + 10 side + (L - 10) hashes the first (side 0) or last (side 1) L bytes of field f
-    if ((FK_EPI_EDGE & 1) && (flags & (DH_EDGE0 | DH_EDGE1)) && (FK_EPI_EDGE & 2)) {
+    if (flags & (DH_EDGE0 | DH_EDGE1)) {
         const int f = lane >= 20 ? 1 : 0;
         const int sidx = lane - 20 * f;
         const uint32_t L = (EDGE_MIN_M - 1) + (uint32_t)(sidx % 10);
@@ -1191,13 +1132,10 @@ __device__ __forceinline__ void fk_epi_edge(const FastTables &FT, const FastScra
 template <uint32_t F1OFF = FK_ITEMS0>
 __device__ bool fk_scan_epilogue(const FastTables &FT, const FastScratch &S, const DevScratch &GS, const FastDoc &D,
                                  uint64_t *items, uint32_t n0, uint32_t n1, uint32_t flags, int64_t wave, OutCtx &O,
-                                 TaskCounts &TC, unsigned long long *ekt = nullptr)
+                                 TaskCounts &TC)
 {
     constexpr uint32_t f1off = F1OFF;
     const int lane = lane_id();
-    unsigned long long ekt_dummy[8];
-    if (!ekt) ekt = ekt_dummy;
-    EK_T0(te0);
     // the fields' items sorted first: the deferral test precedes every emission
     if (n0 > (uint32_t)WAVE) {
         wave_sort_lds(items, n0);
@@ -1209,7 +1147,6 @@ __device__ bool fk_scan_epilogue(const FastTables &FT, const FastScratch &S, con
     }
     uint4 *vq = S.vq + (size_t)wave * S.vcap;
     uint4 *sq = S.sq + (size_t)wave * S.scap, *xq = S.xq + (size_t)wave * S.xcap;
-    EK_TACC(ekt[0], te0);
     for (uint32_t f = 0; f < 2; ++f) {
         FieldCtx F;
         F.arena = D.arena;
@@ -1226,7 +1163,6 @@ __device__ bool fk_scan_epilogue(const FastTables &FT, const FastScratch &S, con
         // (RXM items are exact regex matches in an ASCII field only; a transcoded field's regex names are searched)
         const bool rxm_ok = !(flags & (f ? DH_NA1 : DH_NA0));
         if (F.n <= (uint32_t)MAXM && fk_short_has_cand(FT, F)) {
-            if (SHORT_COUNT && lane == 0) atomicAdd(&S.stats[27 + (flags & (DH_NA0 | DH_NA1) ? 1 : 0)], 1ull);
             task_push(sq, S.scap, TC.s, make_uint4(D.doc, f, 0u, 0u));
         }
         if (N == 0) continue;
@@ -1239,12 +1175,9 @@ __device__ bool fk_scan_epilogue(const FastTables &FT, const FastScratch &S, con
                 if (be == bs) be = bs + WAVE;   // (cannot happen: fk_long_run deferred such documents)
             }
             const uint32_t NB = be - bs;
-            EK_T0(te1);
             uint64_t it = (lane < (int)NB) ? its[bs + lane] : ~0ull;
             it = wave_sort_few(it, NB, its + bs);
             bs = be;
-            EK_TACC(ekt[1], te1);
-            EK_T0(te2);
             const bool valid = lane < (int)NB;
             const uint32_t pat = valid ? it_pat(it) : 0xFFFFFu;
             const uint32_t kind = it_kind(it);
@@ -1271,8 +1204,6 @@ __device__ bool fk_scan_epilogue(const FastTables &FT, const FastScratch &S, con
             // the short path owns fuzzy names at least as long as the field
             const bool live = valid && !(fuzzy && m >= F.n);
             const uint64_t fullm = __ballot(live && kind == FU_FULL);
-            EK_TACC(ekt[2], te2);
-            EK_T0(te3);
             const bool decided = (fullm & gmask) != 0;
             // pieces of undecided fuzzy names -> verify tasks (one per alignment base)
             const bool vpiece = live && fuzzy && !decided && kind == FU_PIECE;
@@ -1334,12 +1265,9 @@ __device__ bool fk_scan_epilogue(const FastTables &FT, const FastScratch &S, con
                 if (xrx && xi < S.xcap) xq[xi] = make_uint4(D.doc, (pat << 1) | f, 0u, 0u);
                 TC.x += (uint32_t)__popcll(xm);
             }
-            EK_TACC(ekt[3], te3);
         }
     }
-    EK_T0(te4);
     fk_epi_edge(FT, S, GS, D, flags, O, TC, xq);
-    EK_TACC(ekt[4], te4);
     return true;
 }
 
@@ -1373,12 +1301,8 @@ __device__ __forceinline__ void fk_regex_pre(const FastTables &FT, const DevTabl
     ++nrx;
     nrx_bt += r < 0;
     nrx_rounds += r >= 0 ? (F.n + 2047) / 2048 : 0;
-#if defined(RX_TIMING_SKIP) && RX_TIMING_SKIP == 5   // (timing variant: no backtracking engine in the kernel)
-    const uint32_t cnt = r >= 0 ? fk_rx_fixed_positions<true>(FT, GS, F, O, P, (uint32_t)r, prm, rxtab, txt) : 1u;
-#else
     const uint32_t cnt = r >= 0 ? fk_rx_fixed_positions<true>(FT, GS, F, O, P, (uint32_t)r, prm, rxtab, txt)
                                 : rx_positions(T, GS, F, O, P);
-#endif
     if (cnt == 0) emit_hits(O, GS, lane_id() == 0, F.doc, P, KW_NOPOS, F.field);
 }
 
@@ -1635,15 +1559,9 @@ __global__ __launch_bounds__(RK_BLOCK, VK_MINW) void kw_verify_kernel(FastTables
         uint32_t nwj = 0, pre = 0, cj = 0;
         if (lanewise) {
             ++nver;
-#if defined(VK_TIMING_SKIP)   // (timing variants only, results void: 1 no band test, 2 no band test and no jobs)
-            nwj = 0;
-            pre = VK_TIMING_SKIP == 1 && q + pl + 1 <= m ? 1u : 0u;
-            cj = VK_TIMING_SKIP == 1 ? nwj + pre + (q + m > n ? 1u : 0u) : 0u;
-#else
             nwj = lv_band(la, fb, n, NW, m, (int64_t)q - (int64_t)o, kfull(m), win, pmin);
             pre = q + pl + 1 <= m ? 1u : 0u;
             cj = nwj + pre + (q + m > n ? 1u : 0u);
-#endif
         }
         int J = 0;
         const int ex = wave_excl_scan((int)cj, &J);
@@ -1736,7 +1654,6 @@ __global__ __launch_bounds__(RK_BLOCK, VK_MINW) void kw_verify_kernel(FastTables
         emit_hits(O, GS, first && !rx, doc, P, KW_NOPOS, field);
         xq_push(X, rx, doc, P, field);
     };
-#if VK_PRETEST
     // the tasks 64 at a time through the pretest; the ones it cannot rule out queue up and run the full test (and
     // their window jobs) 64 at a time, so those rounds run on full waves (~90 % of the tasks fail the band test)
     uint32_t qh = 0, qn = 0;
@@ -1785,9 +1702,6 @@ __global__ __launch_bounds__(RK_BLOCK, VK_MINW) void kw_verify_kernel(FastTables
         const uint32_t kq = vsel[(qh + (uint32_t)lane) & (2u * WAVE - 1u)];
         run(kq, (uint32_t)lane < qn);
     }
-#else
-    for (uint32_t k0 = sub * WAVE; k0 < nv; k0 += (uint32_t)G * WAVE) run(k0 + (uint32_t)lane, k0 + (uint32_t)lane < nv);
-#endif
     task_stats(S, wave_sum64(nver) + nver_w, wave_sum64(nwin) + nwin_w, 0, 0, 0, 0);
 }
 
@@ -1796,8 +1710,8 @@ __global__ __launch_bounds__(RK_BLOCK, VK_MINW) void kw_verify_kernel(FastTables
 // (the field is the needle).  Candidates come from the signature filter as in fk_short_field;
 // then every window of every candidate (full windows of the name, its prefixes, its suffixes and,
 // when m == n, the swapped run) is a job on its own lane: a bit-parallel LCS whose match vectors
-// come from the field's 128-entry table in LDS (pm), the candidate names staged in LDS (names,
-// SL_NAME bytes each).  Names with non-ASCII code points take the wave-serial fk_short_decide.
+// come from the field's 256-entry table in LDS (pm), the candidate names staged in LDS (names,
+// SL_NAME bytes each, one byte per code point).  Names longer than SL_NAME take the wave-serial fk_short_decide.
 constexpr int SL_NAME = 64;
 
 __device__ __forceinline__ void fk_short_run(const FastTables &FT, const DevScratch &GS, const FieldCtx &F, OutCtx &O,
@@ -1815,8 +1729,8 @@ __device__ __forceinline__ void fk_short_run(const FastTables &FT, const DevScra
     const uint32_t m = pi_m(pi);
     // every name on lanes: its code points as one byte each (ASCII, or the transcoded view's markers), the
     // field's match vectors cover all 256 byte values
-    const bool lanes_ok = has && (SHORT_TB || (pi & PI_ASCII) != 0) && m <= (uint32_t)SL_NAME;
-    const int64_t boff = lanes_ok ? (SHORT_TB ? (int64_t)FT.pat_cp_off[P] : FT.pat_boff[P]) : 0;
+    const bool lanes_ok = has && m <= (uint32_t)SL_NAME;
+    const int64_t boff = lanes_ok ? (int64_t)FT.pat_cp_off[P] : 0;
     nver += has ? 1u : 0u;
     // stage the names: 16 dwords per candidate
     for (uint32_t i0 = 0; i0 < nc * (SL_NAME / 4); i0 += WAVE) {
@@ -1827,7 +1741,7 @@ __device__ __forceinline__ void fk_short_run(const FastTables &FT, const DevScra
         const uint32_t bhi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)boff >> 32), k & 63, WAVE);
         const int32_t km = __shfl((int)m, k & 63, WAVE);
         if (idx < nc * (SL_NAME / 4) && 4 * w < (uint32_t)km)
-            ((uint32_t *)names)[idx] = ld_u32_unaligned(SHORT_TB ? FT.pat_tbytes : FT.pat_bytes, (int64_t)(((uint64_t)bhi << 32) | blo) + 4 * w);
+            ((uint32_t *)names)[idx] = ld_u32_unaligned(FT.pat_tbytes, (int64_t)(((uint64_t)bhi << 32) | blo) + 4 * w);
     }
     // jobs per candidate: m - n + 1 full windows, the prefixes, the suffixes, the swapped run (m == n)
     const uint32_t nj = lanes_ok ? (m - n + 3 + (m == n ? 1u : 0u)) : 0u;
@@ -1942,7 +1856,7 @@ __device__ void fk_short_lanes(const FastTables &FT, const DevScratch &GS, const
     uint64_t fb0 = 0, fb1 = 0;
     {
         const uint32_t nx = (uint32_t)__shfl((int)fc, (lane + 1) & (WAVE - 1), WAVE);
-        if (SHORT_BG && lane + 1 < (int)n) {
+        if (lane + 1 < (int)n) {
             const uint32_t h = fk_bg_bit(fc, nx);
             (h & 64u ? fb1 : fb0) = 1ull << (h & 63u);
         }
@@ -1967,7 +1881,7 @@ __device__ void fk_short_lanes(const FastTables &FT, const DevScratch &GS, const
                 FW[w] = x;
             }
 #pragma unroll
-            for (int q = 0; q < (SHORT_TB ? 4 : 2); ++q) pm[lane + 64 * q] = lv_match(FW, (uint32_t)lane + 64u * q, needle);
+            for (int q = 0; q < 4; ++q) pm[lane + 64 * q] = lv_match(FW, (uint32_t)lane + 64u * q, needle);
             have_pm = true;
             wave_sync();
         }
@@ -1985,7 +1899,7 @@ __device__ void fk_short_lanes(const FastTables &FT, const DevScratch &GS, const
         for (int u = 0; u < SIG_U; ++u) {
             const uint32_t idx = c00 + (uint32_t)(u * WAVE + lane);
             nsig[u] = idx < count ? FT.pat_sig[FT.f_first + idx] : ~0ull;
-            nbs[u] = (SHORT_BG && idx < count) ? ((const ulonglong2 *)FT.pat_bsig)[FT.f_first + idx] : make_ulonglong2(~0ull, ~0ull);
+            nbs[u] = idx < count ? ((const ulonglong2 *)FT.pat_bsig)[FT.f_first + idx] : make_ulonglong2(~0ull, ~0ull);
         }
 #pragma unroll
         for (int u = 0; u < SIG_U; ++u) {
@@ -2011,17 +1925,16 @@ __global__ __launch_bounds__(RK_BLOCK, SK_MINW) void kw_short_kernel(FastTables 
                                                             const int64_t *__restrict__ off, int n_regions, int G,
                                                             FastScratch S, DevScratch GS)
 {
-    const int lane = lane_id();
     const int wib = threadIdx.x / WAVE;
     const int64_t gw = (int64_t)blockIdx.x * RK_WAVES + wib;   // G waves per region
     const int64_t t = gw / G;
     const uint32_t sub = (uint32_t)(gw % G);
     if (t >= n_regions) return;
     (void)T;
-    __shared__ uint64_t pm_all[RK_WAVES * (SHORT_TB ? 256 : 128)];
+    __shared__ uint64_t pm_all[RK_WAVES * 256];
     __shared__ uint32_t names_all[RK_WAVES * WAVE * SL_NAME / 4];
     __shared__ uint32_t cand_all[RK_WAVES * WAVE];
-    uint64_t *pm = pm_all + wib * (SHORT_TB ? 256 : 128);
+    uint64_t *pm = pm_all + wib * 256;
     uint8_t *names = (uint8_t *)(names_all + wib * WAVE * SL_NAME / 4);
     uint32_t *cand = cand_all + wib * WAVE;
     OutCtx O = tout_region(S, t);
@@ -2034,17 +1947,7 @@ __global__ __launch_bounds__(RK_BLOCK, SK_MINW) void kw_short_kernel(FastTables 
         const uint4 tk = sq[k];
         fk_field_ctx(F, arena, S, (uint32_t)__builtin_amdgcn_readfirstlane((int)tk.x),
                      (uint32_t)__builtin_amdgcn_readfirstlane((int)tk.y));
-        if (FK_SHORT_LANES)
-        {
-            if (SHORT_COUNT && lane == 0) {   // developer aid: short tasks by length class (stats 21..24)
-                atomicAdd(&S.stats[21 + (F.n <= (uint32_t)SHORT_EXACT_MAX ? 0 : F.n < 40u ? 1 : 2)], 1ull);
-                atomicAdd(&S.stats[24], (unsigned long long)FT.f_count_ge[F.n]);
-            }
-            fk_short_lanes(FT, GS, F, O, X, pm, names, cand, nver, nwin, nver_w, nwin_w);
-        }
-        else
-            fk_short_field(FT, FT.pat_tcps, GS, F, O, nver_w, nwin_w,
-                           [&](uint32_t P) { xq_push(X, lane == 0, F.doc, P, F.field); });
+        fk_short_lanes(FT, GS, F, O, X, pm, names, cand, nver, nwin, nver_w, nwin_w);
     }
     task_stats(S, wave_sum64(nver) + nver_w, wave_sum64(nwin) + nwin_w, 0, 0, 0, 0);
 }
@@ -2162,11 +2065,6 @@ __global__ __launch_bounds__(RK_BLOCK, RX_MINW) void kw_rx_task_kernel(FastTable
             if (L && fk_rx_items(S, GS, F, O, P, L, (uint32_t)__builtin_amdgcn_readfirstlane((int)q.w),
                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)pre[5 * j + 2].x)))
                 continue;
-#if defined(RX_TIMING_SKIP) && RX_TIMING_SKIP <= 2   // (timing variants only: 1 skips the backtracking
-                                                      // searches, 2 every search, 3 the shift-and loops, 4 all
-                                                      // but the mask table load)
-            if (RX_TIMING_SKIP == 2 || FT.rxf_idx[P] < 0) continue;
-#endif
             const uint4 q2 = pre[5 * j + 2], q3 = pre[5 * j + 3];
             RxfParams prm;
             prm.L = (uint32_t)__builtin_amdgcn_readfirstlane((int)q2.z);
@@ -2183,22 +2081,6 @@ __global__ __launch_bounds__(RK_BLOCK, RX_MINW) void kw_rx_task_kernel(FastTable
 
 
 // ---------------------------------------------------------------- kernel 2: resolve
-#ifndef RK_NOINLINE   // 1: the resolve kernels call fk_resolve_field (fewer spills, a call frame); 0: inlined
-#define RK_NOINLINE 0
-#endif
-template <uint32_t ICAP>
-__device__ __attribute__((noinline)) int fk_resolve_field_call(const FastTables &FT, const DevTables &T, const DevScratch &GS,
-                                                               FieldCtx &F, OutCtx &O, uint64_t *items_lds,
-                                                               uint32_t *icnt_f, uint32_t *dflag, uint32_t *cps,
-                                                               uint32_t *blkcnt, uint64_t *rxtab, RxQueue &RQ,
-                                                               bool maybe_nonascii, bool edge, unsigned long long &nver,
-                                                               unsigned long long &nwin, unsigned long long &nedge,
-                                                               unsigned long long *tacc)
-{
-    return fk_resolve_field<ICAP>(FT, T, GS, F, O, items_lds, icnt_f, dflag, cps, blkcnt, rxtab, RQ, maybe_nonascii, edge,
-                                  nver, nwin, nedge, tacc);
-}
-
 struct RkCounters {   // (per wave: the uniform ones in 32 bits, fewer scalar registers to spill)
     unsigned long long nver, nwin, nedge;
     uint32_t ndefer, ndef_cp, ndef_items, nres, nrx, nrx_bt, nrx_rounds;
@@ -2212,8 +2094,7 @@ __device__ __forceinline__ void rk_resolve_doc(const FastTables &FT, const DevTa
                                                const FastScratch &S, const uint8_t *__restrict__ arena,
                                                const int64_t *__restrict__ off, int64_t d, uint32_t hx, uint32_t n0,
                                                uint32_t n1, uint32_t hy, uint64_t *items, uint32_t *icnt, uint32_t *cps,
-                                               uint32_t *blkcnt, uint64_t *rxtab, OutCtx &O, RxQueue &RQ, RkCounters &C,
-                                               unsigned long long *tacc)
+                                               uint32_t *blkcnt, uint64_t *rxtab, OutCtx &O, RxQueue &RQ, RkCounters &C)
 {
     const int lane = lane_id();
     const int64_t t0 = off[2 * d], t1 = off[2 * d + 1], t2 = off[2 * d + 2];
@@ -2239,13 +2120,8 @@ __device__ __forceinline__ void rk_resolve_doc(const FastTables &FT, const DevTa
         F.n = 0;
         const bool na = (hy & (f ? DH_NA1 : DH_NA0)) != 0;
         const bool edge = (hy & (f ? DH_EDGE1 : DH_EDGE0)) != 0;
-        int rs = 0;
-        if constexpr (RK_NOINLINE)
-            rs = fk_resolve_field_call<ICAP>(FT, T, GS, F, O, items, &icnt[0], &icnt[1], cps, blkcnt, rxtab, RQ, na,
-                                             edge, C.nver, C.nwin, C.nedge, tacc);
-        else
-            rs = fk_resolve_field<ICAP>(FT, T, GS, F, O, items, &icnt[0], &icnt[1], cps, blkcnt, rxtab, RQ, na, edge,
-                                        C.nver, C.nwin, C.nedge, tacc);
+        const int rs = fk_resolve_field<ICAP>(FT, T, GS, F, O, items, &icnt[0], &icnt[1], cps, blkcnt, rxtab, RQ, na,
+                                              edge, C.nver, C.nwin, C.nedge);
         if (rs) {
             defer = true;
             if (rs == 1) ++C.ndef_cp;
@@ -2269,14 +2145,12 @@ __device__ __forceinline__ void rk_resolve_doc(const FastTables &FT, const DevTa
 __device__ __forceinline__ void rk_wave_tail(const FastTables &FT, const DevTables &T, const DevScratch &GS,
                                              const FastScratch &S, const uint8_t *__restrict__ arena,
                                              const int64_t *__restrict__ off, int64_t wave, uint32_t *cps,
-                                             uint32_t *blkcnt, uint64_t *rxtab, OutCtx &O, RxQueue &RQ, RkCounters &C,
-                                             unsigned long long *tacc, unsigned long long tall0)
+                                             uint32_t *blkcnt, uint64_t *rxtab, OutCtx &O, RxQueue &RQ, RkCounters &C)
 {
     const int lane = lane_id();
     wave_sync_global();
     if (RQ.n > RQ.cap && lane == 0) atomicMax(&GS.status[2], RQ.n);   // the queue size a rescan needs
     const uint32_t n_rx = RQ.n < RQ.cap ? RQ.n : RQ.cap;
-    FK_T0(trx0);
     uint32_t dec_d = 0xFFFFFFFFu, dec_f = 0;   // the field whose code points cps holds (tasks come in doc order)
     for (uint32_t t = 0; t < n_rx; ++t) {
         const uint4 tk = RQ.q[t];
@@ -2306,10 +2180,6 @@ __device__ __forceinline__ void rk_wave_tail(const FastTables &FT, const DevTabl
                                     : rx_positions(T, GS, F, O, P);
         if (cnt == 0) emit_hits(O, GS, lane == 0, d, P, KW_NOPOS, F.field);
     }
-    FK_TACC(tacc[4], trx0);
-    FK_TACC(tacc[5], tall0);
-    if (FK_TIMING && lane == 0)
-        for (int i = 0; i < 6; ++i) atomicAdd(&S.stats[21 + i], tacc[i]);
     if (lane == 0) S.out_cnt[wave] = O.n;
     unsigned long long v = C.nver, w = C.nwin;
 #pragma unroll
@@ -2362,8 +2232,6 @@ __global__ __launch_bounds__(RK_BLOCK, RK_OCC) void kw_resolve_kernel(FastTables
     RQ.n = 0;
     RQ.txt = (uint8_t *)(rxtxt_all + wib * (RX_TXT / 16));
     RkCounters C = {};
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0};   // FK_TIMING: decode, edge, items, short, regex, all
-    FK_T0(tall0);
 
     const int64_t n_list = (int64_t)min(*S.res_cnt, S.defer_cap);
     // chunks of up to 64 documents per wave, fewer when the list is short (each wave finishes its chunk's
@@ -2435,10 +2303,10 @@ __global__ __launch_bounds__(RK_BLOCK, RK_OCC) void kw_resolve_kernel(FastTables
             const uint32_t hx = (uint32_t)__shfl((int)hl.x, l, WAVE);
             const uint32_t hy = (uint32_t)__shfl((int)hl.y, l, WAVE);
             rk_resolve_doc<FK_ITEMS_MAX>(FT, T, GS, S, arena, off, d, hx, hy & 1023u, (hy >> DH_N1_SHIFT) & 127u, hy,
-                                         items, icnt, cps, blkcnt, rxtab, O, RQ, C, tacc);
+                                         items, icnt, cps, blkcnt, rxtab, O, RQ, C);
         }
     }
-    rk_wave_tail(FT, T, GS, S, arena, off, wave, cps, blkcnt, rxtab, O, RQ, C, tacc, tall0);
+    rk_wave_tail(FT, T, GS, S, arena, off, wave, cps, blkcnt, rxtab, O, RQ, C);
 }
 
 // ---------------------------------------------------------------- kernel 2b: big non-ASCII documents
@@ -2469,16 +2337,14 @@ __global__ __launch_bounds__(WAVE) void kw_resolve_big_kernel(FastTables FT, Dev
     RQ.n = 0;
     RQ.txt = (uint8_t *)rxtxt;
     RkCounters C = {};
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0};
-    FK_T0(tall0);
     for (int64_t i = wave; i < (int64_t)nbig; i += gridDim.x) {
         const uint32_t d = S.big_list[S.defer_cap - 1 - i];   // (the list's tail end: see kw_resolve_kernel)
         const uint2 h = S.hdr[d];
         const uint2 nc = S.ncnt[d];
         rk_resolve_doc<FK_BIG0>(FT, T, GS, S, arena, off, d, h.x, nc.x, nc.y, h.y, items, icnt, cps, blkcnt, rxtab, O,
-                                RQ, C, tacc);
+                                RQ, C);
     }
-    rk_wave_tail(FT, T, GS, S, arena, off, wave, cps, blkcnt, rxtab, O, RQ, C, tacc, tall0);
+    rk_wave_tail(FT, T, GS, S, arena, off, wave, cps, blkcnt, rxtab, O, RQ, C);
     if (wave == 0 && lane_id() == 0) atomicAdd(&S.stats[16], (unsigned long long)nbig);
 }
 }  // namespace kw

@@ -25,11 +25,6 @@
 #pragma once
 #include "kwmatch_device.hpp"
 
-// profiling builds: 0 = filter only, 1 = + anchor probe, 2 = + resolve w/o LCS, 3 = full
-#ifndef KW_STAGE
-#define KW_STAGE 3
-#endif
-
 namespace kw {
 
 // ------------------------------------------------------------------ wave utils
@@ -517,7 +512,6 @@ namespace kw {
 __device__ bool verify_piece(const DevTables &T, const FieldCtx &F, uint32_t P, uint32_t m, uint32_t q, uint32_t o,
                              uint32_t plen, unsigned long long &nwin)
 {
-    if (KW_STAGE < 3) return false;
     const uint32_t n = F.n;
     const uint64_t mask = low_mask(m);
     const uint32_t k = kfull(m);
@@ -1030,7 +1024,7 @@ __global__ __launch_bounds__(BLOCK) void kw_scan_kernel(DevTables T, const uint8
             wave_sync();
             for (int i0 = 0; i0 < total; i0 += WAVE) {
                 const int i = i0 + lane;
-                if (KW_STAGE >= 1 && i < total) process_candidate(T, S, arena, t0, t1, t2, cand[i], items0, items1, icnt, nanchor);
+                if (i < total) process_candidate(T, S, arena, t0, t1, t2, cand[i], items0, items1, icnt, nanchor);
             }
             wave_sync();
         }
@@ -1056,7 +1050,7 @@ __global__ __launch_bounds__(BLOCK) void kw_scan_kernel(DevTables T, const uint8
             const uint32_t N = f ? N1 : N0;
             if (N == 0 && F.n > (uint32_t)MAXM) continue;
             if (!F.ascii) decode_field(S, arena, F.fb, F.fe, cps, blkcnt);
-            if (KW_STAGE >= 2) resolve_field(T, S, F, O, f ? items1 : items0, N, lpm, lext_cp, lext_mask, nwin);
+            resolve_field(T, S, F, O, f ? items1 : items0, N, lpm, lext_cp, lext_mask, nwin);
         }
     }
     if (lane == 0) {

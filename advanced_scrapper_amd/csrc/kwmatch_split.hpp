@@ -50,9 +50,6 @@ constexpr int PK_BLOCK = PK_WAVES * WAVE;
 #define PK_POOL_CFG 768   // (with PK_MINW 5: 5 probe waves per SIMD; 1024 / 4: 6.15 vs 5.97 ms per step)
 #endif
 constexpr int PK_POOL = PK_POOL_CFG;     // items one batch of 64 candidates may stage (more: their documents defer)
-#ifndef FK_TX
-#define FK_TX 1     // 0: every document with a non-ASCII field goes to the resolve kernel
-#endif
 #ifndef EK_MINW
 #define EK_MINW 4   // 128 VGPRs, no spill (5 waves per SIMD spills 96 B per lane: epilogue 2.08 vs 1.98 ms)
 #endif
@@ -64,9 +61,6 @@ constexpr int EK_BIGQ = 64;              // big documents one epilogue workgroup
 constexpr int EK_BLOCK = EK_WAVES * WAVE;
 
 constexpr int FG_DOCS = 32;              // documents per filter group (one flat byte range; 5 bits of a candidate)
-#ifndef EF_TX_FLAT
-#define EF_TX_FLAT 1   // kw_epi_flat_kernel<true> batches the transcoded documents too (KBs without PI_TXUNSAFE names)
-#endif
 
 struct __attribute__((aligned(16))) FilterLds {
     uint32_t s1[FK_S1_WORDS];
@@ -345,15 +339,11 @@ __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds
             wave_sync();
             // the key's two aligned words (joined when the round finishes: no wait for them here)
             uint32_t x0 = 0, x1 = 0;
-#if defined(FS_TIMING_SKIP) && FS_TIMING_SKIP == 2   // (traffic calibration only, results void: no key re-read)
-            x0 = r * 0x9E3779B1u;
-#else
             if ((uint32_t)lane < n) {
                 const int64_t a0 = (gb + (int64_t)r) & ~(int64_t)3;
                 x0 = *(const uint32_t *)(arena + a0);
                 x1 = *(const uint32_t *)(arena + a0 + 4);
             }
-#endif
             if (qn) round_at(qn, qr, __builtin_amdgcn_alignbyte(qx1, qx0, (uint32_t)(gb + qr) & 3u));
             qn = n;
             qr = r;
@@ -410,9 +400,6 @@ __device__ __forceinline__ void fk_filter_groups(const FastTables &FT, FilterLds
             if (!em) return;
             if (sm != 0u) sent[(eh + en + mbcnt(em)) & (2u * WAVE - 1u)] = make_uint2(rel, sm);
             en += (uint32_t)__popcll(em);
-#if defined(FS_TIMING_SKIP) && FS_TIMING_SKIP == 1   // (traffic calibration only, results void: no stage 2)
-            en = 0;
-#endif
             while (en >= (uint32_t)FS_EQ_TRIGGER) round();
         };
         uint4 v[FS_AHEAD];
@@ -613,12 +600,7 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void kw_probe_kernel(FastTables 
             }
         }
         uint32_t tcur = rb[0], tend = re[0], b1 = rb[1], e1 = re[1], b2 = rb[2], e2 = re[2];
-#if defined(PK_TIMING_SKIP) && PK_TIMING_SKIP == 2
-        bool more = false;
-        if (__ballot(valid && (tcur | b1 | b2) == 0xFFFFFFFFu)) nanchor += 1;   // (keeps the lookups)
-#else
         bool more = valid;
-#endif
         uint32_t pn = 0;                    // items in the pool (wave-uniform)
         while (__ballot(more)) {
             // stage A: up to two matching anchors of this lane's candidate
@@ -656,9 +638,6 @@ __global__ __launch_bounds__(PK_BLOCK, PK_MINW) void kw_probe_kernel(FastTables 
             // stage B: (candidate, use) pairs over the lanes
             int total;
             const int ex = wave_excl_scan_dpp((int)(uc + uc1), &total);
-#if defined(PK_TIMING_SKIP)   // (timing variants only, results void: 1 no stage B, 2 no stage A or B)
-            total = 0;
-#endif
             for (int g0 = 0; g0 < total; g0 += WAVE) {
                 const int g = g0 + lane;
                 bool pass = false;
@@ -1054,6 +1033,18 @@ __device__ __forceinline__ bool fk_txu_edge(const FastTables &FT, const uint8_t 
     return __ballot(c) != 0;
 }
 
+// D = document d with its fields at [t0, t1) and [t1, t2) of arena
+__device__ __forceinline__ void epi_fast_doc(FastDoc &D, const uint8_t *arena, uint32_t d, int64_t t0, int64_t t1, int64_t t2)
+{
+    D.arena = arena;
+    D.t0 = t0;
+    D.t1 = t1;
+    D.t2 = t2;
+    D.doc = d;
+    D.l1 = (int32_t)(t1 - t0);
+    D.l2 = (int32_t)(t2 - t0);
+}
+
 // Finish a transcoded document (V = its vrec) in the epilogue.  D0: the document in the arena, flags: its
 // dflags | edge flags (of the arena bytes).  Returns false, before anything is emitted, when the resolve
 // kernel must take it; otherwise *done = the epilogue's result (false: the generic kernel).
@@ -1103,6 +1094,62 @@ __device__ bool epi_tx_doc(const FastTables &FT, const FastScratch &S, const Dev
     return true;
 }
 
+// ---------------------------------------------------------------- the epilogue kernels' shared bookkeeping
+// (kw_epi_kernel, kw_epi_flat_kernel and epi_big_doc.  A document index keeps its caller's type and the counts
+// go by value: so written, the kernels compile to the code they had with these blocks spelled out at each site,
+// scripts/isa_diff.py.  The non-ASCII document's and the plain document's header blocks are still written out
+// in both kernels: as functions they changed the kernels' register allocation.)
+struct EpiCounts {   // per wave: documents deferred / deferred for their items / on the view / left to resolve
+    uint32_t ndefer, ndef_items, ntx, nres;
+};
+
+// document d is the resolve kernel's: DH_RESOLVE in its flags, a place in res_list
+template <typename DocIdx>   // (uint32_t or int64_t, as the caller holds it)
+__device__ __forceinline__ void epi_to_resolve(const FastScratch &S, DocIdx d, uint32_t flags)
+{
+    if (lane_id() == 0) {
+        S.dflags[d] = flags | DH_RESOLVE;
+        const uint32_t i = atomicAdd(S.res_cnt, 1u);
+        if (i < S.defer_cap) S.res_list[i] = (uint32_t)d;
+    }
+}
+
+// document d is the generic kernel's: a place in defer_list (a full list: the scan is redone with a longer one)
+template <typename DocIdx>
+__device__ __forceinline__ void epi_to_generic(const FastScratch &S, DocIdx d)
+{
+    if (lane_id() == 0) {
+        const uint32_t i = atomicAdd(S.defer_cnt, 1u);
+        if (i < S.defer_cap) S.defer_list[i] = (uint32_t)d;
+        else atomicOr(&S.status[0], ST_ITEM_OVERFLOW);
+    }
+}
+
+// An epilogue wave's last words: its record and task counts (a task region that overflowed: the sizes a
+// rescan needs), the statistics.
+__device__ __forceinline__ void epi_wave_close(const FastScratch &S, int64_t wave, uint32_t n_out, TaskCounts TC,
+                                               EpiCounts C)
+{
+    if (lane_id() == 0) {
+        S.kout_cnt[wave] = n_out;
+        S.vcnt[wave] = TC.v;
+        if (TC.e) atomicAdd(&S.stats[7], (unsigned long long)TC.e);
+        S.scnt[wave] = TC.s;
+        S.xcnt[wave] = TC.x;
+        S.xmark[wave] = TC.x;   // (the regex tasks the epilogue queued: KW_RX_SPLIT's early phase)
+        if (TC.v > S.vcap || TC.s > S.scap || TC.x > S.xcap) {
+            atomicOr(&S.status[0], ST_TASK_OVERFLOW);
+            atomicMax(&S.tmax[0], TC.v);
+            atomicMax(&S.tmax[2], TC.s);
+            atomicMax(&S.tmax[3], TC.x);
+        }
+        atomicAdd(&S.stats[4], (unsigned long long)C.ndefer);
+        atomicAdd(&S.stats[5], (unsigned long long)C.ndef_items);
+        if (C.ntx) atomicAdd(&S.stats[18], (unsigned long long)C.ntx);
+        if (C.nres) atomicAdd(&S.stats[19], (unsigned long long)C.nres);
+    }
+}
+
 constexpr uint32_t EK_TXBIG = 0x80000000u;   // blk_docs entry: a transcoded big document (epi_big_doc)
 
 // ---------------------------------------------------------------- big documents
@@ -1113,18 +1160,9 @@ constexpr uint32_t EK_TXBIG = 0x80000000u;   // blk_docs entry: a transcoded big
 // tests and item positions), else left to the resolve kernel.  Returns bit 0: the document went to the
 // generic kernel (a name with > 64 items), bit 1: finished on its transcoded view, bit 2: left to the
 // resolve kernel, bit 3: a deferral of the transcoded view's.
-#ifndef EK_BIG_NOINLINE   // 1: epi_big_doc as a called function (a call frame; 0: inlined into the epilogue)
-#define EK_BIG_NOINLINE 0
-#endif
-#if EK_BIG_NOINLINE
-__device__ __attribute__((noinline))
-#else
-__device__ __forceinline__
-#endif
-uint32_t epi_big_doc(const FastTables &FT, const FastScratch &S, const DevScratch &GS,
-                                                          const uint8_t *__restrict__ arena, const int64_t *__restrict__ off,
-                                                          uint32_t e, uint64_t *items, int64_t wave, OutCtx &O,
-                                                          TaskCounts &TC)
+__device__ __forceinline__ uint32_t epi_big_doc(const FastTables &FT, const FastScratch &S, const DevScratch &GS,
+                                                const uint8_t *__restrict__ arena, const int64_t *__restrict__ off,
+                                                uint32_t e, uint64_t *items, int64_t wave, OutCtx &O, TaskCounts &TC)
 {
     const int lane = lane_id();
     const bool tx = (e & EK_TXBIG) != 0;
@@ -1133,13 +1171,7 @@ uint32_t epi_big_doc(const FastTables &FT, const FastScratch &S, const DevScratc
     const uint2 hv = lane == 3 ? S.hdr[d] : (lane == 4 ? S.ncnt[d] : (lane == 5 ? make_uint2(0u, S.dflags[d]) :
                                                                     make_uint2(0u, 0u)));
     FastDoc D;
-    D.arena = arena;
-    D.t0 = rdlane64(ov, 0);
-    D.t1 = rdlane64(ov, 1);
-    D.t2 = rdlane64(ov, 2);
-    D.doc = d;
-    D.l1 = (int32_t)(D.t1 - D.t0);
-    D.l2 = (int32_t)(D.t2 - D.t0);
+    epi_fast_doc(D, arena, d, rdlane64(ov, 0), rdlane64(ov, 1), rdlane64(ov, 2));
     const uint32_t ibeg = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 3);
     const uint32_t dfl = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 5);
     const uint32_t flags = dfl & ~DH_DEFER;   // (with the filter's edge-prefilter bits)
@@ -1179,11 +1211,7 @@ uint32_t epi_big_doc(const FastTables &FT, const FastScratch &S, const DevScratc
             D.l2 = (int32_t)(c0 + c1);
         }
         if (!view) {
-            if (lane == 0) {
-                S.dflags[d] = dfl | DH_RESOLVE;
-                const uint32_t i = atomicAdd(S.res_cnt, 1u);
-                if (i < S.defer_cap) S.res_list[i] = d;
-            }
+            epi_to_resolve(S, d, dfl);
             wave_sync();
             return 4u;
         }
@@ -1197,10 +1225,8 @@ uint32_t epi_big_doc(const FastTables &FT, const FastScratch &S, const DevScratc
     h.x = ibeg;
     if (!done) {
         h.y = DH_DEFER;
+        epi_to_generic(S, d);
         if (lane == 0) {
-            const uint32_t j = atomicAdd(S.defer_cnt, 1u);
-            if (j < S.defer_cap) S.defer_list[j] = d;
-            else atomicOr(&S.status[0], ST_ITEM_OVERFLOW);
             if (!tx) atomicAdd(&S.stats[5], 1ull);
             atomicAdd(&S.stats[13], 1ull);
         }
@@ -1255,7 +1281,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
     const int64_t wave = (int64_t)blockIdx.x * EK_WAVES + wib;
     const int64_t n_waves = (int64_t)gridDim.x * EK_WAVES;
     uint64_t *items = items_all + wib * (FK_ITEMS0 + FK_ITEMS1);
-    uint32_t ndefer = 0, ndef_items = 0, ntx = 0, nres = 0;
+    EpiCounts C = {0u, 0u, 0u, 0u};
     OutCtx O;
     O.shared = nullptr;
     O.out = S.kout + (size_t)wave * S.out_cap;
@@ -1273,22 +1299,13 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
         epi_meta(S, off, wave, ov, hv);
         epi_prefetch(S, ov, hv, itp);
     }
-    unsigned long long ekt[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    EK_T0(tk0);
     for (int64_t d = wave; d < n_docs; d += n_waves) {
-        EK_T0(td0);
         const int64_t dn = d + n_waves;
         int64_t ovn = 0;
         uint2 hvn = make_uint2(0u, 0u);
         if (dn < n_docs) epi_meta(S, off, dn, ovn, hvn);
         FastDoc D;
-        D.arena = arena;
-        D.t0 = rdlane64(ov, 0);
-        D.t1 = rdlane64(ov, 1);
-        D.t2 = rdlane64(ov, 2);
-        D.doc = (uint32_t)d;
-        D.l1 = (int32_t)(D.t1 - D.t0);
-        D.l2 = (int32_t)(D.t2 - D.t0);
+        epi_fast_doc(D, arena, (uint32_t)d, rdlane64(ov, 0), rdlane64(ov, 1), rdlane64(ov, 2));
         const uint32_t ibeg = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 3);
         uint32_t flags = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 5);
         if (flags & (DH_NA0 | DH_NA1)) {
@@ -1297,37 +1314,28 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 4);
             const uint32_t fl = flags;
             bool done = false;
-            if (FK_TX && epi_tx_doc(FT, S, GS, D, S.vrec[d], ibeg, n0, n1, fl, items, wave, O, TC, &done)) {
-                ++ntx;
+            if (epi_tx_doc(FT, S, GS, D, S.vrec[d], ibeg, n0, n1, fl, items, wave, O, TC, &done)) {
+                ++C.ntx;
                 uint2 h;
                 h.x = ibeg;
                 if (!done) {
-                    ++ndefer;
-                    ++ndef_items;
+                    ++C.ndefer;
+                    ++C.ndef_items;
                     h.y = DH_DEFER;
-                    if (lane == 0) {
-                        atomicAdd(&S.stats[13], 1ull);
-                        const uint32_t i = atomicAdd(S.defer_cnt, 1u);
-                        if (i < S.defer_cap) S.defer_list[i] = (uint32_t)d;
-                        else atomicOr(&S.status[0], ST_ITEM_OVERFLOW);
-                    }
+                    if (lane == 0) atomicAdd(&S.stats[13], 1ull);
+                    epi_to_generic(S, d);
                 } else {
                     h.y = n0 | (n1 << DH_N1_SHIFT) | (fl & ~DH_DEFER) | DH_TX;   // (vrec: kw_tx_kernel's)
                 }
                 if (lane == 0) S.hdr[d] = h;
             } else {
-                ++nres;
-                if (lane == 0) {
-                    S.dflags[d] = flags | DH_RESOLVE;
-                    const uint32_t i = atomicAdd(S.res_cnt, 1u);
-                    if (i < S.defer_cap) S.res_list[i] = (uint32_t)d;
-                }
+                ++C.nres;
+                epi_to_resolve(S, d, flags);
             }
             wave_sync();
         } else {
             const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)hv.x, 4);
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)hv.y, 4);
-            EK_TACC(ekt[5], td0);
             bool defer = (flags & DH_DEFER) != 0 || D.t1 - D.t0 > MAX_FIELD_BYTES || D.t2 - D.t1 > MAX_FIELD_BYTES;
             if (defer && lane == 0) atomicAdd(&S.stats[15], 1ull);   // (rare: counted where they happen)
             bool queued = false;
@@ -1343,16 +1351,12 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
                     queued = true;
                 } else if (n0 <= (uint32_t)FK_BIG0 && n1 <= (uint32_t)FK_BIG0) {
                     // the workgroup's queue is full (or the title is past FK_BIG1): the resolve kernel's big documents
-                    ++nres;
+                    ++C.nres;
                     queued = true;
-                    if (lane == 0) {
-                        S.dflags[d] = flags | DH_RESOLVE;
-                        const uint32_t i = atomicAdd(S.res_cnt, 1u);
-                        if (i < S.defer_cap) S.res_list[i] = (uint32_t)d;
-                    }
+                    epi_to_resolve(S, d, flags);
                 } else {
                     defer = true;
-                    ++ndef_items;
+                    ++C.ndef_items;
                     if (lane == 0) atomicAdd(&S.stats[14], 1ull);
                 }
             }
@@ -1366,25 +1370,19 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
                     for (uint32_t i = (uint32_t)lane; i < n1; i += WAVE)
                         if (n0 + i >= (uint32_t)WAVE) items[FK_ITEMS0 + i] = src[n0 + i];
                     wave_sync();
-                    EK_T0(td2);
-                    const bool done = fk_scan_epilogue(FT, S, GS, D, items, n0, n1, flags, wave, O, TC, ekt);
-                    EK_TACC(ekt[7], td2);
+                    const bool done = fk_scan_epilogue(FT, S, GS, D, items, n0, n1, flags, wave, O, TC);
                     if (!done) {
                         defer = true;
-                        ++ndef_items;
+                        ++C.ndef_items;
                         if (lane == 0) atomicAdd(&S.stats[13], 1ull);
                     }
                 }
                 uint2 h;
                 h.x = ibeg;
                 if (defer) {
-                    ++ndefer;
+                    ++C.ndefer;
                     h.y = DH_DEFER;
-                    if (lane == 0) {
-                        const uint32_t i = atomicAdd(S.defer_cnt, 1u);
-                        if (i < S.defer_cap) S.defer_list[i] = (uint32_t)d;
-                        else atomicOr(&S.status[0], ST_ITEM_OVERFLOW);
-                    }
+                    epi_to_generic(S, d);
                 } else {
                     h.y = n0 | (n1 << DH_N1_SHIFT) | flags;
                     if (lane == 0) S.vrec[d] = make_uint4((uint32_t)D.t0, (uint32_t)((uint64_t)D.t0 >> 32), (uint32_t)(D.t1 - D.t0), (uint32_t)(D.t2 - D.t1));
@@ -1393,46 +1391,19 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_kernel(FastTables FT
                 wave_sync();
             }
         }
-        EK_T0(td3);
         itp = 0;
         if (dn < n_docs) epi_prefetch(S, ovn, hvn, itp);
         ov = ovn;
         hv = hvn;
-        EK_TACC(ekt[8], td3);
-        EK_TACC(ekt[9], td0);
     }
-    EK_TACC(ekt[10], tk0);
-    if (EK_TIMING && lane == 0)
-        for (int i = 0; i < 11; ++i) atomicAdd(&S.stats[21 + i], ekt[i]);
     // the workgroup's big documents: wave 0 with the whole workgroup's LDS as one 4096 + 512-item buffer
     __syncthreads();
-#if defined(EK_TIMING_SKIP_BIG)   // (timing variant only, results void: the big documents are not finished)
-    const uint32_t nb = 0;
-#else
     const uint32_t nb = min(blk_n, S.bigq);
-#endif
     if (wib == 0 && nb) {
-        for (uint32_t i = 0; i < nb; ++i) ndefer += epi_big_doc(FT, S, GS, arena, off, blk_docs[i], items_all, wave, O, TC) & 1u;
+        for (uint32_t i = 0; i < nb; ++i) C.ndefer += epi_big_doc(FT, S, GS, arena, off, blk_docs[i], items_all, wave, O, TC) & 1u;
         if (lane == 0) atomicAdd(&S.stats[16], (unsigned long long)nb);
     }
-    if (lane == 0) {
-        S.kout_cnt[wave] = O.n;
-        S.vcnt[wave] = TC.v;
-        if (TC.e) atomicAdd(&S.stats[7], (unsigned long long)TC.e);
-        S.scnt[wave] = TC.s;
-        S.xcnt[wave] = TC.x;
-        S.xmark[wave] = TC.x;   // (the regex tasks the epilogue queued: KW_RX_SPLIT's early phase)
-        if (TC.v > S.vcap || TC.s > S.scap || TC.x > S.xcap) {
-            atomicOr(&S.status[0], ST_TASK_OVERFLOW);
-            atomicMax(&S.tmax[0], TC.v);
-            atomicMax(&S.tmax[2], TC.s);
-            atomicMax(&S.tmax[3], TC.x);
-        }
-        atomicAdd(&S.stats[4], (unsigned long long)ndefer);
-        atomicAdd(&S.stats[5], (unsigned long long)ndef_items);
-        if (ntx) atomicAdd(&S.stats[18], (unsigned long long)ntx);
-        if (nres) atomicAdd(&S.stats[19], (unsigned long long)nres);
-    }
+    epi_wave_close(S, wave, O.n, TC, C);
 }
 
 
@@ -1463,7 +1434,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
     const int64_t n_waves = (int64_t)gridDim.x * EK_WAVES;
     uint64_t *items = items_all + wib * (FK_ITEMS0 + FK_ITEMS1);
     uint4 *segtx = segtx_all + (TXB ? wib * WAVE : 0);
-    uint32_t ndefer = 0, ndef_items = 0, ntx = 0, nres = 0;
+    EpiCounts C = {0u, 0u, 0u, 0u};
     OutCtx O;
     O.shared = nullptr;
     O.out = S.kout + (size_t)wave * S.out_cap;
@@ -1651,7 +1622,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
         for (int f = 0; f < 2; ++f) {
             const int64_t lf = f ? (int64_t)c1 : (int64_t)c0;
             bool sh = flat && lf <= (int64_t)MAXM;
-            if (EPI_SHORT_PREF && sh && lf > (int64_t)SHORT_EXACT_MAX) {
+            if (sh && lf > (int64_t)SHORT_EXACT_MAX) {
                 const uint32_t n = (uint32_t)lf, cnt = (uint32_t)FT.f_count_ge[n];
                 if (cnt <= (uint32_t)WAVE) {
                     // (a transcoded document's field: its view bytes; the reads past the field stay in tarena's
@@ -1690,7 +1661,6 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
                 }
             }
             const uint64_t shm = __ballot(sh);
-            if (SHORT_COUNT && lane == 0 && shm) atomicAdd(&S.stats[25 + f], (unsigned long long)__popcll(shm));
             if (shm) {
                 const uint32_t si = TC.s + mbcnt(shm);
                 if (sh && si < S.scap) sq[si] = make_uint4((uint32_t)d, (uint32_t)f, 0u, 0u);
@@ -1725,7 +1695,7 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
             if (!txd)   // (a transcoded document's view record is the transcoding kernel's)
                 S.vrec[d] = make_uint4((uint32_t)t0, (uint32_t)((uint64_t)t0 >> 32), (uint32_t)l0, (uint32_t)l1);
         }
-        ntx += (uint32_t)__popcll(txm);
+        C.ntx += (uint32_t)__popcll(txm);
         // ---- the other documents, one at a time (kw_epi_kernel's per-document code)
         uint64_t slow = __ballot(act && !flat);
         while (slow) {
@@ -1733,31 +1703,21 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
             slow &= slow - 1;
             const int64_t dd = d0 + l;
             FastDoc D;
-            D.arena = arena;
-            D.t0 = rdlane64(t0, l);
-            D.t1 = rdlane64(t1, l);
-            D.t2 = rdlane64(t2, l);
-            D.doc = (uint32_t)dd;
-            D.l1 = (int32_t)(D.t1 - D.t0);
-            D.l2 = (int32_t)(D.t2 - D.t0);
+            epi_fast_doc(D, arena, (uint32_t)dd, rdlane64(t0, l), rdlane64(t1, l), rdlane64(t2, l));
             const uint32_t ibeg = (uint32_t)__builtin_amdgcn_readlane((int)hd.x, l);
             const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)nc.x, l);
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)nc.y, l);
             const uint32_t dfl = (uint32_t)__builtin_amdgcn_readlane((int)fl, l);
             const uint32_t dflags = (uint32_t)__builtin_amdgcn_readlane((int)flags, l);
             if (TXB && (dfl & (DH_NA0 | DH_NA1))) {   // (no view, or more than 64 items in a field)
-                ++nres;
-                if (lane == 0) {
-                    S.dflags[dd] = dfl | DH_RESOLVE;
-                    const uint32_t i = atomicAdd(S.res_cnt, 1u);
-                    if (i < S.defer_cap) S.res_list[i] = (uint32_t)dd;
-                }
+                ++C.nres;
+                epi_to_resolve(S, dd, dfl);
                 wave_sync();
                 continue;
             }
             if (dfl & (DH_NA0 | DH_NA1)) {
                 bool done = false;
-                if (FK_TX && (n0 > (uint32_t)FK_ITEMS0 || n1 > (uint32_t)FK_ITEMS1) && n0 <= (uint32_t)FK_BIG0 &&
+                if ((n0 > (uint32_t)FK_ITEMS0 || n1 > (uint32_t)FK_ITEMS1) && n0 <= (uint32_t)FK_BIG0 &&
                     n1 <= (uint32_t)FK_BIG1 && !(dflags & DH_DEFER)) {
                     // more items than a wave holds: the workgroup's big documents, on its LDS after the loop
                     uint32_t bi = 0;
@@ -1769,31 +1729,23 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
                         continue;
                     }
                 }
-                if (FK_TX && epi_tx_doc(FT, S, GS, D, S.vrec[dd], ibeg, n0, n1, dflags, items, wave, O, TC, &done)) {
-                    ++ntx;
+                if (epi_tx_doc(FT, S, GS, D, S.vrec[dd], ibeg, n0, n1, dflags, items, wave, O, TC, &done)) {
+                    ++C.ntx;
                     uint2 h;
                     h.x = ibeg;
                     if (!done) {
-                        ++ndefer;
-                        ++ndef_items;
+                        ++C.ndefer;
+                        ++C.ndef_items;
                         h.y = DH_DEFER;
-                        if (lane == 0) {
-                            atomicAdd(&S.stats[13], 1ull);
-                            const uint32_t i = atomicAdd(S.defer_cnt, 1u);
-                            if (i < S.defer_cap) S.defer_list[i] = (uint32_t)dd;
-                            else atomicOr(&S.status[0], ST_ITEM_OVERFLOW);
-                        }
+                        if (lane == 0) atomicAdd(&S.stats[13], 1ull);
+                        epi_to_generic(S, dd);
                     } else {
                         h.y = n0 | (n1 << DH_N1_SHIFT) | (dflags & ~DH_DEFER) | DH_TX;   // (vrec: kw_tx_kernel's)
                     }
                     if (lane == 0) S.hdr[dd] = h;
                 } else {
-                    ++nres;
-                    if (lane == 0) {
-                        S.dflags[dd] = dfl | DH_RESOLVE;
-                        const uint32_t i = atomicAdd(S.res_cnt, 1u);
-                        if (i < S.defer_cap) S.res_list[i] = (uint32_t)dd;
-                    }
+                    ++C.nres;
+                    epi_to_resolve(S, dd, dfl);
                 }
                 wave_sync();
                 continue;
@@ -1807,19 +1759,14 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
                     uint32_t bi = 0xFFFFFFFFu;
                     if (lane == 0 && n1 <= (uint32_t)FK_BIG1) bi = atomicAdd(&blk_n, 1u);
                     bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)bi);
-                    if (lane == 0) {
-                        if (bi < S.bigq) {
-                            blk_docs[bi] = (uint32_t)dd;
-                        } else {
-                            S.dflags[dd] = dflags | DH_RESOLVE;
-                            const uint32_t i = atomicAdd(S.res_cnt, 1u);
-                            if (i < S.defer_cap) S.res_list[i] = (uint32_t)dd;
-                        }
+                    if (lane == 0) {   // (one lane-0 block for either queue)
+                        if (bi < S.bigq) blk_docs[bi] = (uint32_t)dd;
+                        else epi_to_resolve(S, dd, dflags);
                     }
                     continue;
                 }
                 defer = true;
-                ++ndef_items;
+                ++C.ndef_items;
                 if (lane == 0) atomicAdd(&S.stats[14], 1ull);
             }
             const uint32_t fl2 = dflags & ~DH_DEFER;
@@ -1830,20 +1777,16 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
                 wave_sync();
                 if (!fk_scan_epilogue(FT, S, GS, D, items, n0, n1, fl2, wave, O, TC)) {
                     defer = true;
-                    ++ndef_items;
+                    ++C.ndef_items;
                     if (lane == 0) atomicAdd(&S.stats[13], 1ull);
                 }
             }
             uint2 h;
             h.x = ibeg;
             if (defer) {
-                ++ndefer;
+                ++C.ndefer;
                 h.y = DH_DEFER;
-                if (lane == 0) {
-                    const uint32_t i = atomicAdd(S.defer_cnt, 1u);
-                    if (i < S.defer_cap) S.defer_list[i] = (uint32_t)dd;
-                    else atomicOr(&S.status[0], ST_ITEM_OVERFLOW);
-                }
+                epi_to_generic(S, dd);
             } else {
                 h.y = n0 | (n1 << DH_N1_SHIFT) | fl2;
                 if (lane == 0) S.vrec[dd] = make_uint4((uint32_t)D.t0, (uint32_t)((uint64_t)D.t0 >> 32), (uint32_t)(D.t1 - D.t0), (uint32_t)(D.t2 - D.t1));
@@ -1854,39 +1797,18 @@ __global__ __launch_bounds__(EK_BLOCK, EK_MINW) void kw_epi_flat_kernel(FastTabl
     }
     // the workgroup's big documents: wave 0 with the whole workgroup's LDS as one 4096 + 512-item buffer
     __syncthreads();
-#if defined(EK_TIMING_SKIP_BIG)   // (timing variant only, results void: the big documents are not finished)
-    const uint32_t nb = 0;
-#else
     const uint32_t nb = min(blk_n, S.bigq);
-#endif
     if (wib == 0 && nb) {
         for (uint32_t i = 0; i < nb; ++i) {
             const uint32_t r = epi_big_doc(FT, S, GS, arena, off, blk_docs[i], items_all, wave, O, TC);
-            ndefer += r & 1u;
-            ndef_items += (r >> 3) & 1u;
-            ntx += (r >> 1) & 1u;
-            nres += (r >> 2) & 1u;
+            C.ndefer += r & 1u;
+            C.ndef_items += (r >> 3) & 1u;
+            C.ntx += (r >> 1) & 1u;
+            C.nres += (r >> 2) & 1u;
         }
         if (lane == 0) atomicAdd(&S.stats[16], (unsigned long long)nb);
     }
-    if (lane == 0) {
-        S.kout_cnt[wave] = O.n;
-        S.vcnt[wave] = TC.v;
-        if (TC.e) atomicAdd(&S.stats[7], (unsigned long long)TC.e);
-        S.scnt[wave] = TC.s;
-        S.xcnt[wave] = TC.x;
-        S.xmark[wave] = TC.x;   // (the regex tasks the epilogue queued: KW_RX_SPLIT's early phase)
-        if (TC.v > S.vcap || TC.s > S.scap || TC.x > S.xcap) {
-            atomicOr(&S.status[0], ST_TASK_OVERFLOW);
-            atomicMax(&S.tmax[0], TC.v);
-            atomicMax(&S.tmax[2], TC.s);
-            atomicMax(&S.tmax[3], TC.x);
-        }
-        atomicAdd(&S.stats[4], (unsigned long long)ndefer);
-        atomicAdd(&S.stats[5], (unsigned long long)ndef_items);
-        if (ntx) atomicAdd(&S.stats[18], (unsigned long long)ntx);
-        if (nres) atomicAdd(&S.stats[19], (unsigned long long)nres);
-    }
+    epi_wave_close(S, wave, O.n, TC, C);
 }
 
 }  // namespace kw

@@ -1,3 +1,4 @@
+// Build: hipcc --offload-arch=gfx950 -O2 -o scripts/probe/lds_unaligned scripts/probe/lds_unaligned.hip
 // Does LDS run in unaligned mode on this box: ds_read_b32 / b64 / b128 and ds_write_b128 at byte addresses that are
 // not multiples of their size.  Development probe, not part of the product.
 #include <hip/hip_runtime.h>
