@@ -51,7 +51,8 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_csv_append', 'kw_cdx_run_exclude', 'kw_cdx_exclude_codes', 'kw_cdx_exclude_counts',
            'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms',
            'kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_last_error',
-           'kw_rows_destroy')
+           'kw_rows_destroy',
+           'kw_rows_cells', 'kw_rows_emit', 'kw_rows_emit_result', 'kw_rows_copy_index', 'kw_rows_emit_last_ms')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -71,6 +72,7 @@ KW_URL_SEEN = 5   # a link row of kw_cdx_run_exclude whose string is among the e
  KW_CSV_URL) = range(9)
 KW_DEDUP_NORMALIZE = 1
 KW_ROWS_OK, KW_ROWS_INVALID_REGEX = 0, 1   # verdicts of kw_rows_run (include/kwrows.h)
+KW_EMIT_OK, KW_EMIT_NUL = 0, 1             # verdicts of kw_rows_emit (include/kwrows.h)
 KW_N_STATS = 21
 # KW_RESCAN_* bits of stats[20] (include/kwmatch.h)
 KW_RESCAN_GENERIC_ITEMS, KW_RESCAN_RESULTS, KW_RESCAN_GENERIC_CPS = 1, 2, 4
@@ -142,7 +144,13 @@ def lib() -> ctypes.CDLL:
     L.kw_rows_copy.argtypes = [vp, vp, vp, vp, vp]
     L.kw_rows_last_ms.argtypes = [vp, vp, i32]
     L.kw_rows_destroy.argtypes = [vp]
-    for f in ('kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_destroy'):
+    L.kw_rows_cells.argtypes = [vp, vp, vp, vp, i64, i32, vp]
+    L.kw_rows_emit.argtypes = [vp, vp, vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i32), vp]
+    L.kw_rows_emit_result.argtypes = [vp] + [ctypes.POINTER(vp)] * 6
+    L.kw_rows_copy_index.argtypes = [vp, vp, vp]
+    L.kw_rows_emit_last_ms.argtypes = [vp, vp, i32]
+    for f in ('kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_destroy', 'kw_rows_cells',
+              'kw_rows_emit', 'kw_rows_emit_result', 'kw_rows_copy_index', 'kw_rows_emit_last_ms'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_rows_last_error.argtypes = [vp]
     L.kw_rows_last_error.restype = ctypes.c_char_p

@@ -1,6 +1,7 @@
 // libkwmatch: the per-ticker match cells built on the device (include/kwrows.h) -- the reference's per-article
 // assembly (match_keywords.py:159-187) and json.dumps of the two dicts (:137-138), from hit records that are
 // already in HBM.  The host form of the same rules is csrc/kwrows.c; tests/rows_rule.py restates the stages.
+// csrc/kwemit.hip goes on from the rows to the finished CSV lines on the same handle (kwrows_handle.hpp).
 //
 // Stages of kw_rows_run (kernels exchange data only across launches; every size is found by a count pass and
 // an exclusive scan, the buffers belong to the handle and grow on demand):
@@ -28,24 +29,13 @@
 #include <vector>
 
 #include "../../include/kwrows.h"
+#include "kwrows_handle.hpp"
 
 namespace rw {
 
-constexpr int BLOCK = 256;
-constexpr int SCAN_CHUNKS = 512;
 constexpr uint32_t NOPOS = KW_NOPOS;
 // the run's counters (device, 64-bit words)
 enum { T_VALID = 0, T_ENTRIES = 1, T_INVALID = 2, T_BADPAT = 3, T_BYTES = 4, T_ROWS = 5, T_WORDS = 8 };
-
-struct Tables {
-    const int64_t *occ_off;
-    const int32_t *occ_ti, *occ_rank, *occ_prev;
-    const int64_t *occ_lo, *occ_hi;
-    const uint8_t *invalid;
-    const uint8_t *keys;
-    const int64_t *key_off;
-    uint32_t n_patterns;
-};
 
 // exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
 __device__ __forceinline__ unsigned long long block_scan(unsigned long long x, unsigned long long *ws,
@@ -359,41 +349,8 @@ __global__ __launch_bounds__(BLOCK) void rw_fill_kernel(const uint4 *__restrict_
     if (j + 1 == n_ent) out_off[2 * tot[T_ROWS]] = (int64_t)(w - out);
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
-}  // namespace rw
-
-struct kw_rows {
-    int device = 0;
-    std::string err;
-    rw::Tables T{};
-    void *d_tables = nullptr;          // one allocation holding every table
-    int64_t n_occ = 0;
-    int32_t n_patterns = 0, n_tickers = 0;
-    rw::Buf date_us, date_ok, doc_off, cursor, tmp, rec, ecnt, ent_raw, ent, len, head, json, json_off, row_doc, row_ti;
-    unsigned long long *tot = nullptr, *chunk = nullptr;
-    int64_t n_rows = 0, n_bytes = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    float ms[4] = {0, 0, 0, 0};
-    bool have_run = false;
-};
-
-#define RWCHK(h, x)                                                                    \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            (h)->err = std::string("HIP error ") + hipGetErrorString(e_) + " at " #x; \
-            return KW_EHIP;                                                            \
-        }                                                                              \
-    } while (0)
-
-namespace rw {
-
 // a buffer of at least `bytes` (contents are not kept when it grows)
-static int ensure(kw_rows *h, Buf &b, size_t bytes)
+int ensure(kw_rows *h, Buf &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p) return KW_OK;
     const size_t want = std::max<size_t>(256, bytes + bytes / 4);
@@ -406,8 +363,8 @@ static int ensure(kw_rows *h, Buf &b, size_t bytes)
 }
 
 // exclusive scan of a[0, m) in place; *d_grand (device) receives the total.  chunk: SCAN_CHUNKS words of scratch
-static void scan_launch(unsigned long long *a, int64_t m, unsigned long long *chunk, unsigned long long *d_grand,
-                        hipStream_t st)
+void scan_launch(unsigned long long *a, int64_t m, unsigned long long *chunk, unsigned long long *d_grand,
+                 hipStream_t st)
 {
     const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(SCAN_CHUNKS, (m + 4 * BLOCK - 1) / (4 * BLOCK)));
     const int64_t per = std::max<int64_t>(1, (m + nchunk - 1) / nchunk);
@@ -511,12 +468,14 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
     if ((uintptr_t)d_hits & 15) { h->err = "kw_rows_run: d_hits must be 16-byte aligned"; return KW_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     h->have_run = false;
+    h->run_rows = false;
+    h->run_docs = n_docs;
     h->n_rows = h->n_bytes = 0;
     *n_rows = *n_bytes = 0;
     *verdict = KW_ROWS_OK;
     for (auto &m : h->ms) m = 0.f;
     if (n_hits == 0 || n_docs == 0) {
-        h->have_run = true;
+        h->have_run = h->run_rows = true;
         return KW_OK;
     }
     RWCHK(h, hipSetDevice(h->device));
@@ -568,7 +527,7 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
     const u64 n_ent = tot[T_ENTRIES];
     if (n_ent >= 1ull << 31) { h->err = "kw_rows_run: 2^31 entries or more"; return KW_EOVERFLOW; }
     if (n_ent == 0) {
-        h->have_run = true;
+        h->have_run = h->run_rows = true;
         return KW_OK;
     }
     if ((rc = ensure(h, h->ent_raw, (size_t)n_ent * 32)) || (rc = ensure(h, h->ent, (size_t)n_ent * 32)) ||
@@ -602,7 +561,7 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
     RWCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[3]));
     h->n_rows = *n_rows = (int64_t)nr;
     h->n_bytes = *n_bytes = (int64_t)nb;
-    h->have_run = true;
+    h->have_run = h->run_rows = true;
     return KW_OK;
 }
 
@@ -640,6 +599,7 @@ extern "C" int kw_rows_destroy(kw_rows *h)
 {
     if (!h) return KW_OK;
     (void)hipSetDevice(h->device);
+    rw::emit_destroy(h);
     rw::Buf *bufs[] = {&h->date_us, &h->date_ok, &h->doc_off, &h->cursor, &h->tmp, &h->rec, &h->ecnt, &h->ent_raw,
                        &h->ent, &h->len, &h->head, &h->json, &h->json_off, &h->row_doc, &h->row_ti};
     for (rw::Buf *b : bufs)

@@ -343,6 +343,29 @@ def render_native(chunk, raw_rows, stamps_by_doc, tickers):
              flags[a:b], rd[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
 
+def render_device(chunk, matcher, stamps_by_doc, n_rows_use: int):
+    """:func:`render_native`'s list of 6-tuples for the first ``n_rows_use`` rows of ``matcher``'s last
+    ``rows_device``, rendered on the GPU from the chunk's tokenized cells and the JSON cells still in device
+    memory (csrc/kwemit.hip, ``kw_rows_emit``): the line bytes are memoryviews over the handle's pinned host
+    buffer, valid until the next call.  ``None`` as :func:`render_native` (a NUL cell, a platform line end
+    other than "\n"); a library error raises ``KwError``."""
+    if n_rows_use == 0:
+        return []
+    if not (_FAST_OK and _NL_ONLY):
+        return None
+    cols = np.asarray([chunk.col[k] for k in ('date_time', 'title', 'url', 'source', 'source_url', 'article_text')],
+                      dtype=np.int32)
+    got = matcher.rows_emit(chunk.cells, cols, stamps_by_doc, int(n_rows_use))
+    if got is None:
+        return None
+    lines, line_off, flags, rd, ti, rs = got
+    tickers = matcher.ckb.tickers
+    lens = np.diff(line_off)
+    cuts = np.flatnonzero(np.r_[True, ti[1:] != ti[:-1], True]).tolist()
+    return [(f'{tickers[ti[a]]}_match.csv', lines[line_off[a]:line_off[b]], rs[a:b], lens[a:b], flags[a:b], rd[a:b])
+            for a, b in zip(cuts[:-1], cuts[1:])]
+
+
 def header_bytes() -> bytes:
     return _join(list(_HEADER_COLUMNS)).encode('utf-8')
 

@@ -36,7 +36,7 @@ from .ingest import NativeChunk, ShardChunk
 from .dates import parse_date
 from .kb import (ATTRIBUTES, compile_kb, extract_time_periods, is_within_period,  # noqa: F401 (re-export)
                  process_json_data, read_and_process_json_files)
-from .rows import assemble_json_device, assemble_json_raw, assemble_json_rows
+from .rows import assemble_json_device, assemble_json_raw, assemble_json_rows, emit_on_device
 from .matcher import (GpuMatcher, assemble_ticker_matches, background_sample, field_str, group_hits,  # noqa: F401
                       pack_fields, records_from_tensor, resolve_host_positions)
 
@@ -312,13 +312,30 @@ def _json_raw(matcher, hits, dates):
     return assemble_json_raw(matcher.ckb, hits, dates)
 
 
-def _native_rows(chunk, matcher, hits, dates, error):
+def _emit_on_device(matcher, hits, dates) -> bool:
+    """The chunk's CSV lines can be rendered on the device (egress.render_device): the JSON cells are built there
+    (:func:`_rows_on_device`), the emitter's QUOTE_MINIMAL rule is this interpreter's csv writer's, and
+    ``KW_EMIT_DEVICE`` asks for it (rows.emit_on_device)."""
+    return emit_on_device() and egress._FAST_OK and egress._NL_ONLY and _rows_on_device(matcher, hits, dates)
+
+
+def _native_rows(chunk, matcher, hits, dates, error, device_emit: bool = True):
     """The rows of a native chunk rendered in C (egress.render_native: JSON cells from :func:`_json_raw`,
-    the other cells straight from the tokenized chunk), up to its first failing article, with that article's
-    exception and row (as :func:`_hit_rows`); ``None`` when only the Python path can answer."""
+    the other cells straight from the tokenized chunk) or, where :func:`_emit_on_device` holds, on the device
+    (egress.render_device: the JSON text stays there; ``device_emit=False`` keeps the host emitter), up to its
+    first failing article, with that article's exception and row (as :func:`_hit_rows`); ``None`` when only
+    the Python path can answer."""
     if not isinstance(chunk, NativeChunk) or hits is None:
         return None
-    raw = _json_raw(matcher, hits, dates)
+    on_device = device_emit and _emit_on_device(matcher, hits, dates)
+    if on_device:
+        matcher.rows_copy_json = False
+        try:
+            raw = assemble_json_device(matcher, dates)    # the row index alone
+        finally:
+            matcher.rows_copy_json = True
+    else:
+        raw = _json_raw(matcher, hits, dates)
     if raw is None:
         return None
     row_doc = raw[0]
@@ -338,10 +355,15 @@ def _native_rows(chunk, matcher, hits, dates, error):
             except Exception as e:   # noqa: BLE001 - that article's append raises in the reference
                 exc, row = e, d
                 break
+    k = len(row_doc)
     if exc is not None:
         k = int(np.searchsorted(row_doc, row))   # rows are in document order
-        raw = (raw[0][:k], raw[1][:k], raw[2], raw[3][:2 * k + 1])
-    rendered = egress.render_native(chunk, raw, stamps, matcher.ckb.tickers)
+    if on_device:
+        rendered = egress.render_device(chunk, matcher, stamps, k)
+    else:
+        if exc is not None:
+            raw = (raw[0][:k], raw[1][:k], raw[2], raw[3][:2 * k + 1])
+        rendered = egress.render_native(chunk, raw, stamps, matcher.ckb.tickers)
     if rendered is None:
         return None
     if exc is None and error is not None:
@@ -478,7 +500,7 @@ def _write_shard(source_name, chunk: ShardChunk, processed_data, matcher, exchan
         d_arena, d_off = matcher.upload(arena, off[:2 * n_ok + 1])
         matcher.scan(d_arena, d_off, n_ok)
         hits = _host_positions(chunk, matcher, matcher.fetch())
-    nat = _native_rows(chunk, matcher, hits, dates, error)
+    nat = _native_rows(chunk, matcher, hits, dates, error, device_emit=False)   # (the sharded route: host emitter)
     if nat is not None:
         rendered, exc, row = nat
         by_ticker = None

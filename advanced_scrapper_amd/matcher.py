@@ -95,6 +95,7 @@ class GpuMatcher:
         self.h = h
         self._keep = None
         self._rows = None         # rows.DeviceRows of this KB, made on first use
+        self.rows_copy_json = True  # rows_device copies the JSON text to the host (False: it stays for rows_emit)
         self._fetched = None      # the array the last fetch_host() / fetch() returned
 
     @property
@@ -248,7 +249,14 @@ class GpuMatcher:
         n = ctypes.c_int64()
         p = ctypes.c_void_p()
         _native.check(_native.lib().kw_hits(self.h, ctypes.byref(n), ctypes.byref(p)), self.h)
-        return handle.run(p, int(n.value), date_us, date_ok)
+        return handle.run(p, int(n.value), date_us, date_ok, copy_json=self.rows_copy_json)
+
+    def rows_emit(self, cells, cols, stamp_by_doc: np.ndarray, n_rows_use: int):
+        """The first ``n_rows_use`` rows of the last :meth:`rows_device` as CSV lines rendered on the device from
+        the chunk's tokenized ``cells`` (rows.DeviceRows.cells + emit; ``None`` on the verdict KW_EMIT_NUL)."""
+        handle = self.rows_handle()
+        handle.cells(cells, handle.n_docs)
+        return handle.emit(cols, np.asarray(stamp_by_doc, dtype=np.int64)[:handle.n_docs], n_rows_use)
 
     def match_device(self, texts: Sequence[str], titles: Sequence[str]):
         """Pack, upload and scan; the records as a device tensor [n, 4] (int32 view of kw_hit)."""

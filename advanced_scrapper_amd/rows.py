@@ -9,7 +9,8 @@ the Python path can answer: a date or period bound without a UTC offset, or an i
 does not compile (the Python path raises the reference's ``re.error``).
 
 ``assemble_json_device`` builds the same arrays on the GPU from the records the scan left in HBM
-(csrc/kwrows.hip, include/kwrows.h); the host route above stays the fallback.
+(csrc/kwrows.hip, include/kwrows.h); the host route above stays the fallback.  ``DeviceRows.cells`` + ``emit``
+go on from there to the finished CSV lines (csrc/kwemit.hip) without the JSON text reaching the host.
 """
 from __future__ import annotations
 
@@ -127,6 +128,16 @@ def assemble_json_device(matcher, dates: Sequence):
     return matcher.rows_device(prepared[0], prepared[1])
 
 
+def emit_on_device() -> bool:
+    """The CSV lines are rendered on the device where that route applies (match_keywords._native_rows):
+    the default, ``KW_EMIT_DEVICE=0`` keeps the host emitter (profiles/e2e_emit.json holds the measurement
+    behind the default)."""
+    return os.environ.get('KW_EMIT_DEVICE', EMIT_DEVICE_DEFAULT) != '0'
+
+
+EMIT_DEVICE_DEFAULT = '1'
+
+
 class DeviceRows:
     """One KB's occurrence tables on one GPU (a ``kw_rows`` handle, include/kwrows.h)."""
 
@@ -143,15 +154,17 @@ class DeviceRows:
                 L.kw_rows_destroy(h)
             raise _native.KwError(rc, msg.decode() if msg else '')
         self.h = h
+        self.n_docs = self.n_rows = 0      # of the last run
 
     def _check(self, rc: int) -> None:
         if rc != _native.KW_OK:
             msg = _native.lib().kw_rows_last_error(self.h)
             raise _native.KwError(rc, msg.decode('utf-8', 'replace') if msg else '')
 
-    def run(self, d_hits, n_hits: int, date_us: np.ndarray, date_ok: np.ndarray, stream=None):
+    def run(self, d_hits, n_hits: int, date_us: np.ndarray, date_ok: np.ndarray, stream=None, copy_json: bool = True):
         """The four arrays of :func:`assemble_json_raw` for ``n_hits`` device records at ``d_hits`` (a raw
-        pointer, or a tensor), or ``None`` on the verdict KW_ROWS_INVALID_REGEX."""
+        pointer, or a tensor), or ``None`` on the verdict KW_ROWS_INVALID_REGEX.  ``copy_json=False`` leaves the
+        JSON text on the device (for :meth:`emit`): ``(row_doc, row_ti, None, None)``."""
         date_us = np.ascontiguousarray(date_us, dtype=np.int64)
         date_ok = np.ascontiguousarray(date_ok, dtype=np.uint8)
         if len(date_ok) != len(date_us):
@@ -162,15 +175,69 @@ class DeviceRows:
         L = _native.lib()
         self._check(L.kw_rows_run(self.h, d_hits, int(n_hits), _ptr(date_us), _ptr(date_ok), len(date_us),
                                   ctypes.byref(n_rows), ctypes.byref(n_bytes), ctypes.byref(verdict), stream))
+        self.n_docs, self.n_rows = len(date_us), int(n_rows.value)
         if verdict.value == _native.KW_ROWS_INVALID_REGEX:
             return None
         n = int(n_rows.value)
         row_doc = np.empty(n, dtype=np.int32)
         row_ti = np.empty(n, dtype=np.int32)
+        if not copy_json:
+            self._check(L.kw_rows_copy_index(self.h, _ptr(row_doc), _ptr(row_ti)))
+            return row_doc, row_ti, None, None
         out = np.empty(int(n_bytes.value), dtype=np.uint8)
         out_off = np.empty(2 * n + 1, dtype=np.int64)
         self._check(L.kw_rows_copy(self.h, _ptr(row_doc), _ptr(row_ti), _ptr(out), _ptr(out_off)))
         return row_doc, row_ti, out, out_off
+
+    def cells(self, cells, n_docs: Optional[int] = None, stream=None) -> None:
+        """Upload the tokenized cells (an ``ingest.Cells``: ``buf`` / ``off`` / ``flags`` / ``nrows`` / ``ncols``) of
+        the chunk's first ``n_docs`` rows (all by default) for :meth:`emit`."""
+        n = cells.nrows if n_docs is None else int(n_docs)
+        if not 0 <= n <= cells.nrows:
+            raise ValueError('n_docs outside the cells')
+        nc = n * cells.ncols
+        buf = np.ascontiguousarray(cells.buf, dtype=np.uint8)
+        off = np.ascontiguousarray(cells.off[:nc + 1], dtype=np.int64)
+        fl = np.ascontiguousarray(cells.flags[:nc], dtype=np.uint8)
+        if len(off) != nc + 1 or len(fl) != nc or (nc and len(buf) < off[nc]):
+            raise ValueError('the cells are shorter than their offsets say')
+        self._check(_native.lib().kw_rows_cells(self.h, _ptr(buf), _ptr(off), _ptr(fl), n, int(cells.ncols), stream))
+
+    def emit(self, cols, stamp_by_doc: np.ndarray, n_rows_use: int, stream=None):
+        """The first ``n_rows_use`` rows of the last :meth:`run` as CSV lines, rendered on the device from the cells
+        of :meth:`cells` (``cols``: their columns of date_time, title, url, source, source_url, article_text;
+        ``stamp_by_doc[d]`` = article d's time_unix), in the stable order by KB ticker index: ``(lines, line_off
+        int64[n + 1], flags uint32[n], row_doc int32[n], row_ti int32[n], stamps int64[n])``, or ``None`` on the
+        verdict KW_EMIT_NUL.  ``lines`` is a memoryview over the handle's pinned buffer, valid until the next
+        emit; the arrays are copies."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if cols.shape != (6,):
+            raise ValueError('cols: six column indexes')
+        stamps = np.ascontiguousarray(stamp_by_doc, dtype=np.int64)
+        nb, verdict = ctypes.c_int64(), ctypes.c_int32()
+        L = _native.lib()
+        self._check(L.kw_rows_emit(self.h, _ptr(cols), _ptr(stamps), len(stamps), int(n_rows_use), ctypes.byref(nb),
+                                   ctypes.byref(verdict), stream))
+        if verdict.value == _native.KW_EMIT_NUL:
+            return None
+        p = [ctypes.c_void_p() for _ in range(6)]
+        self._check(L.kw_rows_emit_result(self.h, *[ctypes.byref(x) for x in p]))
+        n = int(n_rows_use)
+
+        def arr(ptr, count, dtype):
+            if count == 0:
+                return np.zeros(0, dtype=dtype)
+            raw = (ctypes.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(ptr.value)
+            return np.frombuffer(raw, dtype=dtype).copy()
+        lines = memoryview((ctypes.c_uint8 * int(nb.value)).from_address(p[0].value)).cast('B') if nb.value else memoryview(b'')
+        return (lines, arr(p[1], n + 1, np.int64), arr(p[2], n, np.uint32), arr(p[3], n, np.int32),
+                arr(p[4], n, np.int32), arr(p[5], n, np.int64))
+
+    def emit_last_ms(self):
+        """Device times (ms) of the last emit: order, measure, fill, copy (to the pinned host buffers)."""
+        v = np.zeros(4, dtype=np.float32)
+        self._check(_native.lib().kw_rows_emit_last_ms(self.h, _ptr(v), 4))
+        return dict(zip(('order', 'measure', 'fill', 'copy'), (float(x) for x in v)))
 
     def last_ms(self):
         """Device times (ms) of the last run: order, expand, render, total."""

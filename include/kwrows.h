@@ -17,6 +17,18 @@
  * adds no number (a group of only such records prints "[]").  Documents with
  * date_ok == 0 and records with doc >= n_docs give nothing.
  *
+ * The CSV rows.  kw_rows_cells + kw_rows_emit go on from there to the finished lines of the per-ticker files
+ * (the reference's append_to_csv, match_keywords.py:128-146) without the JSON text reaching the host: the rows
+ * in the stable order by KB ticker index (article order kept within a ticker), each
+ *     decimal(time_unix),date_time,text_matches,title_matches,title,url,source,source_url,article_text\n
+ * byte for byte what kwcsv_emit_mt (csrc/kwcsv.c) writes: every cell in the csv writer's QUOTE_MINIMAL form
+ * (wrapped in '"' iff it is non-empty and holds ',', '"' or '\n', every '"' inside then doubled; a lone '\r' does
+ * not quote), an NA cell (flag bit 2 of the tokenized cells) empty whatever its bytes are, the stamp a signed
+ * decimal int64.  Per row a uint32 of flags: bit c (c = 0 date_time, 3..7 title .. article_text) = that cell is a
+ * text witness (not NA, and no number or bool literal: blanks only, or a byte other than 0-9 + - . e E, and
+ * not true / false / [+-]inf / [+-]infinity in any case, blanks at both ends dropped); bits 1 and 2 always set
+ * (the JSON cells); bit 8 + c = that cell is NA; bit 16 = a written cell holds '\r'.
+ *
  * Conventions as kwmatch.h: 0 or a negative KW_E* code; kw_rows_last_error gives
  * the message; one handle per device and host thread.
  */
@@ -65,6 +77,41 @@ int kw_rows_copy(kw_rows *r, int32_t *row_doc, int32_t *row_ti, uint8_t *json, i
 /* Device times (ms) of the last run, up to 4 values: [0] order (count, scan, scatter and sort of the
  * records), [1] expand (groups -> entries and their order), [2] render (byte lengths, scans, fill), [3] all. */
 int kw_rows_last_ms(kw_rows *r, float *ms, int32_t n);
+
+/* The last run's row index alone: row_doc[n_rows], row_ti[n_rows] (what kw_rows_copy gives, without the text). */
+int kw_rows_copy_index(kw_rows *r, int32_t *row_doc, int32_t *row_ti);
+
+/* verdicts of kw_rows_emit */
+#define KW_EMIT_OK 0
+#define KW_EMIT_NUL 1   /* a NUL byte in a non-NA cell of an article that has a rendered row (or in a JSON cell):
+                           no output; the csv writer raises there, the caller takes its per-row path */
+
+/* Upload one chunk's tokenized cells (host arrays, copied before the call returns; device buffers kept across
+ * chunks): cell c of document d is cells[coff[d * ncols + c], coff[d * ncols + c + 1]) with flags
+ * cfl[d * ncols + c]; coff has n_docs * ncols + 1 non-decreasing entries from coff[0] >= 0 (KW_EINVAL
+ * otherwise).  Before or after kw_rows_run. */
+int kw_rows_cells(kw_rows *r, const uint8_t *cells, const int64_t *coff, const uint8_t *cfl, int64_t n_docs,
+                  int32_t ncols, void *stream);
+
+/* Render the first n_rows_use rows (in kw_rows_run's document order: any prefix, 0 included) of the last run.
+ * cols[6]: the cells' columns of date_time, title, url, source, source_url, article_text; stamp_by_doc: host
+ * int64[n_docs], each document's time_unix.  Returns after the lines are in the handle's pinned host buffers:
+ * *n_out_bytes of them (0 when *verdict is KW_EMIT_NUL).  KW_EINVAL, before anything is launched: a null
+ * pointer, a column outside [0, ncols), n_rows_use outside [0, n_rows].  KW_ESTATE: no kw_rows_run that
+ * succeeded with KW_ROWS_OK, no kw_rows_cells, or their n_docs differ from this one. */
+int kw_rows_emit(kw_rows *r, const int32_t *cols, const int64_t *stamp_by_doc, int64_t n_docs, int64_t n_rows_use,
+                 int64_t *n_out_bytes, int32_t *verdict, void *stream);
+
+/* The last emit's result in pinned host memory owned by the handle, valid until the next kw_rows_emit or
+ * kw_rows_destroy: n = n_rows_use rows (0 after KW_EMIT_NUL) in output order; row i's line is
+ * out[line_off[i], line_off[i + 1]) (line_off[0] = 0 always), flags[i] as above, row_doc / row_ti / stamps[i] its
+ * document, KB ticker index and time_unix. */
+int kw_rows_emit_result(kw_rows *r, const uint8_t **out, const int64_t **line_off, const uint32_t **flags,
+                        const int32_t **row_doc, const int32_t **row_ti, const int64_t **stamps);
+
+/* Device times (ms) of the last emit, up to 4 values: [0] order (the rows by ticker), [1] measure (cell and line
+ * lengths, flags, scans), [2] fill (cells into scratch, lines), [3] the copy to the pinned buffers. */
+int kw_rows_emit_last_ms(kw_rows *r, float *ms, int32_t n);
 
 const char *kw_rows_last_error(kw_rows *r);
 int kw_rows_destroy(kw_rows *r);

@@ -17,6 +17,11 @@ fresh child process per run (one warm-up, then the median of 5), on this tree wi
 ``--parent-tree DIR`` (a built checkout of the parent commit), on that tree.  Every configuration must write the
 same bytes.  OUT.json gets the three medians, the device route's ``kw_rows_last_ms`` split summed over the
 chunks (order, expand, render) and the wall time either route spent building the cells.
+
+``--emit-ab OUT.json`` compares the routes of the CSV rows the same way: this tree with ``KW_EMIT_DEVICE=1`` (the
+lines rendered on the device, csrc/kwemit.hip), this tree with ``KW_EMIT_DEVICE=0`` (kwcsv_emit_mt on the host) and,
+with ``--parent-tree DIR``, that tree.  OUT.json gets the medians, the wall time inside either renderer, and the
+device route's per-chunk ``kw_rows_emit_last_ms`` (order, measure, fill, copy).
 """
 import argparse
 import contextlib
@@ -129,16 +134,65 @@ print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span
 '''
 
 
-def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs):
+EMIT_CHILD = r'''
+import contextlib, hashlib, io, json, os, sys, tempfile, time
+tree, info_dir, csv_path, chunksize = sys.argv[1:5]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import egress, match_keywords as mk
+span = {'device_s': 0.0, 'host_s': 0.0, 'device_calls': 0, 'host_calls': 0, 'emit_ms': [], 'bytes': 0}
+host = egress.render_native
+def timed_host(*a):
+    t = time.perf_counter()
+    out = host(*a)
+    span['host_s'] += time.perf_counter() - t
+    span['host_calls'] += 1
+    return out
+egress.render_native = timed_host
+device = getattr(egress, 'render_device', None)      # (the parent tree has none)
+if device is not None:
+    def timed_device(chunk, matcher, stamps, k):
+        t = time.perf_counter()
+        out = device(chunk, matcher, stamps, k)
+        span['device_s'] += time.perf_counter() - t
+        span['device_calls'] += 1
+        if k and out is not None:
+            span['emit_ms'].append({n: round(v, 3) for n, v in matcher.rows_handle().emit_last_ms().items()})
+            span['bytes'] += sum(len(r[1]) for r in out)
+        return out
+    egress.render_device = timed_device
+work = tempfile.mkdtemp(prefix='e2e_emit_')
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()):
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0
+h = hashlib.sha256()
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+import shutil
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
+def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS_CHILD):
     """main() in a fresh child per run on ``tree``: one warm-up, then ``runs`` timed runs."""
     import statistics
     import subprocess
     env = dict(os.environ)
     env.pop('KW_ROWS_DEVICE', None)
+    env.pop('KW_EMIT_DEVICE', None)
     env.update(env_extra)
     got = []
     for _ in range(runs + 1):
-        p = subprocess.run([sys.executable, '-c', ROWS_CHILD, tree, info_dir, csv_path, str(chunksize)], env=env,
+        p = subprocess.run([sys.executable, '-c', child, tree, info_dir, csv_path, str(chunksize)], env=env,
                            cwd=tree, capture_output=True, text=True, timeout=900)
         if p.returncode != 0:
             raise RuntimeError(f"child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
@@ -189,11 +243,49 @@ def rows_ab(args):
     assert res['same_bytes'], 'the configurations wrote different bytes'
 
 
+def emit_ab(args):
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=0)
+    csv_path = os.path.join(work, 'articles.csv')
+    synth.to_dataframe(corpus).to_csv(csv_path, index=False)
+    del corpus
+    res = {'docs': args.docs, 'chunksize': args.chunksize, 'csv_bytes': os.path.getsize(csv_path),
+           'runs_per_config': args.runs,
+           'timed': 'match_keywords.main() wall time in a fresh child per run; 1 warm-up + the median of the runs; '
+                    'cells: the median run\'s wall time inside the renderer of the CSV rows (host: egress.render_native '
+                    '= kwcsv_emit_mt; device: egress.render_device = kw_rows_cells + kw_rows_emit), the bytes the '
+                    'device route rendered and its per-chunk kw_rows_emit_last_ms (ms)'}
+    try:
+        res['device'] = rows_config(REPO, {'KW_EMIT_DEVICE': '1'}, info_dir, csv_path, args.chunksize, args.runs, EMIT_CHILD)
+        res['host'] = rows_config(REPO, {'KW_EMIT_DEVICE': '0'}, info_dir, csv_path, args.chunksize, args.runs, EMIT_CHILD)
+        if args.parent_tree:
+            res['parent'] = rows_config(os.path.abspath(args.parent_tree), {}, info_dir, csv_path, args.chunksize,
+                                        args.runs, EMIT_CHILD)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    assert res['device']['cells']['device_calls'] > 0 and res['device']['cells']['host_calls'] == 0
+    assert res['host']['cells']['device_calls'] == 0 and res['host']['cells']['host_calls'] > 0
+    res['same_bytes'] = len({res[k]['sha256'] for k in ('device', 'host', 'parent') if k in res}) == 1
+    res['device_faster'] = res['device']['median_s'] < res['host']['median_s']
+    with open(args.emit_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['same_bytes'], 'the configurations wrote different bytes'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--emit-ab', metavar='OUT.json', help='compare the CSV rows\' routes (see the module doc)')
     ap.add_argument('--rows-ab', metavar='OUT.json', help='compare the JSON cells\' routes (see the module doc)')
-    ap.add_argument('--parent-tree', help='--rows-ab: a built checkout of the parent commit')
-    ap.add_argument('--runs', type=int, default=5, help='--rows-ab: timed runs per configuration')
+    ap.add_argument('--parent-tree', help='--rows-ab / --emit-ab: a built checkout of the parent commit')
+    ap.add_argument('--runs', type=int, default=5, help='--rows-ab / --emit-ab: timed runs per configuration')
     ap.add_argument('--docs', type=int, default=200000)
     ap.add_argument('--chunksize', type=int, default=20000)
     ap.add_argument('--profile', action='store_true', help='cProfile main() (top functions by cumulative time)')
@@ -203,6 +295,9 @@ def main():
     if args.rows_ab:
         args.rows_ab = os.path.abspath(args.rows_ab)
         return rows_ab(args)
+    if args.emit_ab:
+        args.emit_ab = os.path.abspath(args.emit_ab)
+        return emit_ab(args)
     import bench
     from advanced_scrapper_amd import ingest, match_keywords as mk, synth
     from advanced_scrapper_amd.kb import compile_kb
