@@ -37,7 +37,7 @@ KW_NOPOS = 0xFFFFFFFF
 
 HIT_DTYPE = np.dtype([('doc', '<u4'), ('pattern', '<u4'), ('pos', '<u4'), ('field', '<u4')])
 
-# every symbol include/kwmatch.h, include/kwdedup.h and include/kwrows.h declare
+# every symbol include/kwmatch.h, include/kwdedup.h, include/kwrows.h and include/kwingest.h declare
 EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_last_kernel_ms',
            'kw_last_kernel_times', 'kw_doc_routes', 'kw_last_error', 'kw_destroy',
            'kw_scan_host', 'kw_hits_host', 'kw_device_count', 'kw_device_init',
@@ -52,7 +52,13 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms',
            'kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_last_error',
            'kw_rows_destroy',
-           'kw_rows_cells', 'kw_rows_emit', 'kw_rows_emit_result', 'kw_rows_copy_index', 'kw_rows_emit_last_ms')
+           'kw_rows_cells', 'kw_rows_emit', 'kw_rows_emit_result', 'kw_rows_copy_index', 'kw_rows_emit_last_ms',
+           'kw_rows_cells_device',
+           'kw_ingest_create', 'kw_ingest_destroy', 'kw_ingest_last_error', 'kw_ingest_last_ms',
+           'kw_ingest_tile_bytes', 'kw_ingest_parse', 'kw_ingest_cells', 'kw_ingest_arena', 'kw_ingest_dates',
+           'kw_ingest_column_flags', 'kw_ingest_copy_cells', 'kw_ingest_copy_column', 'kw_ingest_stage',
+           'kw_ingest_copy_arena',
+           'kw_ingest_upload')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -73,6 +79,9 @@ KW_URL_SEEN = 5   # a link row of kw_cdx_run_exclude whose string is among the e
 KW_DEDUP_NORMALIZE = 1
 KW_ROWS_OK, KW_ROWS_INVALID_REGEX = 0, 1   # verdicts of kw_rows_run (include/kwrows.h)
 KW_EMIT_OK, KW_EMIT_NUL = 0, 1             # verdicts of kw_rows_emit (include/kwrows.h)
+# KW_INGEST_* verdicts of kw_ingest_parse (include/kwingest.h), in the order they are tested
+(KW_INGEST_OK, KW_INGEST_NUL, KW_INGEST_UTF8, KW_INGEST_QUOTE, KW_INGEST_CR, KW_INGEST_BLANK, KW_INGEST_FIELDS,
+ KW_INGEST_ROWS) = range(8)
 KW_N_STATS = 21
 # KW_RESCAN_* bits of stats[20] (include/kwmatch.h)
 KW_RESCAN_GENERIC_ITEMS, KW_RESCAN_RESULTS, KW_RESCAN_GENERIC_CPS = 1, 2, 4
@@ -152,6 +161,29 @@ def lib() -> ctypes.CDLL:
     for f in ('kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_destroy', 'kw_rows_cells',
               'kw_rows_emit', 'kw_rows_emit_result', 'kw_rows_copy_index', 'kw_rows_emit_last_ms'):
         getattr(L, f).restype = ctypes.c_int
+    L.kw_rows_cells_device.argtypes = [vp, vp, vp, vp, i64, i32, vp]
+    L.kw_rows_cells_device.restype = ctypes.c_int
+    L.kw_ingest_create.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(vp)]
+    L.kw_ingest_destroy.argtypes = [vp]
+    L.kw_ingest_last_ms.argtypes = [vp, vp, i32]
+    L.kw_ingest_tile_bytes.argtypes = []
+    L.kw_ingest_parse.argtypes = [vp, vp, i64, i32, i64, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                  ctypes.POINTER(i64), vp]
+    L.kw_ingest_cells.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.kw_ingest_arena.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.kw_ingest_dates.argtypes = [vp, vp, vp]
+    L.kw_ingest_column_flags.argtypes = [vp, vp]
+    L.kw_ingest_copy_cells.argtypes = [vp, vp, vp, vp]
+    L.kw_ingest_copy_column.argtypes = [vp, i32, vp, i64, vp, vp]
+    L.kw_ingest_stage.argtypes = [vp, i32, i64, ctypes.POINTER(vp)]
+    L.kw_ingest_upload.argtypes = [vp, i32, i64, i64, ctypes.POINTER(vp), vp]
+    L.kw_ingest_copy_arena.argtypes = [vp, vp, vp]
+    for f in ('kw_ingest_create', 'kw_ingest_destroy', 'kw_ingest_last_ms', 'kw_ingest_tile_bytes', 'kw_ingest_parse',
+              'kw_ingest_stage', 'kw_ingest_upload', 'kw_ingest_cells', 'kw_ingest_arena', 'kw_ingest_dates',
+              'kw_ingest_column_flags', 'kw_ingest_copy_cells', 'kw_ingest_copy_arena', 'kw_ingest_copy_column'):
+        getattr(L, f).restype = ctypes.c_int
+    L.kw_ingest_last_error.argtypes = [vp]
+    L.kw_ingest_last_error.restype = ctypes.c_char_p
     L.kw_rows_last_error.argtypes = [vp]
     L.kw_rows_last_error.restype = ctypes.c_char_p
     L.kw_compile.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)]

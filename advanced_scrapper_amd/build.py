@@ -45,6 +45,7 @@ def _kw_sources():
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.hpp')))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwmatch.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwrows.h'))
+    srcs.append(os.path.join(HERE, '..', 'include', 'kwingest.h'))
     return srcs
 
 

@@ -49,6 +49,10 @@ struct Pin {
 
 struct Emit {
     Buf c_buf, c_off, c_fl;             // the chunk's tokenized cells
+    const uint8_t *b_cells = nullptr;   // kw_rows_cells_device: the caller's device buffers instead
+    const int64_t *b_coff = nullptr;
+    const uint8_t *b_cfl = nullptr;
+    bool borrowed = false;
     int64_t cells_docs = -1;
     int32_t ncols = 0;
     Buf stamps, tcnt, tcur, seg, ord, used, dfl, slen, cq, llen, jl, flags, o_doc, o_ti, o_stamp, scratch, out;
@@ -461,6 +465,61 @@ extern "C" int kw_rows_cells(kw_rows *h, const uint8_t *cells, const int64_t *co
     RWCHK(h, hipStreamSynchronize(st));    // the caller's arrays are free again
     E->cells_docs = n_docs;
     E->ncols = ncols;
+    E->borrowed = false;
+    return KW_OK;
+}
+
+namespace rw {
+
+// kw_rows_cells' offset checks on device-resident offsets: bad[0] = 1 + the first cell whose offsets decrease
+// (1 + nc for a negative coff[0]), 0 when they are in order
+__global__ __launch_bounds__(BLOCK) void em_coff_check_kernel(const int64_t *__restrict__ coff, uint64_t nc,
+                                                              unsigned long long *__restrict__ bad)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0 && coff[0] < 0) atomicMax(bad, (unsigned long long)nc + 1ull);
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < nc; i += (uint64_t)gridDim.x * BLOCK)
+        if (coff[i + 1] < coff[i]) atomicMax(bad, (unsigned long long)(nc - i));   // (max of nc - i: the first such cell)
+}
+
+}  // namespace rw
+
+extern "C" int kw_rows_cells_device(kw_rows *h, const uint8_t *d_cells, const int64_t *d_coff, const uint8_t *d_cfl,
+                                    int64_t n_docs, int32_t ncols, void *stream)
+{
+    using namespace rw;
+    if (!h) return KW_EINVAL;
+    if (h->emit) h->emit->cells_docs = -1;
+    if (!d_coff || n_docs < 0 || ncols < 1 || n_docs >= (int64_t)1 << 31 || (n_docs > 0 && (!d_cfl || !d_cells))) {
+        h->err = "kw_rows_cells_device: bad arguments";
+        return KW_EINVAL;
+    }
+    const int64_t nc = n_docs * ncols;
+    if (nc >= (int64_t)1 << 34) { h->err = "kw_rows_cells_device: 2^34 cells or more"; return KW_EINVAL; }
+    int rc;
+    if ((rc = emit_state(h))) return rc;
+    Emit *E = h->emit;
+    hipStream_t st = (hipStream_t)stream;
+    RWCHK(h, hipSetDevice(h->device));
+    // every later read of the cell bytes must lie inside [0, coff[nc]): the offsets are checked where they are
+    unsigned long long bad = 0;
+    RWCHK(h, hipMemsetAsync(E->tot, 0, 8, st));
+    const uint64_t blocks = ((uint64_t)nc + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(em_coff_check_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks))), dim3(BLOCK),
+                       0, st, d_coff, (uint64_t)nc, E->tot);
+    RWCHK(h, hipMemcpyAsync(&bad, E->tot, 8, hipMemcpyDeviceToHost, st));
+    RWCHK(h, hipStreamSynchronize(st));
+    RWCHK(h, hipGetLastError());
+    if (bad == (unsigned long long)nc + 1ull) { h->err = "kw_rows_cells_device: a negative offset"; return KW_EINVAL; }
+    if (bad) {
+        h->err = "kw_rows_cells_device: offsets decrease at cell " + std::to_string((unsigned long long)nc - bad);
+        return KW_EINVAL;
+    }
+    E->b_cells = d_cells;
+    E->b_coff = d_coff;
+    E->b_cfl = d_cfl;
+    E->cells_docs = n_docs;
+    E->ncols = ncols;
+    E->borrowed = true;
     return KW_OK;
 }
 
@@ -516,8 +575,9 @@ extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stam
     const int32_t *row_doc = (const int32_t *)h->row_doc.p, *row_ti = (const int32_t *)h->row_ti.p;
     const uint8_t *json = (const uint8_t *)h->json.p;
     const int64_t *json_off = (const int64_t *)h->json_off.p;
-    const uint8_t *cbuf = (const uint8_t *)E->c_buf.p, *cfl = (const uint8_t *)E->c_fl.p;
-    const int64_t *coff = (const int64_t *)E->c_off.p;
+    const uint8_t *cbuf = E->borrowed ? E->b_cells : (const uint8_t *)E->c_buf.p;
+    const uint8_t *cfl = E->borrowed ? E->b_cfl : (const uint8_t *)E->c_fl.p;
+    const int64_t *coff = E->borrowed ? E->b_coff : (const int64_t *)E->c_off.p;
     const int64_t *stamps = (const int64_t *)E->stamps.p;
     u64 *tcnt = (u64 *)E->tcnt.p, *slen = (u64 *)E->slen.p, *llen = (u64 *)E->llen.p, *jl = (u64 *)E->jl.p;
     uint32_t *seg = (uint32_t *)E->seg.p, *ord = (uint32_t *)E->ord.p, *dfl = (uint32_t *)E->dfl.p;

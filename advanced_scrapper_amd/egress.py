@@ -355,7 +355,10 @@ def render_device(chunk, matcher, stamps_by_doc, n_rows_use: int):
         return None
     cols = np.asarray([chunk.col[k] for k in ('date_time', 'title', 'url', 'source', 'source_url', 'article_text')],
                       dtype=np.int32)
-    got = matcher.rows_emit(chunk.cells, cols, stamps_by_doc, int(n_rows_use))
+    if hasattr(chunk, 'device_cells'):       # an ingest.DeviceChunk: the cells are in device memory already
+        got = matcher.rows_emit_device(chunk, cols, stamps_by_doc, int(n_rows_use))
+    else:
+        got = matcher.rows_emit(chunk.cells, cols, stamps_by_doc, int(n_rows_use))
     if got is None:
         return None
     lines, line_off, flags, rd, ti, rs = got

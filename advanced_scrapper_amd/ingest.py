@@ -386,3 +386,363 @@ def parse_all(data: bytes):
         return None
     cells = Cells(out, coff[:rows * ncols + 1], cfl[:rows * ncols], int(rows), ncols)
     return names, cells, span[:2 * rows].reshape(-1, 2)
+
+
+# --------------------------------------------------------------------- the ingest on the device (include/kwingest.h)
+INGEST_DEVICE_DEFAULT = '1'
+DEFAULT_WINDOW = 32 << 20          # the least bytes of CSV uploaded at once (KW_INGEST_WINDOW sets them)
+MAX_WINDOW = (1 << 31) - (1 << 20)
+LAST_STATS = None                  # the counters of the last read_chunks_device
+
+
+def ingest_on_device() -> bool:
+    """The article CSV is tokenized on the device where that route applies (match_keywords.run, one GPU):
+    ``KW_INGEST_DEVICE=1`` asks for it, ``KW_INGEST_DEVICE=0`` keeps the host tokenizer
+    (profiles/e2e_ingest.json holds the measurement behind the default)."""
+    return os.environ.get('KW_INGEST_DEVICE', INGEST_DEVICE_DEFAULT) != '0'
+
+
+class DeviceIngest:
+    """One ``kw_ingest`` handle: raw CSV bytes in, the cells, the arena and the dates in device memory."""
+
+    def __init__(self, device: int, ncols: int, cols6: Sequence[int]):
+        from . import _native
+        global _NA
+        if _NA is None:
+            _NA = _na_table()
+        na_buf, na_off, n_na = _NA
+        self._n = _native
+        self.h = None
+        self.ncols = int(ncols)
+        self.cols = np.ascontiguousarray(cols6, dtype=np.int32)
+        if self.cols.shape != (6,):
+            raise ValueError('cols: six column indexes')
+        h = ctypes.c_void_p()
+        rc = _native.lib().kw_ingest_create(int(device), self.ncols, _p(self.cols), _p(na_buf), _p(na_off), n_na,
+                                            ctypes.byref(h))
+        if rc != _native.KW_OK:
+            raise _native.KwError(rc, 'kw_ingest_create: bad arguments or no device')
+        self.h = h
+        self.gen = 0               # parses so far: a DeviceChunk belongs to one
+        self.n_rows = 0
+        self._stage = [None, None]
+
+    def _check(self, rc: int) -> None:
+        if rc != self._n.KW_OK:
+            msg = self._n.lib().kw_ingest_last_error(self.h)
+            raise self._n.KwError(rc, msg.decode('utf-8', 'replace') if msg else '')
+
+    def stage(self, slot: int, n_bytes: int) -> np.ndarray:
+        """The pinned staging window ``slot`` (0 / 1) as a uint8 array of ``n_bytes``."""
+        have = self._stage[slot]
+        if have is not None and len(have) >= n_bytes:
+            return have[:n_bytes]
+        p = ctypes.c_void_p()
+        want = min(int(n_bytes) + int(n_bytes) // 8, (1 << 31) - 1)      # (kw_ingest_stage takes less than 2^31)
+        self._check(self._n.lib().kw_ingest_stage(self.h, slot, want, ctypes.byref(p)))
+        arr = np.frombuffer((ctypes.c_uint8 * max(want, 1)).from_address(p.value), dtype=np.uint8)
+        self._stage[slot] = arr
+        return arr[:n_bytes]
+
+    def upload(self, slot: int, start: int, n_bytes: int, stream=None):
+        """Bytes [start, start + n_bytes) of a staging window to the device text buffer; its device pointer."""
+        p = ctypes.c_void_p()
+        self._check(self._n.lib().kw_ingest_upload(self.h, slot, int(start), int(n_bytes), ctypes.byref(p), stream))
+        return p
+
+    def parse(self, d_text, n_bytes: int, final: bool, max_rows: int, stream=None):
+        """kw_ingest_parse: ``(verdict, bad_pos, n_rows, consumed)``."""
+        if not isinstance(d_text, (int, ctypes.c_void_p)):
+            d_text = self._n.ptr(d_text)
+        n_rows, consumed, verdict, bad = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+        self.gen += 1
+        self._check(self._n.lib().kw_ingest_parse(self.h, d_text, int(n_bytes), 1 if final else 0, int(max_rows),
+                                                  ctypes.byref(n_rows), ctypes.byref(consumed), ctypes.byref(verdict),
+                                                  ctypes.byref(bad), stream))
+        self.n_rows = int(n_rows.value)
+        return int(verdict.value), int(bad.value), self.n_rows, int(consumed.value)
+
+    def cells_device(self):
+        """``(d_cells, d_coff, d_cfl, cell_bytes)``: device pointers, valid until the next parse."""
+        a, b, c, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._n.lib().kw_ingest_cells(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                  ctypes.byref(n)))
+        return a, b, c, int(n.value)
+
+    def arena_device(self):
+        """``(d_arena, d_off, arena_bytes)``: device pointers, valid until the next parse."""
+        a, b, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._n.lib().kw_ingest_arena(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n)))
+        return a, b, int(n.value)
+
+    def dates(self):
+        us = np.zeros(max(self.n_rows, 1), dtype=np.int64)
+        kind = np.zeros(max(self.n_rows, 1), dtype=np.uint8)
+        self._check(self._n.lib().kw_ingest_dates(self.h, _p(us), _p(kind)))
+        return us[:self.n_rows], kind[:self.n_rows]
+
+    def column_flags(self) -> np.ndarray:
+        w = np.zeros(6, dtype=np.int32)
+        self._check(self._n.lib().kw_ingest_column_flags(self.h, _p(w)))
+        return w
+
+    def copy_cells(self) -> Cells:
+        n, nc = self.n_rows, self.n_rows * self.ncols
+        nb = self.cells_device()[3]
+        buf = np.empty(nb + 16, dtype=np.uint8)
+        coff = np.empty(nc + 1, dtype=np.int64)
+        cfl = np.empty(max(nc, 1), dtype=np.uint8)
+        self._check(self._n.lib().kw_ingest_copy_cells(self.h, _p(buf), _p(coff), _p(cfl)))
+        return Cells(buf, coff, cfl[:nc], n, self.ncols)
+
+    def copy_arena(self):
+        """The matcher's arena (its 64 zero bytes included) and 2n+1 offsets, as :meth:`NativeChunk.arena`."""
+        nb = self.arena_device()[2]
+        arena = np.empty(nb + 64, dtype=np.uint8)
+        off = np.empty(2 * self.n_rows + 1, dtype=np.int64)
+        self._check(self._n.lib().kw_ingest_copy_arena(self.h, _p(arena), _p(off)))
+        return arena, off
+
+    def copy_column(self, col: int):
+        """One column's cells, dense: ``(bytes, off int64[n + 1], flags uint8[n])``."""
+        n = self.n_rows
+        cap = self.cells_device()[3]
+        buf = np.empty(cap + 16, dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.int64)
+        fl = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self._n.lib().kw_ingest_copy_column(self.h, int(col), _p(buf), cap, _p(off), _p(fl)))
+        return buf[:int(off[n])], off, fl[:n]
+
+    def last_ms(self):
+        """Device times (ms) of the last parse: classify, cells, arena (+ dates), all."""
+        v = np.zeros(4, dtype=np.float32)
+        self._check(self._n.lib().kw_ingest_last_ms(self.h, _p(v), 4))
+        return dict(zip(('classify', 'cells', 'arena', 'all'), (float(x) for x in v)))
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            self._n.lib().kw_ingest_destroy(self.h)
+        self.h = None
+        self._stage = [None, None]
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceChunk(NativeChunk):
+    """One chunk tokenized on the device: the cells, the arena and the dates lie in the buffers of a
+    :class:`DeviceIngest` until its next parse; the host sees the date arrays, and the cells only when a
+    consumer reads them as ``str`` (downloaded once, on first use)."""
+
+    def __init__(self, dev: DeviceIngest, n_rows: int, columns: Sequence[str], index0: int):
+        self.dev, self.gen, self.n = dev, dev.gen, int(n_rows)
+        self.columns = list(columns)
+        self.col = {c: i for i, c in enumerate(self.columns)}
+        self.index0 = index0
+        self._cache = {}
+        self._cells = None
+
+    def _live(self) -> DeviceIngest:
+        if self.dev.h is None or self.dev.gen != self.gen:
+            raise RuntimeError('the device buffers of this chunk were taken by a later chunk')
+        return self.dev
+
+    @property
+    def cells(self) -> Cells:
+        if self._cells is None:
+            self._cells = self._live().copy_cells()
+        return self._cells
+
+    def __len__(self):
+        return self.n
+
+    def device_arena(self):
+        return self._live().arena_device()
+
+    def arena(self, pad: int = 64):
+        if pad != 64 or self._cells is not None:
+            return super().arena(pad)
+        return self._live().copy_arena()
+
+    def device_cells(self):
+        return self._live().cells_device()
+
+    def column_values(self, name: str, limit: Optional[int] = None) -> List:
+        """The first ``limit`` cells of one column as pandas gives them (``str`` / NaN), from that column alone."""
+        if self._cells is not None:
+            return [self._cells.value(r, self.col[name]) for r in range(min(self.n, self.n if limit is None else limit))]
+        buf, off, fl = self._live().copy_column(self.col[name])
+        mv, o = memoryview(buf), off.tolist()
+        k = self.n if limit is None else min(self.n, limit)
+        return [math.nan if fl[r] & NA else bytes(mv[o[r]:o[r + 1]]).decode('utf-8') for r in range(k)]
+
+    def dates(self):
+        from .dates import Dates, parse_date
+        us, kind = self._live().dates()
+        n = self.n
+        slow = {}
+        rows = np.flatnonzero(kind == 0).tolist()
+        if rows:
+            buf, off, _fl = self._live().copy_column(self.col['date_time'])
+            mv, o = memoryview(buf), off.tolist()
+            for r in rows:
+                try:
+                    slow[r] = parse_date(bytes(mv[o[r]:o[r + 1]]).decode('utf-8'))
+                except Exception as exc:   # noqa: BLE001 - match_keywords.py:152 raises here for this row
+                    return Dates(us[:r], kind[:r], {k: v for k, v in slow.items() if k < r}), exc
+        return Dates(us[:n], kind[:n], slow), None
+
+
+def _host_chunk(data, buf, pos, chunksize, ncols, names, need_idx, index0, head_end, starts):
+    """One chunk on the host route, as read_chunks_bytes reads it: (item or None at the end, rows, end); rows < 0:
+    pandas takes the rest of the file."""
+    rows = _lib().kwcsv_records(_p(buf), len(buf), pos, chunksize, ncols, _p(starts))
+    if rows <= 0:
+        return None, int(rows), pos
+    end = int(starts[rows])
+    cells = _tokenize(buf, starts[:rows + 1], ncols)
+    if cells is None:
+        return None, -2, pos
+    if not _native_flags(cells, need_idx).any():
+        return NativeChunk(cells, names, index0), int(rows), end
+    return _pandas_rows(data, pos, end, index0, head_end), int(rows), end
+
+
+def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[Union[NativeChunk, pd.DataFrame]]:
+    """:func:`read_chunks` with the tokenizing on the device: a window of the memory-mapped file goes through a
+    pinned staging buffer to the GPU once, ``kw_ingest_parse`` takes the next ``chunksize`` records there, and
+    the chunk comes back as a :class:`DeviceChunk`.  A window that ends before the chunk does is grown; what a
+    window holds beyond the chunk serves the next one; while a chunk is at work a background thread fills the
+    other staging buffer.  A chunk the device refuses (the take rule, include/kwingest.h) goes through the host
+    route alone, with its own pandas decisions, and the device resumes where that ended; a chunk without a
+    text witness in a needed column is parsed by pandas, as on the host route.  ``LAST_STATS`` counts the routes."""
+    global LAST_STATS
+    from . import _native
+    from concurrent.futures import ThreadPoolExecutor
+    stats = LAST_STATS = {'device': 0, 'host': 0, 'pandas': 0, 'grown': 0, 'reused': 0, 'routes': [], 'ms': [],
+                          'bytes': 0, 'wall_s': 0.0, 'wall_ms': []}
+    data = _map(path)
+    names, head, pos = _split_header(data)
+    ncols = len(names)
+    if not _header_ok(names) or ncols < 6:
+        yield from pd.read_csv(path, chunksize=chunksize)
+        return
+    need_idx = [names.index(n) for n in NEEDED]
+    buf = np.frombuffer(data, dtype=np.uint8)
+    total = len(buf)
+    if pos >= total:       # a header alone: no record, and no device is touched (as on the host route)
+        return
+    head_end = pos
+    index0 = 0
+    starts = np.empty(chunksize + 1, dtype=np.int64)
+    env = os.environ.get('KW_INGEST_WINDOW')
+    if env:
+        window = max(64, int(env))
+    else:
+        # a chunk and a third, from the line ends outside quotes of the first MB (a window that is too small is
+        # grown; the later windows follow the chunks' own sizes)
+        probe = np.frombuffer(data, dtype=np.uint8, count=min(1 << 20, total - pos), offset=pos)
+        inside = np.cumsum(probe == 0x22) & 1
+        ends = int(np.count_nonzero((probe == 0x0A) & (inside == 0)))
+        per_row = len(probe) / max(1, ends)
+        window = int(min(MAX_WINDOW, max(DEFAULT_WINDOW, 1.34 * chunksize * per_row)))
+    dev = DeviceIngest(device, ncols, need_idx)
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='kw-ingest')
+    import time
+
+    def copy(view, slot, lo, n):
+        np.copyto(view, buf[lo:lo + n])     # (releases the GIL)
+        return slot, lo, n
+
+    def fill(slot, lo, n):
+        return copy(dev.stage(slot, n), slot, lo, n)
+
+    try:
+        have = None        # (slot, file position, bytes) of the filled staging window
+        ahead = None       # the same, being filled by the background thread
+        est = window       # the bytes a chunk is expected to take: the last one's
+        while pos < total:
+            t0 = time.perf_counter()
+            want = window
+            verdict = _native.KW_INGEST_OK
+            first = True
+            while True:
+                need = min(want, total - pos)
+                rem = have[1] + have[2] - pos if (have is not None and have[1] <= pos < have[1] + have[2]) else 0
+                if not (rem >= need or (first and rem >= min(est, total - pos))):
+                    got = None
+                    if ahead is not None:
+                        got = ahead.result()
+                        ahead = None
+                    if got is not None and got[1] == pos and got[2] >= need:
+                        have = got
+                    else:
+                        have = fill(0 if have is None else 1 - have[0], pos, need)
+                first = False
+                slot, lo, n = have
+                final = lo + n == total
+                d_text = dev.upload(slot, pos - lo, lo + n - pos)
+                verdict, _bad, n_rows, consumed = dev.parse(d_text, lo + n - pos, final, chunksize)
+                if verdict == _native.KW_INGEST_OK and n_rows < chunksize and not final:
+                    if lo + n - pos >= want:           # the whole window was not enough: a larger one
+                        if want >= MAX_WINDOW:
+                            verdict = -1               # no chunk within the largest window: the host route
+                            break
+                        want = min(2 * want, MAX_WINDOW)
+                    stats['grown'] += 1
+                    continue
+                break
+            if verdict != _native.KW_INGEST_OK:
+                if ahead is not None:
+                    ahead.result()
+                    ahead = None
+                item, rows, end = _host_chunk(data, buf, pos, chunksize, ncols, names, need_idx, index0, head_end, starts)
+                if rows == 0:
+                    break
+                if rows < 0:
+                    stats['routes'].append('pandas-rest')
+                    yield from _pandas_rest(data, pos, chunksize, index0, head_end)
+                    return
+                stats['host'] += 1
+                stats['routes'].append('host')
+                yield item
+                index0 += rows
+                pos = end
+                continue
+            if n_rows == 0:
+                break
+            end = pos + consumed
+            if lo < pos:
+                stats['reused'] += 1
+            est = consumed
+            if not env:
+                window = max(DEFAULT_WINDOW, consumed + consumed // 4)
+            # the next window, unless this one still holds a chunk's worth beyond `end`
+            if end < total and lo + n - end < min(est, total - end) and ahead is None:
+                nxt = min(window, total - end)
+                ahead = pool.submit(copy, dev.stage(1 - slot, nxt), 1 - slot, end, nxt)
+            if dev.column_flags().all():
+                stats['device'] += 1
+                stats['routes'].append('device')
+                stats['ms'].append(dev.last_ms())
+                stats['bytes'] += consumed
+                stats['wall_s'] += time.perf_counter() - t0
+                stats['wall_ms'].append(round(1e3 * (time.perf_counter() - t0), 3))
+                yield DeviceChunk(dev, n_rows, names, index0)
+            else:
+                stats['pandas'] += 1
+                stats['routes'].append('pandas')
+                yield _pandas_rows(data, pos, end, index0, head_end)
+            index0 += n_rows
+            pos = end
+    finally:
+        if ahead is not None:
+            try:
+                ahead.result()
+            except Exception:   # noqa: BLE001 - the reader is leaving
+                pass
+        pool.shutdown(wait=True)
+        dev.close()

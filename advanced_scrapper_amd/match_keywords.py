@@ -32,7 +32,7 @@ import pandas as pd
 from dateutil import parser
 
 from . import egress, ingest
-from .ingest import NativeChunk, ShardChunk
+from .ingest import DeviceChunk, NativeChunk, ShardChunk
 from .dates import parse_date
 from .kb import (ATTRIBUTES, compile_kb, extract_time_periods, is_within_period,  # noqa: F401 (re-export)
                  process_json_data, read_and_process_json_files)
@@ -447,6 +447,8 @@ def _write_chunk_sharded(source_name, chunk, processed_data, matcher, exchange):
 
 def _native_sample(chunk: NativeChunk, limit: int = 4000):
     """The first rows' article texts (the anchor statistics' sample; speed only)."""
+    if isinstance(chunk, DeviceChunk):       # that column alone comes to the host
+        return [field_str(v) for v in chunk.column_values('article_text', limit)]
     col = chunk.col['article_text']
     return [field_str(chunk.cells.value(i, col)) for i in range(min(len(chunk), limit))]
 
@@ -460,6 +462,10 @@ def _native_match(chunk: NativeChunk, processed_data, matcher, exchange=None):
     matcher = matcher or get_matcher(processed_data, sample_texts=_native_sample(chunk))
     if n_ok == 0:
         return None, dates, error, matcher
+    if isinstance(chunk, DeviceChunk) and exchange is None:
+        d_arena, d_off, _nb = chunk.device_arena()   # packed on the device from the same upload: nothing to copy
+        matcher.scan_ptr(d_arena, d_off, n_ok, keep=chunk)
+        return matcher.fetch_host(), dates, error, matcher
     arena, off = chunk.arena()
     off = off[:2 * n_ok + 1]
     if exchange is None:
@@ -737,7 +743,13 @@ def run(args, rank: int, world: int, device, backend, matcher=None):
     try:
         # the native tokenizer (ingest.py), chunk by chunk, with pandas' own chunks where it cannot be exact;
         # the next chunk is read while this one is matched and written
-        for chunk in _prefetch(ingest.read_chunks(args.articles, args.chunksize)):
+        # with KW_INGEST_DEVICE the tokenizing runs on the GPU (ingest.read_chunks_device: its own background
+        # thread fills the next staging window; every device call stays on this thread)
+        if ingest.ingest_on_device() and (matcher is None or hasattr(matcher, 'scan_ptr')):
+            chunks = ingest.read_chunks_device(args.articles, args.chunksize, 0 if device is None else int(device))
+        else:
+            chunks = _prefetch(ingest.read_chunks(args.articles, args.chunksize))
+        for chunk in chunks:
             if warm is not None:
                 warm.join()
                 warm = None

@@ -215,6 +215,13 @@ class GpuMatcher:
         _native.check(_native.lib().kw_scan_host(self.h, _native.ptr(arena), int(arena.size), _native.ptr(off),
                                                  int(n_docs)), self.h)
 
+    def scan_ptr(self, d_arena, d_off, n_docs: int, keep=None) -> None:
+        """Launch kw_scan on raw device pointers (an ingest.DeviceChunk's arena; ``keep`` is held until the next
+        scan) on the default stream: no torch in this path.  Asynchronous until :meth:`fetch_host`."""
+        self._keep = keep
+        self._fetched = None
+        _native.check(_native.lib().kw_scan(self.h, d_arena, d_off, int(n_docs), None), self.h)
+
     def fetch_host(self) -> np.ndarray:
         """Records of the last scan on the host (structured HIT_DTYPE array)."""
         n = self.n_hits()
@@ -256,6 +263,14 @@ class GpuMatcher:
         the chunk's tokenized ``cells`` (rows.DeviceRows.cells + emit; ``None`` on the verdict KW_EMIT_NUL)."""
         handle = self.rows_handle()
         handle.cells(cells, handle.n_docs)
+        return handle.emit(cols, np.asarray(stamp_by_doc, dtype=np.int64)[:handle.n_docs], n_rows_use)
+
+    def rows_emit_device(self, chunk, cols, stamp_by_doc: np.ndarray, n_rows_use: int):
+        """:meth:`rows_emit` from the cells of an ingest.DeviceChunk where they lie in device memory
+        (``kw_rows_cells_device``: no download, no upload)."""
+        handle = self.rows_handle()
+        d_cells, d_coff, d_cfl, _nb = chunk.device_cells()
+        handle.cells_device(d_cells, d_coff, d_cfl, handle.n_docs, len(chunk.columns))
         return handle.emit(cols, np.asarray(stamp_by_doc, dtype=np.int64)[:handle.n_docs], n_rows_use)
 
     def match_device(self, texts: Sequence[str], titles: Sequence[str]):

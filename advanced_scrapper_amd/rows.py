@@ -203,6 +203,11 @@ class DeviceRows:
             raise ValueError('the cells are shorter than their offsets say')
         self._check(_native.lib().kw_rows_cells(self.h, _ptr(buf), _ptr(off), _ptr(fl), n, int(cells.ncols), stream))
 
+    def cells_device(self, d_cells, d_coff, d_cfl, n_docs: int, ncols: int, stream=None) -> None:
+        """:meth:`cells` on device-resident cells (raw pointers, as ``kw_ingest_cells`` gives them): borrowed, they
+        must stay valid through the next :meth:`emit`."""
+        self._check(_native.lib().kw_rows_cells_device(self.h, d_cells, d_coff, d_cfl, int(n_docs), int(ncols), stream))
+
     def emit(self, cols, stamp_by_doc: np.ndarray, n_rows_use: int, stream=None):
         """The first ``n_rows_use`` rows of the last :meth:`run` as CSV lines, rendered on the device from the cells
         of :meth:`cells` (``cols``: their columns of date_time, title, url, source, source_url, article_text;

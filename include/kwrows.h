@@ -93,6 +93,13 @@ int kw_rows_copy_index(kw_rows *r, int32_t *row_doc, int32_t *row_ti);
 int kw_rows_cells(kw_rows *r, const uint8_t *cells, const int64_t *coff, const uint8_t *cfl, int64_t n_docs,
                   int32_t ncols, void *stream);
 
+/* kw_rows_cells on cells that are already in device memory (kw_ingest_cells' buffers, kwingest.h): nothing is
+ * copied, the handle borrows the three buffers, which must stay valid and unchanged through the next
+ * kw_rows_emit.  The same layout and the same checks (the offsets are checked on the device; the call returns
+ * after that check). */
+int kw_rows_cells_device(kw_rows *r, const uint8_t *d_cells, const int64_t *d_coff, const uint8_t *d_cfl,
+                         int64_t n_docs, int32_t ncols, void *stream);
+
 /* Render the first n_rows_use rows (in kw_rows_run's document order: any prefix, 0 included) of the last run.
  * cols[6]: the cells' columns of date_time, title, url, source, source_url, article_text; stamp_by_doc: host
  * int64[n_docs], each document's time_unix.  Returns after the lines are in the handle's pinned host buffers:

@@ -22,6 +22,13 @@ chunks (order, expand, render) and the wall time either route spent building the
 lines rendered on the device, csrc/kwemit.hip), this tree with ``KW_EMIT_DEVICE=0`` (kwcsv_emit_mt on the host) and,
 with ``--parent-tree DIR``, that tree.  OUT.json gets the medians, the wall time inside either renderer, and the
 device route's per-chunk ``kw_rows_emit_last_ms`` (order, measure, fill, copy).
+
+``--ingest-ab OUT.json`` compares the routes of the article ingest the same way: this tree with ``KW_INGEST_DEVICE=1``
+(the CSV tokenized on the device, csrc/kwingest.hip), this tree with ``KW_INGEST_DEVICE=0`` (csrc/kwcsv.c on the
+host threads) and, with ``--parent-tree DIR``, that tree.  OUT.json gets the medians and ranges, the wall time of the
+ingest span per chunk (device: staging, upload and kw_ingest_parse on the main thread; host: the tokenizer on its
+prefetch thread, overlapped with the matching), the ``kw_ingest_last_ms`` sums, the parse rate, and which route the
+standing rule makes the default.
 """
 import argparse
 import contextlib
@@ -182,6 +189,65 @@ print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span
 '''
 
 
+INGEST_CHILD = r'''
+import contextlib, hashlib, io, json, os, sys, tempfile, time
+tree, info_dir, csv_path, chunksize = sys.argv[1:5]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import ingest, match_keywords as mk
+span = {'device_calls': 0, 'host_calls': 0, 'host_s': 0.0, 'device_s': 0.0, 'chunks': 0, 'bytes': 0,
+        'classify': 0.0, 'cells': 0.0, 'arena': 0.0, 'all': 0.0, 'routes': {}}
+host = ingest.read_chunks
+def timed_host(path, chunksize):
+    span['host_calls'] += 1
+    it = host(path, chunksize)
+    while True:
+        t = time.perf_counter()
+        try:
+            chunk = next(it)
+        except StopIteration:
+            return
+        span['host_s'] += time.perf_counter() - t
+        span['chunks'] += 1
+        yield chunk
+ingest.read_chunks = timed_host
+device = getattr(ingest, 'read_chunks_device', None)      # (the parent tree has none)
+if device is not None:
+    def counted_device(*a, **kw):
+        span['device_calls'] += 1
+        return device(*a, **kw)
+    ingest.read_chunks_device = counted_device
+work = tempfile.mkdtemp(prefix='e2e_ingest_')
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()):
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0
+st = getattr(ingest, 'LAST_STATS', None)
+if st is not None:
+    span['device_s'] = st['wall_s']
+    span['chunks'] = st['device'] + st['host'] + st['pandas']
+    span['bytes'] = st['bytes']
+    span['routes'] = {k: st[k] for k in ('device', 'host', 'pandas', 'grown', 'reused')}
+    span['wall_ms'] = st['wall_ms']
+    for m in st['ms']:
+        for k in ('classify', 'cells', 'arena', 'all'):
+            span[k] += m[k]
+h = hashlib.sha256()
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+import shutil
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
 def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS_CHILD):
     """main() in a fresh child per run on ``tree``: one warm-up, then ``runs`` timed runs."""
     import statistics
@@ -189,6 +255,8 @@ def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS
     env = dict(os.environ)
     env.pop('KW_ROWS_DEVICE', None)
     env.pop('KW_EMIT_DEVICE', None)
+    env.pop('KW_INGEST_DEVICE', None)
+    env.pop('KW_INGEST_WINDOW', None)
     env.update(env_extra)
     got = []
     for _ in range(runs + 1):
@@ -280,8 +348,52 @@ def emit_ab(args):
     assert res['same_bytes'], 'the configurations wrote different bytes'
 
 
+def ingest_ab(args):
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=0)
+    csv_path = os.path.join(work, 'articles.csv')
+    synth.to_dataframe(corpus).to_csv(csv_path, index=False)
+    del corpus
+    res = {'docs': args.docs, 'chunksize': args.chunksize, 'csv_bytes': os.path.getsize(csv_path),
+           'runs_per_config': args.runs,
+           'timed': 'match_keywords.main() wall time in a fresh child per run; 1 warm-up + the median of the runs; '
+                    'cells: the median run\'s ingest span -- device_s: the wall time of staging, upload and '
+                    'kw_ingest_parse on the main thread; host_s: the wall time the host tokenizer took on its prefetch '
+                    'thread (overlapped with the matching) -- and the device times (ms) of kw_ingest_last_ms summed over '
+                    'the chunks'}
+    try:
+        res['device'] = rows_config(REPO, {'KW_INGEST_DEVICE': '1'}, info_dir, csv_path, args.chunksize, args.runs, INGEST_CHILD)
+        res['host'] = rows_config(REPO, {'KW_INGEST_DEVICE': '0'}, info_dir, csv_path, args.chunksize, args.runs, INGEST_CHILD)
+        if args.parent_tree:
+            res['parent'] = rows_config(os.path.abspath(args.parent_tree), {}, info_dir, csv_path, args.chunksize,
+                                        args.runs, INGEST_CHILD)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    d, hst = res['device']['cells'], res['host']['cells']
+    assert d['device_calls'] > 0 and d['host_calls'] == 0 and d['routes'].get('device', 0) == d['chunks'] > 0
+    assert hst['device_calls'] == 0 and hst['host_calls'] > 0
+    res['same_bytes'] = len({res[k]['sha256'] for k in ('device', 'host', 'parent') if k in res}) == 1
+    res['ingest_span_ms_per_chunk'] = {'device': round(1e3 * d['device_s'] / d['chunks'], 3),
+                                       'host': round(1e3 * hst['host_s'] / max(hst['chunks'], 1), 3)}
+    res['parse_GBps'] = round(d['bytes'] / (d['all'] * 1e-3) / 1e9, 2) if d['all'] else None
+    res['device_faster'] = res['device']['median_s'] < res['host']['median_s']
+    res['default'] = 'device' if res['device_faster'] else 'host (the device route behind KW_INGEST_DEVICE=1)'
+    with open(args.ingest_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['same_bytes'], 'the configurations wrote different bytes'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--ingest-ab', metavar='OUT.json', help='compare the article ingest\'s routes (see the module doc)')
     ap.add_argument('--emit-ab', metavar='OUT.json', help='compare the CSV rows\' routes (see the module doc)')
     ap.add_argument('--rows-ab', metavar='OUT.json', help='compare the JSON cells\' routes (see the module doc)')
     ap.add_argument('--parent-tree', help='--rows-ab / --emit-ab: a built checkout of the parent commit')
@@ -298,6 +410,9 @@ def main():
     if args.emit_ab:
         args.emit_ab = os.path.abspath(args.emit_ab)
         return emit_ab(args)
+    if args.ingest_ab:
+        args.ingest_ab = os.path.abspath(args.ingest_ab)
+        return ingest_ab(args)
     import bench
     from advanced_scrapper_amd import ingest, match_keywords as mk, synth
     from advanced_scrapper_amd.kb import compile_kb
