@@ -25,6 +25,7 @@
 #include <string>
 
 #include "../../include/kwingest.h"
+#include "kwenv.hpp"
 
 namespace ig {
 
@@ -682,11 +683,23 @@ static int ensure(kw_ingest *h, Buf &b, size_t bytes)
     return KW_OK;
 }
 
-static dim3 grid_for(long long items)
+// The cap on every launch grid of a call: MAX_GRID, or the tests' KW_TEST_INGEST_GRID in [1, MAX_GRID] (read per
+// call through kw_env: the kernels' loops then make several trips on a small text).
+static int grid_cap()
+{
+    if (const char *e = kw_env("KW_TEST_INGEST_GRID")) {
+        char *end = nullptr;
+        const long g = strtol(e, &end, 10);
+        if (end != e && *end == '\0' && g >= 1 && g <= MAX_GRID) return (int)g;
+    }
+    return MAX_GRID;
+}
+
+static dim3 grid_for(long long items, int cap)
 {
     long long g = (items + BLOCK - 1) / BLOCK;
     if (g < 1) g = 1;
-    if (g > MAX_GRID) g = MAX_GRID;
+    if (g > cap) g = cap;
     return dim3((unsigned)g);
 }
 
@@ -806,7 +819,8 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     A.coff = (long long *)h->coff.p;
     A.cflw = (uint32_t *)h->cflw.p;
     A.cells = (uint8_t *)h->cells.p;
-    const dim3 tgrid((unsigned)(ntiles < 1 ? 1 : (ntiles > MAX_GRID ? MAX_GRID : ntiles)));
+    const int gcap = grid_cap();
+    const dim3 tgrid((unsigned)(ntiles < 1 ? 1 : (ntiles > gcap ? gcap : ntiles)));
 
     IGCHK(h, hipEventRecord(h->ev[0], st));
     IGCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
@@ -834,14 +848,14 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     hipLaunchKernelGGL(ig_tile_kernel<1>, tgrid, dim3(BLOCK), 0, st, A);
     hipLaunchKernelGGL(ig_finish_kernel, dim3(1), dim3(64), 0, st, h->D, (const long long *)A.coff, n, A.final_,
                        (long long)max_rows, (int)ncols);
-    hipLaunchKernelGGL(ig_flags_kernel, grid_for(cells_cap), dim3(BLOCK), 0, st, h->D, (const uint8_t *)A.cells,
+    hipLaunchKernelGGL(ig_flags_kernel, grid_for(cells_cap, gcap), dim3(BLOCK), 0, st, h->D, (const uint8_t *)A.cells,
                        (const long long *)A.coff, (const uint32_t *)A.cflw, (uint8_t *)h->cfl.p, (int)ncols, h->cols,
                        (const uint8_t *)h->d_na, (const int *)h->d_na_off, h->n_na);
     IGCHK(h, hipEventRecord(h->ev[2], st));
     // arena + dates
-    hipLaunchKernelGGL(ig_rows_kernel, grid_for(rows_cap), dim3(BLOCK), 0, st, (const Dev *)h->D, (const uint8_t *)A.cells,
-                       (const long long *)A.coff, (const uint8_t *)h->cfl.p, (int)ncols, h->cols, (long long *)h->us.p,
-                       (uint8_t *)h->kind.p, (u64 *)h->aoff.p);
+    hipLaunchKernelGGL(ig_rows_kernel, grid_for(rows_cap, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
+                       (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p, (int)ncols, h->cols,
+                       (long long *)h->us.p, (uint8_t *)h->kind.p, (u64 *)h->aoff.p);
     {
         ScanArgs S{};
         S.a[0] = (u64 *)h->aoff.p;
@@ -852,8 +866,8 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
         S.m_add = 1;
         hipLaunchKernelGGL(ig_scan_kernel, dim3(1), dim3(BLOCK), 0, st, S);
     }
-    hipLaunchKernelGGL(ig_gather_kernel<true>, grid_for((n + 6 * rows_cap + ARENA_PAD) / 16 + 1), dim3(BLOCK), 0, st,
-                       (const Dev *)h->D, (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p,
+    hipLaunchKernelGGL(ig_gather_kernel<true>, grid_for((n + 6 * rows_cap + ARENA_PAD) / 16 + 1, gcap), dim3(BLOCK), 0,
+                       st, (const Dev *)h->D, (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p,
                        (int)ncols, h->cols.c[0], h->cols.c[1], (const u64 *)h->aoff.p, (uint8_t *)h->arena.p, ARENA_PAD);
     IGCHK(h, hipEventRecord(h->ev[3], st));
     IGCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
@@ -997,8 +1011,10 @@ extern "C" int kw_ingest_copy_column(kw_ingest *h, int32_t col, uint8_t *bytes, 
     if ((rc = ensure(h, h->col_off, (size_t)(nr + 1) * 8)) || (rc = ensure(h, h->col_fl, (size_t)nr)) ||
         (rc = ensure(h, h->col_buf, (size_t)h->H->cell_bytes + 32)))
         return rc;
-    hipLaunchKernelGGL(ig_collen_kernel, grid_for(nr), dim3(BLOCK), 0, st, (const Dev *)h->D, (const long long *)h->coff.p,
-                       (const uint8_t *)h->cfl.p, h->ncols, (int)col, (u64 *)h->col_off.p, (uint8_t *)h->col_fl.p);
+    const int gcap = grid_cap();
+    hipLaunchKernelGGL(ig_collen_kernel, grid_for(nr, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
+                       (const long long *)h->coff.p, (const uint8_t *)h->cfl.p, h->ncols, (int)col, (u64 *)h->col_off.p,
+                       (uint8_t *)h->col_fl.p);
     {
         ScanArgs S{};
         S.a[0] = (u64 *)h->col_off.p;
@@ -1006,9 +1022,9 @@ extern "C" int kw_ingest_copy_column(kw_ingest *h, int32_t col, uint8_t *bytes, 
         S.m = nr + 1;
         hipLaunchKernelGGL(ig_scan_kernel, dim3(1), dim3(BLOCK), 0, st, S);
     }
-    hipLaunchKernelGGL(ig_gather_kernel<false>, grid_for(h->H->cell_bytes / 16 + 1), dim3(BLOCK), 0, st, (const Dev *)h->D,
-                       (const uint8_t *)h->cells.p, (const long long *)h->coff.p, (const uint8_t *)h->cfl.p, h->ncols,
-                       (int)col, 0, (const u64 *)h->col_off.p, (uint8_t *)h->col_buf.p, 0);
+    hipLaunchKernelGGL(ig_gather_kernel<false>, grid_for(h->H->cell_bytes / 16 + 1, gcap), dim3(BLOCK), 0, st,
+                       (const Dev *)h->D, (const uint8_t *)h->cells.p, (const long long *)h->coff.p,
+                       (const uint8_t *)h->cfl.p, h->ncols, (int)col, 0, (const u64 *)h->col_off.p, (uint8_t *)h->col_buf.p, 0);
     IGCHK(h, hipMemcpyAsync(off, h->col_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, st));
     IGCHK(h, hipMemcpyAsync(fl, h->col_fl.p, (size_t)nr, hipMemcpyDeviceToHost, st));
     IGCHK(h, hipStreamSynchronize(st));

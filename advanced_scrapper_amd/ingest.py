@@ -405,12 +405,20 @@ def ingest_on_device() -> bool:
 class DeviceIngest:
     """One ``kw_ingest`` handle: raw CSV bytes in, the cells, the arena and the dates in device memory."""
 
-    def __init__(self, device: int, ncols: int, cols6: Sequence[int]):
+    def __init__(self, device: int, ncols: int, cols6: Sequence[int], na=None):
+        """``na``: the NA strings as a ``(buf, off, n)`` triple in :func:`_na_table`'s shape (pandas' own by default)."""
         from . import _native
         global _NA
-        if _NA is None:
-            _NA = _na_table()
-        na_buf, na_off, n_na = _NA
+        if na is not None:
+            na_buf = np.ascontiguousarray(na[0], dtype=np.uint8)
+            na_off = np.ascontiguousarray(na[1], dtype=np.int32)
+            n_na = int(na[2])
+            if n_na < 0 or len(na_off) < n_na + 1 or len(na_buf) < int(na_off[n_na]):
+                raise ValueError('na: (buf, off, n) with n + 1 offsets into buf')
+        else:
+            if _NA is None:
+                _NA = _na_table()
+            na_buf, na_off, n_na = _NA
         self._n = _native
         self.h = None
         self.ncols = int(ncols)

@@ -215,12 +215,13 @@ def na_set():
     return frozenset(bytes(buf[off[k]:off[k + 1]]) for k in range(n))
 
 
-def host_parse(text: bytes, ncols: int, max_rows: int):
-    """kwcsv_parse of text from position 0: (rows or a negative code, pos_out, cell bytes, offsets, flags, spans)."""
+def host_parse(text: bytes, ncols: int, max_rows: int, na=None):
+    """kwcsv_parse of text from position 0: (rows or a negative code, pos_out, cell bytes, offsets, flags, spans).
+    ``na``: a (buf, off, n) triple in the shape of ingest._na_table() (pandas' own table by default)."""
     import ctypes
     import numpy as np
     from advanced_scrapper_amd import ingest
-    na_buf, na_off, n_na = ingest._na_table()
+    na_buf, na_off, n_na = ingest._na_table() if na is None else na
     buf = np.frombuffer(text + b'\0' * 16, dtype=np.uint8)
     cap_rows = min(max_rows, len(text) + 1)
     out = np.zeros(len(text) + 16, dtype=np.uint8)
@@ -247,13 +248,13 @@ def names_for(ncols: int, cols):
     return names
 
 
-def host_oracle(text: bytes, ncols: int, cols, max_rows: int):
+def host_oracle(text: bytes, ncols: int, cols, max_rows: int, na=None):
     """What the host route computes for the first max_rows records of text (read as a final text): a dict of
-    n_rows, consumed, cells, coff, cfl, arena, off, us, kind, witness -- through kwcsv_parse, kwcsv_pack_mt and
-    kwcsv_dates (advanced_scrapper_amd.ingest)."""
+    n_rows, consumed, cells, coff, cfl, arena, off, us, kind, witness -- through kwcsv_parse (with the NA table
+    ``na``, pandas' own by default), kwcsv_pack_mt and kwcsv_dates (advanced_scrapper_amd.ingest)."""
     import numpy as np
     from advanced_scrapper_amd import ingest
-    rows, pos, out, coff, cfl, spans = host_parse(text, ncols, max_rows)
+    rows, pos, out, coff, cfl, spans = host_parse(text, ncols, max_rows, na)
     assert rows >= 0, rows
     cells = ingest.Cells(np.frombuffer(out + b'\0' * 16, dtype=np.uint8), np.asarray(coff, dtype=np.int64),
                          np.asarray(cfl, dtype=np.uint8), rows, ncols)
