@@ -37,7 +37,7 @@ KW_NOPOS = 0xFFFFFFFF
 
 HIT_DTYPE = np.dtype([('doc', '<u4'), ('pattern', '<u4'), ('pos', '<u4'), ('field', '<u4')])
 
-# every symbol include/kwmatch.h, include/kwdedup.h, include/kwrows.h and include/kwingest.h declare
+# every symbol include/kwmatch.h, include/kwdedup.h, include/kwrows.h, include/kwingest.h and include/kwsort.h declare
 EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_last_kernel_ms',
            'kw_last_kernel_times', 'kw_doc_routes', 'kw_last_error', 'kw_destroy',
            'kw_scan_host', 'kw_hits_host', 'kw_device_count', 'kw_device_init',
@@ -58,7 +58,9 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_ingest_tile_bytes', 'kw_ingest_parse', 'kw_ingest_cells', 'kw_ingest_arena', 'kw_ingest_dates',
            'kw_ingest_column_flags', 'kw_ingest_copy_cells', 'kw_ingest_copy_column', 'kw_ingest_stage',
            'kw_ingest_copy_arena',
-           'kw_ingest_upload')
+           'kw_ingest_upload', 'kw_ingest_spans', 'kw_ingest_copy_spans',
+           'kw_sort_create', 'kw_sort_destroy', 'kw_sort_last_error', 'kw_sort_last_ms', 'kw_sort_keys',
+           'kw_sort_gather')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -82,6 +84,8 @@ KW_EMIT_OK, KW_EMIT_NUL = 0, 1             # verdicts of kw_rows_emit (include/k
 # KW_INGEST_* verdicts of kw_ingest_parse (include/kwingest.h), in the order they are tested
 (KW_INGEST_OK, KW_INGEST_NUL, KW_INGEST_UTF8, KW_INGEST_QUOTE, KW_INGEST_CR, KW_INGEST_BLANK, KW_INGEST_FIELDS,
  KW_INGEST_ROWS) = range(8)
+# KW_SORT_* verdicts of kw_sort_keys (include/kwsort.h), in the order they are tested
+KW_SORT_OK, KW_SORT_KEY, KW_SORT_FORM, KW_SORT_DTYPE = range(4)
 KW_N_STATS = 21
 # KW_RESCAN_* bits of stats[20] (include/kwmatch.h)
 KW_RESCAN_GENERIC_ITEMS, KW_RESCAN_RESULTS, KW_RESCAN_GENERIC_CPS = 1, 2, 4
@@ -184,6 +188,20 @@ def lib() -> ctypes.CDLL:
         getattr(L, f).restype = ctypes.c_int
     L.kw_ingest_last_error.argtypes = [vp]
     L.kw_ingest_last_error.restype = ctypes.c_char_p
+    L.kw_ingest_spans.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                  ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.kw_ingest_copy_spans.argtypes = [vp, vp, vp]
+    L.kw_sort_create.argtypes = [i32, ctypes.POINTER(vp)]
+    L.kw_sort_destroy.argtypes = [vp]
+    L.kw_sort_keys.argtypes = [vp, vp, i32, i64, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64),
+                               ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
+    L.kw_sort_gather.argtypes = [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.kw_sort_last_ms.argtypes = [vp, vp, i32]
+    for f in ('kw_ingest_spans', 'kw_ingest_copy_spans', 'kw_sort_create', 'kw_sort_destroy', 'kw_sort_keys',
+              'kw_sort_gather', 'kw_sort_last_ms'):
+        getattr(L, f).restype = ctypes.c_int
+    L.kw_sort_last_error.argtypes = [vp]
+    L.kw_sort_last_error.restype = ctypes.c_char_p
     L.kw_rows_last_error.argtypes = [vp]
     L.kw_rows_last_error.restype = ctypes.c_char_p
     L.kw_compile.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, i32, ctypes.POINTER(vp)]

@@ -46,6 +46,7 @@ def _kw_sources():
     srcs.append(os.path.join(HERE, '..', 'include', 'kwmatch.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwrows.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwingest.h'))
+    srcs.append(os.path.join(HERE, '..', 'include', 'kwsort.h'))
     return srcs
 
 

@@ -17,6 +17,8 @@
 //   ig_flags_kernel    lane = cell: CANON, the NA compare, the text witness, the columns' witnesses.
 //   ig_rows_kernel     lane = row: the date fast path, the two arena segment lengths.
 //   ig_gather_kernel   lane = 16 arena bytes: the segment by binary search in the scanned offsets.
+//   ig_spans_kernel    on request (kw_ingest_spans), after an OK parse: the tile masks once more, for every taken
+//                      record's first byte and the byte after its last.
 // One host synchronisation a parse; every buffer is sized from n_bytes and max_rows before the first launch.
 #include <hip/hip_runtime.h>
 
@@ -447,6 +449,56 @@ __global__ void ig_finish_kernel(Dev *__restrict__ D, const long long *__restric
     D->arena_bytes = 0;
 }
 
+// Every taken record's byte span, as kwcsv_parse's rspan gives it.  A record with bytes starts at a byte outside
+// quotes that follows a '\n' outside quotes (or the text's start) and is neither '\n' nor '\r' (outside quotes a
+// '\r' is followed by '\n': the CR rule, so either begins a record of no bytes); the records that ended before it
+// are its rank.  A record ends where ig_tile_kernel counts its end, before the '\r' of a "\r\n".  Runs on the
+// scanned tile counts (tq, te) the parse left.
+__global__ __launch_bounds__(BLOCK) void ig_spans_kernel(Args A, long long *__restrict__ rs, long long *__restrict__ re)
+{
+    __shared__ u64 ws[BLOCK / 64];
+    if (A.D->verdict != KW_INGEST_OK) return;
+    const uint8_t *__restrict__ text = A.text;
+    const long long n = A.n, n_take = A.D->n_rows;
+    for (long long tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
+        const long long p = tile * TILE + (long long)threadIdx.x * 16;
+        const bool in = p < n;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (in) v = *(const uint4 *)(text + p);
+        const uint32_t qraw = in ? mask16(v, 0x22u) & (n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u) : 0u;
+        u64 total;
+        const u64 qb = block_scan((u64)__popc(qraw), ws, &total);
+        Lane L{};
+        if (in) L = lane_masks(text, n, p, A.final_, v, (uint32_t)((A.tq[tile] + qb) & 1ull));
+        const u64 before = block_scan((u64)(__popc(L.E) + L.vE), ws, &total);
+        if (!in) continue;   // (after the block's scans)
+        const long long ce = (long long)(A.te[tile] + before);   // records ended before the lane
+        const uint32_t pnl = ((L.nl << 1) | ((p == 0 || text[p - 1] == 0x0Au) ? 1u : 0u)) & 0xFFFFu;
+        uint32_t todo = L.valid & ~L.sb & pnl & ~L.nl & ~L.cr;
+        while (todo) {
+            const int k = __builtin_ctz(todo);
+            todo &= todo - 1u;
+            const long long r = ce + __popc(L.E & ((1u << k) - 1u));
+            if (r < n_take) rs[r] = p + k;
+        }
+        todo = L.E;
+        while (todo || L.vE) {
+            long long at, r;
+            if (todo) {
+                const int k = __builtin_ctz(todo);
+                todo &= todo - 1u;
+                at = p + k;
+                r = ce + __popc(L.E & ((1u << k) - 1u));
+            } else {
+                at = n;
+                r = ce + __popc(L.E);
+                L.vE = 0;
+            }
+            if (r < n_take) re[r] = (at > 0 && text[at - 1] == 0x0Du) ? at - 1 : at;
+        }
+    }
+}
+
 // s[0, m) equals lit (lower case) without regard to ASCII case
 __device__ __forceinline__ bool ieq(const uint8_t *__restrict__ s, long long m, const char *lit, int len)
 {
@@ -657,6 +709,11 @@ struct kw_ingest {
     size_t stage_cap[2] = {0, 0};
     ig::Buf text;                  // kw_ingest_upload's device copy of a window
     hipStream_t stream = nullptr;  // the last parse's
+    const uint8_t *ptext = nullptr;   // the last parse's text, its bytes and its final flag (kw_ingest_spans)
+    long long pn = 0;
+    int pfinal = 0;
+    ig::Buf spans;                 // the taken records' starts, then their ends
+    bool have_spans = false;
 };
 
 #define IGCHK(h, x)                                                                    \
@@ -751,7 +808,7 @@ extern "C" int kw_ingest_destroy(kw_ingest *h)
     if (!h) return KW_OK;
     (void)hipSetDevice(h->device);
     Buf *bufs[] = {&h->tiles, &h->cells, &h->coff, &h->cflw, &h->cfl, &h->arena, &h->aoff, &h->us, &h->kind,
-                   &h->col_buf, &h->col_off, &h->col_fl};
+                   &h->col_buf, &h->col_off, &h->col_fl, &h->spans};
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (h->d_na) (void)hipFree(h->d_na);
@@ -774,6 +831,7 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
 {
     if (!h) return KW_EINVAL;
     h->have = false;
+    h->have_spans = false;
     if (!n_rows || !consumed || !verdict || !bad_pos || n_bytes < 0 || n_bytes >= (int64_t)1 << 31 || max_rows < 1 ||
         (n_bytes > 0 && !d_text) || ((uintptr_t)d_text & 15u)) {
         h->err = "kw_ingest_parse: bad arguments";
@@ -880,6 +938,9 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     *n_rows = h->H->n_rows;
     *consumed = h->H->consumed;
     h->have = h->H->verdict == KW_INGEST_OK;
+    h->ptext = d_text;
+    h->pn = n;
+    h->pfinal = A.final_;
     return KW_OK;
 }
 
@@ -1032,6 +1093,64 @@ extern "C" int kw_ingest_copy_column(kw_ingest *h, int32_t col, uint8_t *bytes, 
     const int64_t nb = off[nr];
     if (nb > cap) { h->err = "kw_ingest_copy_column: the column holds " + std::to_string(nb) + " bytes"; return KW_EOVERFLOW; }
     if (nb) IGCHK(h, hipMemcpy(bytes, h->col_buf.p, (size_t)nb, hipMemcpyDeviceToHost));
+    return KW_OK;
+}
+
+extern "C" int kw_ingest_spans(kw_ingest *h, const int64_t **d_start, const int64_t **d_end, int64_t *n_rows,
+                               int32_t *ncols, const uint8_t **d_text, int64_t *n_bytes)
+{
+    IG_NEED_PARSE(h, "kw_ingest_spans");
+    if (!d_start || !d_end || !n_rows || !ncols || !d_text || !n_bytes) {
+        h->err = "kw_ingest_spans: bad arguments";
+        return KW_EINVAL;
+    }
+    const long long nr = h->H->n_rows;
+    if (!h->have_spans) {
+        IGCHK(h, hipSetDevice(h->device));
+        int rc;
+        if ((rc = ensure(h, h->spans, (size_t)(2 * nr + 2) * 8))) return rc;
+        if (nr) {
+            Args A{};
+            A.text = h->ptext;
+            A.n = h->pn;
+            A.ntiles = (h->pn + TILE - 1) / TILE;
+            A.final_ = h->pfinal;
+            A.ncols = h->ncols;
+            A.tq = (u64 *)h->tiles.p;
+            A.te = A.tq + (A.ntiles + 1);
+            A.D = h->D;
+            const int gcap = grid_cap();
+            const dim3 tgrid((unsigned)(A.ntiles < 1 ? 1 : (A.ntiles > gcap ? gcap : A.ntiles)));
+            hipLaunchKernelGGL(ig_spans_kernel, tgrid, dim3(BLOCK), 0, h->stream, A, (long long *)h->spans.p,
+                               (long long *)h->spans.p + nr);
+            IGCHK(h, hipGetLastError());
+        }
+        h->have_spans = true;
+    }
+    *d_start = (const int64_t *)h->spans.p;
+    *d_end = (const int64_t *)h->spans.p + nr;
+    *n_rows = nr;
+    *ncols = h->ncols;
+    *d_text = h->ptext;
+    *n_bytes = h->pn;
+    return KW_OK;
+}
+
+extern "C" int kw_ingest_copy_spans(kw_ingest *h, int64_t *start, int64_t *end)
+{
+    IG_NEED_PARSE(h, "kw_ingest_copy_spans");
+    const int64_t *ds, *de;
+    const uint8_t *dt;
+    int64_t nr, nb;
+    int32_t nc;
+    int rc;
+    if ((rc = kw_ingest_spans(h, &ds, &de, &nr, &nc, &dt, &nb))) return rc;
+    if (!nr) return KW_OK;
+    if (!start || !end) { h->err = "kw_ingest_copy_spans: bad arguments"; return KW_EINVAL; }
+    IGCHK(h, hipMemcpyAsync(start, ds, (size_t)nr * 8, hipMemcpyDeviceToHost, h->stream));
+    IGCHK(h, hipMemcpyAsync(end, de, (size_t)nr * 8, hipMemcpyDeviceToHost, h->stream));
+    IGCHK(h, hipStreamSynchronize(h->stream));
+    IGCHK(h, hipGetLastError());
     return KW_OK;
 }
 

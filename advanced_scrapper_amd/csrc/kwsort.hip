@@ -1,0 +1,617 @@
+// libkwmatch: the output sort on the device (include/kwsort.h) -- over the cells, flags and record spans an OK
+// kw_ingest_parse of a per-ticker file's body left in device memory: the time_unix keys, the verdict of the take
+// rule of kwsort.h, and the records laid out again in the order the host's np.argsort of the keys gives.
+//
+//   ks_rows_kernel    lane = row: the key from the time_unix cell (the canonical decimal form, inside int64), the
+//                     FORM condition over the row's cells, the text / not-NA witnesses of the row's block and
+//                     column, the record's bytes + 1 into the body's length.
+//   ks_check_kernel   lane = row: a key that does not exceed the row before (not ascending); lane = block x column:
+//                     the first one without a text witness that is not all NA.
+//   ks_len_kernel     lane = order entry: its range check; the record's bytes + 1, scanned inside a tile of 256.
+//   ks_scan_kernel    one block: the exclusive scan of the tiles' sums, the body's bytes.
+//   ks_add_kernel     lane = order entry: the sum of the tiles before its own onto its offset.
+//   ks_copy_kernel    lane = 16 body bytes, a wave = 1 to 16 KiB one after the other: the record of the wave's
+//                     first byte by binary search in the scanned offsets, once; a KiB that lies inside one
+//                     record's bytes is copied with one 16-byte load (at the source's own alignment) and one
+//                     16-byte store a lane; in the others the lanes search on between the records of the KiB's
+//                     first and last byte, and only a lane that holds a record's end goes byte by byte.
+// kw_sort_keys synchronises once; kw_sort_gather twice (the body's size is known after the scan, and with it the
+// range check's result: nothing is copied for a bad order).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "../../include/kwsort.h"
+#include "kwenv.hpp"
+
+namespace ks {
+
+typedef unsigned long long u64;
+constexpr int BLOCK = 256;
+constexpr int MAX_GRID = 2048;
+constexpr u64 NONE = ~0ull;
+constexpr uint32_t F_QUOTED = 1u, F_NA = 2u, F_TEXT = 4u, F_CANON = 8u;   // KWCSV_* (csrc/kwcsv.c)
+constexpr int COL_BITS = 12;                                              // ncols <= 4096 (kw_ingest_create)
+
+// a call's state on the device; copied to the host at each synchronisation
+struct Dev {
+    u64 first_key, first_form, first_dtype;   // the first offender of each condition (NONE)
+    u64 body_bytes;                           // the rows' bytes + 1 each
+    u64 total;                                // kw_sort_gather: the body's bytes
+    int not_asc, bad_order;
+};
+
+__device__ __forceinline__ u64 wave_min(u64 x)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u64 y = __shfl_xor(x, d, 64);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+__device__ __forceinline__ u64 wave_sum(u64 x)
+{
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+    return x;
+}
+
+// The int64 a cell of the canonical decimal form `0` or `-?[1-9][0-9]*` holds; false for any other cell.
+__device__ __forceinline__ bool parse_key(const uint8_t *__restrict__ s, long long len, long long *key)
+{
+    if (len < 1 || len > 20) return false;
+    int i = 0;
+    const bool neg = s[0] == '-';
+    if (neg) i = 1;
+    const int nd = (int)len - i;
+    if (nd < 1 || nd > 19) return false;
+    if (s[i] == '0') {
+        if (nd != 1 || neg) return false;
+        *key = 0;
+        return true;
+    }
+    u64 mag = 0;   // (19 digits stay below 2^64)
+    for (; i < (int)len; ++i) {
+        const uint32_t d = (uint32_t)s[i] - '0';
+        if (d > 9u) return false;
+        mag = mag * 10ull + d;
+    }
+    if (mag > (1ull << 63) - (neg ? 0ull : 1ull)) return false;
+    *key = (long long)(neg ? 0ull - mag : mag);
+    return true;
+}
+
+__global__ __launch_bounds__(BLOCK) void ks_rows_kernel(const uint8_t *__restrict__ cells,
+                                                        const long long *__restrict__ coff,
+                                                        const uint8_t *__restrict__ cfl,
+                                                        const long long *__restrict__ rs,
+                                                        const long long *__restrict__ re, long long n, int ncols, int ti,
+                                                        long long block_rows, long long *__restrict__ keys,
+                                                        uint8_t *__restrict__ btext, uint8_t *__restrict__ bnonna,
+                                                        Dev *__restrict__ D)
+{
+    const long long rounds = (n + BLOCK - 1) / BLOCK;   // (every lane of a wave makes the same trips)
+    for (long long q = blockIdx.x; q < rounds; q += gridDim.x) {
+        const long long r = q * BLOCK + threadIdx.x;
+        u64 ek = NONE, ef = NONE, bytes = 0;
+        if (r < n) {
+            const long long c0 = r * ncols;
+            long long key = 0;
+            {
+                const long long c = c0 + ti, s = coff[c];
+                if ((cfl[c] & (F_NA | F_QUOTED)) || !parse_key(cells + s, coff[c + 1] - s, &key)) ek = (u64)r;
+            }
+            keys[r] = key;
+            const long long blk = (r / block_rows) * ncols;
+            for (int c = 0; c < ncols; ++c) {
+                const uint32_t fl = cfl[c0 + c];
+                if (ef == NONE && (!(fl & F_CANON) || ((fl & F_NA) && coff[c0 + c + 1] != coff[c0 + c])))
+                    ef = ((u64)r << COL_BITS) | (u64)c;
+                if (c != ti) {
+                    if ((fl & F_TEXT) && !btext[blk + c]) btext[blk + c] = 1;
+                    if (!(fl & F_NA) && !bnonna[blk + c]) bnonna[blk + c] = 1;
+                }
+            }
+            bytes = (u64)(re[r] - rs[r] + 1);
+        }
+        if (__any((ek & ef) != NONE)) {   // (rare: one atomic a wave and condition)
+            ek = wave_min(ek);
+            ef = wave_min(ef);
+            if ((threadIdx.x & 63) == 0) {
+                if (ek != NONE) atomicMin(&D->first_key, ek);
+                if (ef != NONE) atomicMin(&D->first_form, ef);
+            }
+        }
+        bytes = wave_sum(bytes);
+        if ((threadIdx.x & 63) == 0 && bytes) atomicAdd(&D->body_bytes, bytes);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void ks_check_kernel(const long long *__restrict__ keys, long long n,
+                                                         const uint8_t *__restrict__ btext,
+                                                         const uint8_t *__restrict__ bnonna, long long nbc, int ncols,
+                                                         int ti, Dev *__restrict__ D)
+{
+    const long long step = (long long)gridDim.x * BLOCK, t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    for (long long r = t + 1; r < n; r += step)
+        if (keys[r] <= keys[r - 1] && !D->not_asc) D->not_asc = 1;
+    for (long long i = t; i < nbc; i += step)
+        if ((int)(i % ncols) != ti && !btext[i] && bnonna[i]) atomicMin(&D->first_dtype, (u64)i);
+}
+
+// exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
+__device__ __forceinline__ u64 block_scan(u64 x, u64 *ws, u64 *total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u64 inc = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 y = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += y;
+    }
+    __syncthreads();   // ws free again
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    u64 before = 0, all = 0;
+    for (int k = 0; k < BLOCK / 64; ++k) {
+        const u64 s = ws[k];
+        if (k < wv) before += s;
+        all += s;
+    }
+    *total = all;
+    return before + inc - x;
+}
+
+// A tile = BLOCK order entries: each one's range check and its record's bytes + 1, scanned inside the tile into
+// doff; the tile's sum to tsum[tile].
+__global__ __launch_bounds__(BLOCK) void ks_len_kernel(const long long *__restrict__ order, long long n, long long n_rows,
+                                                       const long long *__restrict__ rs,
+                                                       const long long *__restrict__ re, u64 *__restrict__ doff,
+                                                       u64 *__restrict__ tsum, Dev *__restrict__ D)
+{
+    __shared__ u64 ws[BLOCK / 64];
+    const long long ntiles = (n + BLOCK - 1) / BLOCK;
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {   // (block-uniform trip count)
+        const long long j = tile * BLOCK + threadIdx.x;
+        u64 len = 0;
+        if (j < n) {
+            const long long o = order[j];
+            if (o < 0 || o >= n_rows) {
+                if (!D->bad_order) D->bad_order = 1;
+            } else {
+                len = (u64)(re[o] - rs[o] + 1);
+            }
+        }
+        u64 total;
+        const u64 before = block_scan(len, ws, &total);
+        if (j < n) doff[j] = before;
+        if (threadIdx.x == 0) tsum[tile] = total;
+    }
+}
+
+// the exclusive scan of a[0, m) in place by one block (the tiles' sums: m = n / BLOCK); its sum to *total
+__global__ __launch_bounds__(BLOCK) void ks_scan_kernel(u64 *__restrict__ a, long long m, u64 *__restrict__ total)
+{
+    __shared__ u64 ws[BLOCK / 64];
+    u64 carry = 0;
+    for (long long i0 = 0; i0 < m; i0 += BLOCK) {   // (block-uniform trip count)
+        const long long i = i0 + threadIdx.x;
+        u64 all;
+        const u64 before = block_scan(i < m ? a[i] : 0ull, ws, &all);
+        if (i < m) a[i] = carry + before;
+        carry += all;
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// doff[j] += the sum of the tiles before j's; doff[n] = the body's bytes
+__global__ __launch_bounds__(BLOCK) void ks_add_kernel(u64 *__restrict__ doff, long long n, const u64 *__restrict__ tsum,
+                                                       const u64 *__restrict__ total)
+{
+    const long long step = (long long)gridDim.x * BLOCK, t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (t == 0) doff[n] = *total;
+    for (long long j = t; j < n; j += step) doff[j] += tsum[j / BLOCK];
+}
+
+typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));   // 16 bytes at any address
+
+// A lane's 16 bytes from out position x0 < total, its record among [lo, l2] (doff[lo] <= x0, the record of the
+// wave's last byte is l2): one 16-byte load where they lie inside one record's bytes, else byte by byte.
+__device__ __forceinline__ uint4 copy_lane(const uint8_t *__restrict__ text, const long long *__restrict__ rs,
+                                           const long long *__restrict__ order, const u64 *__restrict__ doff,
+                                           u64 total, u64 x0, long long lo, long long l2)
+{
+    long long s = lo, hi = l2 + 1;   // the last record with doff[s] <= x0
+    while (hi - s > 1) {
+        const long long mid = (s + hi) >> 1;
+        if (doff[mid] <= x0) s = mid; else hi = mid;
+    }
+    u64 seg_lo = doff[s], seg_end = doff[s + 1];
+    const uint8_t *src = text + rs[order[s]];
+    if (x0 + 16 < seg_end) {   // 16 bytes of one record (its '\n' stands at seg_end - 1)
+        const u32x4_u v = *(const u32x4_u *)(src + (x0 - seg_lo));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+    uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+    #pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const u64 x = x0 + k;
+        if (x < total) {
+            while (x >= seg_end) {   // (x < total = doff[n]: s + 1 <= n - 1)
+                ++s;
+                seg_lo = seg_end;
+                seg_end = doff[s + 1];
+                src = text + rs[order[s]];
+            }
+            const uint32_t b = (x == seg_end - 1 ? 0x0Au : (uint32_t)src[x - seg_lo]) << (8 * (k & 3));
+            if (k < 4) w0 |= b; else if (k < 8) w1 |= b; else if (k < 12) w2 |= b; else w3 |= b;
+        }
+    }
+    return make_uint4(w0, w1, w2, w3);
+}
+
+// out[doff[j], doff[j + 1]) = the bytes of record order[j], then '\n'; doff[n] = the body's bytes (what follows
+// them up to the next multiple of 16 is written as zeros).  Every order entry has passed ks_len_kernel's check.
+// A wave lays out `iters` KiB one after the other: it searches the record of its first byte once, and from then
+// on the record of a KiB's first byte is the record of the last KiB's last byte or the next one.
+__global__ __launch_bounds__(BLOCK) void ks_copy_kernel(const uint8_t *__restrict__ text,
+                                                        const long long *__restrict__ rs,
+                                                        const long long *__restrict__ order,
+                                                        const u64 *__restrict__ doff, long long n,
+                                                        uint8_t *__restrict__ out, int iters)
+{
+    const u64 total = doff[n];
+    const u64 wspan = (u64)iters << 10;
+    const u64 nspans = (total + wspan - 1) / wspan;
+    const u64 wv = (u64)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (a scalar)
+    const u64 lane16 = (u64)(threadIdx.x & 63) << 4;
+    for (u64 sp = (u64)blockIdx.x * (BLOCK / 64) + wv; sp < nspans; sp += (u64)gridDim.x * (BLOCK / 64)) {
+        u64 w0 = sp * wspan;                      // the first byte of the wave's next KiB (wave-uniform, as all below)
+        const u64 send = w0 + wspan, wend = send < total ? send : total;
+        long long lo = 0, hi = n;                 // the last record with doff[lo] <= w0
+        while (hi - lo > 1) {
+            const long long mid = (lo + hi) >> 1;
+            if (doff[mid] <= w0) lo = mid; else hi = mid;
+        }
+        u64 d0 = doff[lo], d1 = doff[lo + 1];
+        const uint8_t *src0 = text + rs[order[lo]];
+        while (w0 < wend) {
+            if (w0 >= d1) {                       // (one step at most; w0 < total = doff[n]: lo + 1 <= n - 1)
+                ++lo;
+                d0 = d1;
+                d1 = doff[lo + 1];
+                src0 = text + rs[order[lo]];
+            }
+            if (w0 + 1024 < d1) {
+                // whole KiBs inside the record's bytes (its '\n' stands at d1 - 1): one 16-byte load at the
+                // source's own alignment and one aligned store a lane and KiB
+                u64 m = (d1 - 1 - w0) >> 10;
+                const u64 room = (send - w0) >> 10;
+                if (m > room) m = room;
+                const uint8_t *src = src0 + (w0 - d0) + lane16;
+                uint8_t *dst = out + w0 + lane16;
+                #pragma unroll 4
+                for (u64 k = 0; k < m; ++k) {
+                    const u32x4_u v = *(const u32x4_u *)(src + (k << 10));
+                    *(uint4 *)(dst + (k << 10)) = make_uint4(v.x, v.y, v.z, v.w);
+                }
+                w0 += m << 10;
+                continue;
+            }
+            // a KiB with a record's end in it: the record of its last byte, by a galloping search from lo
+            const u64 wl = w0 + 1023 < total - 1 ? w0 + 1023 : total - 1;
+            long long a = lo, step = 1;
+            while (a + step < n && doff[a + step] <= wl) {
+                a += step;
+                step <<= 1;
+            }
+            long long b = a + step < n ? a + step : n;   // doff[a] <= wl < doff[b]
+            while (b - a > 1) {
+                const long long mid = (a + b) >> 1;
+                if (doff[mid] <= wl) a = mid; else b = mid;
+            }
+            const u64 x0 = w0 + lane16;
+            if (x0 < total) *(uint4 *)(out + x0) = copy_lane(text, rs, order, doff, total, x0, lo, a);
+            if (a != lo) {
+                lo = a;
+                d0 = doff[lo];
+                d1 = doff[lo + 1];
+                src0 = text + rs[order[lo]];
+            }
+            w0 += 1024;
+        }
+    }
+}
+
+struct Buf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+}  // namespace ks
+
+struct kw_sort {
+    int device = 0;
+    std::string err;
+    ks::Dev *D = nullptr;          // device
+    ks::Dev *H = nullptr;          // pinned host copy
+    ks::Buf keys, bflags, order, doff, tsum, out;
+    void *h_keys = nullptr, *h_out = nullptr;   // pinned
+    size_t h_keys_cap = 0, h_out_cap = 0;
+    hipEvent_t ev[9] = {};
+    float ms[4] = {0, 0, 0, 0};
+    float ms_keys_copy = 0;
+    // what the last taken kw_sort_keys saw (kw_sort_gather)
+    bool have = false;
+    const uint8_t *text = nullptr;
+    const int64_t *rs = nullptr, *re = nullptr;
+    long long n_rows = 0;
+    hipStream_t stream = nullptr;
+};
+
+#define KSCHK(h, x)                                                                    \
+    do {                                                                               \
+        hipError_t e_ = (x);                                                           \
+        if (e_ != hipSuccess) {                                                        \
+            (h)->err = std::string("HIP error ") + hipGetErrorString(e_) + " at " #x; \
+            return KW_EHIP;                                                            \
+        }                                                                              \
+    } while (0)
+
+namespace ks {
+
+// a device buffer of at least `bytes` (contents are not kept when it grows)
+static int ensure(kw_sort *h, Buf &b, size_t bytes)
+{
+    if (b.cap >= bytes && b.p) return KW_OK;
+    const size_t want = bytes + bytes / 4 + 256;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    KSCHK(h, hipMalloc(&b.p, want));
+    b.cap = want;
+    return KW_OK;
+}
+
+static int ensure_pinned(kw_sort *h, void **p, size_t *cap, size_t bytes)
+{
+    if (*cap >= bytes && *p) return KW_OK;
+    const size_t want = bytes + bytes / 4 + 4096;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    KSCHK(h, hipHostMalloc(p, want, hipHostMallocDefault));
+    *cap = want;
+    return KW_OK;
+}
+
+// The cap on every launch grid of a call: MAX_GRID, or the tests' KW_TEST_SORT_GRID in [1, MAX_GRID] (read per
+// call through kw_env: the kernels' loops then make several trips on a small file).
+static int grid_cap()
+{
+    if (const char *e = kw_env("KW_TEST_SORT_GRID")) {
+        char *end = nullptr;
+        const long g = strtol(e, &end, 10);
+        if (end != e && *end == '\0' && g >= 1 && g <= MAX_GRID) return (int)g;
+    }
+    return MAX_GRID;
+}
+
+static dim3 grid_for(long long items, int cap)
+{
+    long long g = (items + BLOCK - 1) / BLOCK;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return dim3((unsigned)g);
+}
+
+}  // namespace ks
+
+using namespace ks;
+
+extern "C" int kw_sort_create(int32_t device, kw_sort **out)
+{
+    if (!out) return KW_EINVAL;
+    *out = nullptr;
+    if (hipSetDevice(device) != hipSuccess) return KW_EHIP;
+    kw_sort *h = new kw_sort();
+    h->device = device;
+    bool ok = hipMalloc((void **)&h->D, sizeof(Dev)) == hipSuccess &&
+              hipHostMalloc((void **)&h->H, sizeof(Dev), hipHostMallocDefault) == hipSuccess;
+    for (auto &e : h->ev)
+        if (ok) ok = hipEventCreate(&e) == hipSuccess;
+    if (!ok) {
+        kw_sort_destroy(h);
+        return KW_EHIP;
+    }
+    *out = h;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_destroy(kw_sort *h)
+{
+    if (!h) return KW_OK;
+    (void)hipSetDevice(h->device);
+    Buf *bufs[] = {&h->keys, &h->bflags, &h->order, &h->doff, &h->tsum, &h->out};
+    for (Buf *b : bufs)
+        if (b->p) (void)hipFree(b->p);
+    if (h->D) (void)hipFree(h->D);
+    if (h->H) (void)hipHostFree(h->H);
+    if (h->h_keys) (void)hipHostFree(h->h_keys);
+    if (h->h_out) (void)hipHostFree(h->h_out);
+    for (auto &e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete h;
+    return KW_OK;
+}
+
+extern "C" const char *kw_sort_last_error(kw_sort *h) { return h ? h->err.c_str() : "null handle"; }
+
+extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t block_rows, const int64_t **keys,
+                            int64_t *n_rows, int64_t *body_bytes, int32_t *verdict, int64_t *bad_row, int32_t *bad_col,
+                            int32_t *ascending, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    h->have = false;
+    if (!ig || !keys || !n_rows || !body_bytes || !verdict || !bad_row || !bad_col || !ascending || block_rows < 1) {
+        h->err = "kw_sort_keys: bad arguments";
+        return KW_EINVAL;
+    }
+    *keys = nullptr;
+    *n_rows = *body_bytes = *bad_row = 0;
+    *verdict = KW_SORT_OK;
+    *bad_col = *ascending = 0;
+    hipStream_t st = (hipStream_t)stream;
+    KSCHK(h, hipSetDevice(h->device));
+    KSCHK(h, hipEventRecord(h->ev[0], st));
+    const int64_t *rs, *re, *coff;
+    const uint8_t *text, *cells, *cfl;
+    int64_t n, n_bytes, cell_bytes;
+    int32_t ncols;
+    if (kw_ingest_spans(ig, &rs, &re, &n, &ncols, &text, &n_bytes) != KW_OK ||
+        kw_ingest_cells(ig, &cells, &coff, &cfl, &cell_bytes) != KW_OK) {
+        h->err = std::string("kw_sort_keys: ") + kw_ingest_last_error(ig);
+        return KW_ESTATE;
+    }
+    if (n < 1 || time_col < 0 || time_col >= ncols) {
+        h->err = "kw_sort_keys: no rows, or no such column";
+        return KW_EINVAL;
+    }
+    const long long nblk = (n + block_rows - 1) / block_rows, nbc = nblk * ncols;
+    int rc;
+    if ((rc = ensure(h, h->keys, (size_t)n * 8)) || (rc = ensure(h, h->bflags, (size_t)nbc * 2)) ||
+        (rc = ensure_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8)))
+        return rc;
+    uint8_t *btext = (uint8_t *)h->bflags.p, *bnonna = btext + nbc;
+    Dev init;
+    memset(&init, 0, sizeof(init));
+    init.first_key = init.first_form = init.first_dtype = NONE;
+    *h->H = init;   // (pinned: the copy below reads it in stream order; the last call's copy back has finished)
+    const int gcap = grid_cap();
+    KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
+    KSCHK(h, hipMemsetAsync(btext, 0, (size_t)nbc * 2, st));
+    hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
+                       (const long long *)rs, (const long long *)re, (long long)n, (int)ncols, (int)time_col,
+                       (long long)block_rows, (long long *)h->keys.p, btext, bnonna, h->D);
+    hipLaunchKernelGGL(ks_check_kernel, grid_for(n > nbc ? n : nbc, gcap), dim3(BLOCK), 0, st,
+                       (const long long *)h->keys.p, (long long)n, (const uint8_t *)btext, (const uint8_t *)bnonna, nbc,
+                       (int)ncols, (int)time_col, h->D);
+    KSCHK(h, hipEventRecord(h->ev[1], st));
+    KSCHK(h, hipMemcpyAsync(h->h_keys, h->keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipEventRecord(h->ev[2], st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    KSCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[0], h->ev[1]));
+    KSCHK(h, hipEventElapsedTime(&h->ms_keys_copy, h->ev[1], h->ev[2]));
+    h->ms[1] = h->ms[2] = 0;
+    h->ms[3] = h->ms_keys_copy;
+    *n_rows = n;
+    const Dev &R = *h->H;
+    if (R.first_key != NONE) {
+        *verdict = KW_SORT_KEY;
+        *bad_row = (int64_t)R.first_key;
+        *bad_col = time_col;
+    } else if (R.first_form != NONE) {
+        *verdict = KW_SORT_FORM;
+        *bad_row = (int64_t)(R.first_form >> COL_BITS);
+        *bad_col = (int32_t)(R.first_form & ((1u << COL_BITS) - 1u));
+    } else if (R.first_dtype != NONE) {
+        *verdict = KW_SORT_DTYPE;
+        *bad_row = (int64_t)(R.first_dtype / (u64)ncols) * block_rows;
+        *bad_col = (int32_t)(R.first_dtype % (u64)ncols);
+    } else {
+        *keys = (const int64_t *)h->h_keys;
+        *body_bytes = (int64_t)R.body_bytes;
+        *ascending = R.not_asc ? 0 : 1;
+        h->have = true;
+        h->text = text;
+        h->rs = rs;
+        h->re = re;
+        h->n_rows = n;
+        h->stream = st;
+    }
+    return KW_OK;
+}
+
+extern "C" int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const uint8_t **out, int64_t *out_bytes)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->have) {
+        h->err = "kw_sort_gather: no kw_sort_keys that was taken";
+        return KW_ESTATE;
+    }
+    if (!order || !out || !out_bytes || n < 1 || n > h->n_rows) {
+        h->err = "kw_sort_gather: bad arguments";
+        return KW_EINVAL;
+    }
+    *out = nullptr;
+    *out_bytes = 0;
+    hipStream_t st = h->stream;
+    KSCHK(h, hipSetDevice(h->device));
+    int rc;
+    const long long ntiles = (n + BLOCK - 1) / BLOCK;
+    if ((rc = ensure(h, h->order, (size_t)n * 8)) || (rc = ensure(h, h->doff, (size_t)(n + 1) * 8)) ||
+        (rc = ensure(h, h->tsum, (size_t)ntiles * 8)))
+        return rc;
+    const int gcap = grid_cap();
+    h->H->total = 0;
+    h->H->bad_order = 0;
+    KSCHK(h, hipEventRecord(h->ev[3], st));
+    KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
+    KSCHK(h, hipMemcpyAsync(h->order.p, order, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    KSCHK(h, hipEventRecord(h->ev[4], st));
+    hipLaunchKernelGGL(ks_len_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, (const long long *)h->order.p, (long long)n,
+                       h->n_rows, (const long long *)h->rs, (const long long *)h->re, (u64 *)h->doff.p, (u64 *)h->tsum.p,
+                       h->D);
+    hipLaunchKernelGGL(ks_scan_kernel, dim3(1), dim3(BLOCK), 0, st, (u64 *)h->tsum.p, ntiles, &h->D->total);
+    hipLaunchKernelGGL(ks_add_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, (u64 *)h->doff.p, (long long)n,
+                       (const u64 *)h->tsum.p, (const u64 *)&h->D->total);
+    KSCHK(h, hipEventRecord(h->ev[5], st));
+    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    if (h->H->bad_order) {
+        h->err = "kw_sort_gather: an order entry outside [0, n_rows)";
+        return KW_EINVAL;
+    }
+    const u64 total = h->H->total;
+    if (total >= 1ull << 31) {
+        h->err = "kw_sort_gather: the body holds " + std::to_string(total) + " bytes";
+        return KW_EOVERFLOW;
+    }
+    if ((rc = ensure(h, h->out, (size_t)total + 32)) ||
+        (rc = ensure_pinned(h, &h->h_out, &h->h_out_cap, (size_t)total + 16)))
+        return rc;
+    KSCHK(h, hipEventRecord(h->ev[6], st));
+    // the KiB a wave lays out: one while the body gives every wave of a full grid something to do, up to 16 beyond
+    const long long kib = (long long)((total + 1023) >> 10), waves = (long long)gcap * (BLOCK / 64);
+    long long iters = (kib + waves - 1) / waves;
+    iters = iters < 1 ? 1 : (iters > 16 ? 16 : iters);
+    const long long spans = (kib + iters - 1) / iters;
+    hipLaunchKernelGGL(ks_copy_kernel, grid_for(spans * 64, gcap), dim3(BLOCK), 0, st, h->text,
+                       (const long long *)h->rs, (const long long *)h->order.p, (const u64 *)h->doff.p, (long long)n,
+                       (uint8_t *)h->out.p, (int)iters);
+    KSCHK(h, hipEventRecord(h->ev[7], st));
+    KSCHK(h, hipMemcpyAsync(h->h_out, h->out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipEventRecord(h->ev[8], st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    float a = 0, b = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->ev[3], h->ev[4]));
+    KSCHK(h, hipEventElapsedTime(&h->ms[1], h->ev[4], h->ev[5]));
+    KSCHK(h, hipEventElapsedTime(&h->ms[2], h->ev[6], h->ev[7]));
+    KSCHK(h, hipEventElapsedTime(&b, h->ev[7], h->ev[8]));
+    h->ms[3] = h->ms_keys_copy + a + b;
+    *out = (const uint8_t *)h->h_out;
+    *out_bytes = (int64_t)total;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_last_ms(kw_sort *h, float *ms, int32_t n)
+{
+    if (!h || !ms || n < 0) return KW_EINVAL;
+    for (int k = 0; k < n && k < 4; ++k) ms[k] = h->ms[k];
+    return KW_OK;
+}

@@ -521,6 +521,14 @@ class DeviceIngest:
         self._check(self._n.lib().kw_ingest_copy_column(self.h, int(col), _p(buf), cap, _p(off), _p(fl)))
         return buf[:int(off[n])], off, fl[:n]
 
+    def copy_spans(self):
+        """The taken records' byte spans in the parsed text: ``(start int64[n], end int64[n])``, the terminator
+        excluded (kwcsv_parse's rspan); the text must still stand in device memory."""
+        start = np.zeros(max(self.n_rows, 1), dtype=np.int64)
+        end = np.zeros(max(self.n_rows, 1), dtype=np.int64)
+        self._check(self._n.lib().kw_ingest_copy_spans(self.h, _p(start), _p(end)))
+        return start[:self.n_rows], end[:self.n_rows]
+
     def last_ms(self):
         """Device times (ms) of the last parse: classify, cells, arena (+ dates), all."""
         v = np.zeros(4, dtype=np.float32)

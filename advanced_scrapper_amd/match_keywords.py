@@ -25,13 +25,15 @@ import hashlib
 import json
 import os
 import sys
+import threading
+import time
 from typing import Dict, List, Optional
 
 import numpy as np
 import pandas as pd
 from dateutil import parser
 
-from . import egress, ingest
+from . import egress, ingest, sortfiles
 from .ingest import DeviceChunk, NativeChunk, ShardChunk
 from .dates import parse_date
 from .kb import (ATTRIBUTES, compile_kb, extract_time_periods, is_within_period,  # noqa: F401 (re-export)
@@ -603,10 +605,11 @@ def _sort_native(file_path) -> bool:
     return True
 
 
-def sort_matched_csv(file_path):
-    """Re-read, sort by ``time_unix`` (pandas default quicksort) and rewrite (match_keywords.py:195-217)."""
+def _sort_host(file_path):
+    """sort_matched_csv on the host: :func:`_sort_native`, then pandas (match_keywords.py:195-217)."""
     try:
         if _sort_native(file_path):
+            sortfiles.note('native')
             print(f"Sorted and saved: {file_path}")
             return
         frame = pd.read_csv(file_path)
@@ -616,9 +619,32 @@ def sort_matched_csv(file_path):
         ordered = frame.sort_values('time_unix', ascending=True)
         ordered['time_unix'] = ordered['time_unix'].astype(int)
         ordered.to_csv(file_path, index=False)
+        sortfiles.note('pandas')
         print(f"Sorted and saved: {file_path}")
     except Exception as exc:  # noqa: BLE001 - mirrors the reference
         print(f"Error processing {file_path}: {str(exc)}")
+
+
+# run()'s sharded form (--gpus N) keeps every file on the host routes: set on the thread that runs that loop only
+_SORT_HOST_ONLY = threading.local()
+
+
+def sort_matched_csv(file_path):
+    """Re-read, sort by ``time_unix`` (pandas default quicksort) and rewrite (match_keywords.py:195-217): on the
+    device where the rewrite is provably a permutation of the file's records (sortfiles.sort_file; a ``KwError``
+    of that route is raised, the file untouched), else :func:`_sort_native`, else pandas.  ``KW_SORT_DEVICE=0``
+    skips the device route."""
+    if not getattr(_SORT_HOST_ONLY, 'on', False) and sortfiles.sort_on_device():
+        from ._native import KwError
+        try:
+            if sortfiles.sort_file(file_path):
+                print(f"Sorted and saved: {file_path}")
+                return
+        except KwError:
+            raise
+        except Exception:  # noqa: BLE001 - not this route's file: the host routes take it, or report it
+            pass
+    _sort_host(file_path)
 
 
 # --------------------------------------------------------------------- CLI
@@ -762,16 +788,26 @@ def run(args, rank: int, world: int, device, backend, matcher=None):
                 matcher = get_matcher(processed, device, [field_str(v) for v in chunk['article_text'].tolist()])
             matcher = _write_chunk(args.source, chunk, processed, matcher)
         print("All matched CSV files have been processed.")
+        sortfiles.reset_stats()
+        rest = []
         for name in os.listdir(out_dir):
             # the files this run created are sorted from their write index (no re-read when already in
             # time order); the others take the reference's re-read, sort and rewrite
             if _RUN.finish(name):
                 print(f"Sorted and saved: {out_dir}/{name}")
             else:
-                sort_matched_csv(f"{out_dir}/{name}")
+                rest.append(f"{out_dir}/{name}")
+        # one sorter for all of them: it knows the files to come and reads the next one while this one is on
+        # the device
+        t0 = time.perf_counter()
+        sortfiles.plan(rest, device)
+        for path in rest:
+            sort_matched_csv(path)
+        sortfiles.LAST_STATS['loop_s'] = time.perf_counter() - t0
         print("All matched CSV files have been sorted by date and time.")
     finally:
         _RUN = None
+        sortfiles.close()
     return 0
 
 
@@ -785,6 +821,7 @@ def _run_sharded(args, processed, exchange, device, out_dir, matcher=None):
     global _RUN
     rank, world = exchange.rank, exchange.world
     _RUN = egress.RunFiles(out_dir)          # every rank lists the directory before any rank writes
+    _SORT_HOST_ONLY.on = True                # (the device route of the sort is the single GPU's)
     try:
         for chunk in ingest.read_chunks_sharded(args.articles, args.chunksize, rank, world, exchange.allreduce_min):
             if isinstance(chunk, ShardChunk):
@@ -813,6 +850,7 @@ def _run_sharded(args, processed, exchange, device, out_dir, matcher=None):
         exchange.barrier()
     finally:
         _RUN = None
+        _SORT_HOST_ONLY.on = False
     if rank == 0:
         print("All matched CSV files have been sorted by date and time.")
     return 0

@@ -1,0 +1,355 @@
+"""sort_matched_csv on the device (include/kwsort.h; reference match_keywords.py:195-217).
+
+``sort_file(path)`` re-reads one per-ticker CSV file, sorts it by ``time_unix`` and writes it again with the
+bytes pandas' ``read_csv`` -> ``sort_values('time_unix')`` -> ``to_csv`` would write -- where that is provably
+a permutation of the file's own records (the take rule of kwsort.h): the body goes through a pinned staging
+window to the GPU, ``kw_ingest_parse`` tokenizes it, ``kw_sort_keys`` reads the keys and the verdict, the host
+makes pandas' own ``np.argsort(keys, kind='quicksort')`` call (ties keep pandas' order), and ``kw_sort_gather``
+lays the records out in that order.  No cell is rendered on this route: every other file is refused, untouched,
+and stays with ``match_keywords._sort_native`` and pandas.
+
+``LAST_STATS`` counts the files by route (``device``: rewritten here, ``unchanged``: found in order here,
+``native`` and ``pandas``: the host routes, noted by ``match_keywords.sort_matched_csv``), the refusals by
+reason, the bytes the device route took and its summed device times.
+"""
+from __future__ import annotations
+
+import atexit
+import ctypes
+import os
+import time
+from typing import Dict, Optional
+
+import numpy as np
+
+from . import egress, ingest
+
+SORT_DEVICE_DEFAULT = '1'
+_HEAD_PROBE = 1 << 16              # the header line lies within the file's first bytes, or the file is refused
+INGEST_VERDICTS = ('OK', 'NUL', 'UTF8', 'QUOTE', 'CR', 'BLANK', 'FIELDS', 'ROWS')
+SORT_VERDICTS = ('OK', 'KEY', 'FORM', 'DTYPE')
+
+
+def _new_stats() -> dict:
+    return {'device': 0, 'unchanged': 0, 'native': 0, 'pandas': 0, 'refused': {}, 'bytes': 0, 'gather_bytes': 0,
+            'prefetched': 0,
+            'ms': {'parse': 0.0, 'keys': 0.0, 'scan': 0.0, 'gather': 0.0, 'copies': 0.0},
+            'wall_s': {'read': 0.0, 'device': 0.0, 'argsort': 0.0, 'write': 0.0}, 'last': None}
+
+
+LAST_STATS = _new_stats()
+
+
+def reset_stats() -> dict:
+    global LAST_STATS
+    LAST_STATS = _new_stats()
+    return LAST_STATS
+
+
+def note(route: str) -> None:
+    """A file that took a host route (``native`` / ``pandas``)."""
+    LAST_STATS[route] += 1
+
+
+def sort_on_device() -> bool:
+    """``KW_SORT_DEVICE=0`` keeps every file on the host routes; ``KW_SORT_DEVICE=1`` asks for the device route
+    (profiles/e2e_sort.json holds the measurement behind the default)."""
+    return os.environ.get('KW_SORT_DEVICE', SORT_DEVICE_DEFAULT) != '0'
+
+
+class _Job:
+    """One file on its way to the device: the header's decisions, the staging slot its body is read into."""
+
+    def __init__(self, path):
+        self.path = path
+        self.refusal: Optional[str] = None
+        self.future = None
+        self.dev = self.view = self.names = None
+        self.slot = self.pos = self.nbody = 0
+        self.head = (b'', b'')         # the header line as the file holds it, and as the csv writer renders it
+
+    def read(self):
+        """The body into the staging window (runs on the reader thread: no device call)."""
+        t0 = time.perf_counter()
+        with open(self.path, 'rb', buffering=0) as fh:
+            fh.seek(self.pos)
+            mv, got = memoryview(self.view), 0
+            while got < self.nbody:
+                k = fh.readinto(mv[got:])
+                if not k:
+                    raise OSError(f'{self.path}: the file shrank while it was read')
+                got += k
+        return time.perf_counter() - t0
+
+
+class DeviceSorter:
+    """One ``kw_sort`` handle and the ``DeviceIngest`` handles (keyed by the header's shape) of one device and
+    host thread.  ``sort_file(path, next_path)`` sorts a file; with ``next_path`` the next file's body is read
+    into the other staging slot by a background thread while this one is on the device."""
+
+    def __init__(self, device: int = 0):
+        from . import _native
+        self._n = _native
+        self.device = int(device)
+        self.h = None
+        self._ingests: Dict[tuple, ingest.DeviceIngest] = {}
+        self._slot: Dict[tuple, int] = {}
+        self._ahead: Optional[_Job] = None
+        self._pool = None
+        h = ctypes.c_void_p()
+        rc = _native.lib().kw_sort_create(self.device, ctypes.byref(h))
+        if rc != _native.KW_OK:
+            raise _native.KwError(rc, 'kw_sort_create: no device')
+        self.h = h
+
+    def _check(self, rc: int) -> None:
+        if rc != self._n.KW_OK:
+            msg = self._n.lib().kw_sort_last_error(self.h)
+            raise self._n.KwError(rc, msg.decode('utf-8', 'replace') if msg else '')
+
+    # ------------------------------------------------------------------ the header's decisions (no device work)
+    def _prepare(self, path: str) -> _Job:
+        job = _Job(path)
+        size = os.path.getsize(path)
+        with open(path, 'rb') as fh:
+            head = fh.read(_HEAD_PROBE)
+        if size > len(head) and b'\n' not in head:
+            job.refusal = 'header'
+            return job
+        try:
+            names, _line, pos = ingest._split_header(head)
+        except UnicodeDecodeError:
+            job.refusal = 'header'
+            return job
+        ncols = len(names)
+        if ncols == 0:
+            job.refusal = 'header-empty'
+        elif len(set(names)) != ncols:
+            job.refusal = 'header-duplicate'
+        elif 'time_unix' not in names:
+            job.refusal = 'header-no-time_unix'
+        elif ncols < 6 or not all(c in names for c in ingest.NEEDED):
+            job.refusal = 'header-columns'
+        elif pos >= size:
+            job.refusal = 'header-only'
+        elif size - pos >= ingest.MAX_WINDOW:
+            job.refusal = 'size'
+        if job.refusal is None:
+            line = egress._join(list(names))
+            if line is None:
+                job.refusal = 'header'
+        if job.refusal is not None:
+            return job
+        job.names, job.pos, job.nbody = names, pos, size - pos
+        job.head = (head[:pos], line.encode('utf-8'))
+        key = (ncols, tuple(names.index(c) for c in ingest.NEEDED))
+        dev = self._ingests.get(key)
+        if dev is None:
+            dev = self._ingests[key] = ingest.DeviceIngest(self.device, ncols, key[1])
+        job.slot = self._slot[key] = 1 - self._slot.get(key, 1)
+        job.dev = dev
+        job.view = dev.stage(job.slot, job.nbody)
+        return job
+
+    def _start(self, path: str) -> _Job:
+        job = self._prepare(path)
+        if job.refusal is None:
+            if self._pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='kw-sort')
+            job.future = self._pool.submit(job.read)
+        return job
+
+    def _drop_ahead(self):
+        job, self._ahead = self._ahead, None
+        if job is not None and job.future is not None:
+            try:
+                job.future.result()
+            except Exception:   # noqa: BLE001 - that file is read again when its turn comes
+                pass
+
+    # ------------------------------------------------------------------ the two device calls
+    def keys(self, dev: ingest.DeviceIngest, time_col: int, block_rows: int = egress.PANDAS_BLOCK_ROWS):
+        """kw_sort_keys over ``dev``'s last parse: ``(verdict, bad_row, bad_col, keys, body_bytes, ascending)``;
+        ``keys`` (None unless the verdict is OK) is a view of the handle's pinned buffer, valid until the next call."""
+        keys_p, nr, body = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
+        sv, bad_row, bad_col, asc = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._n.lib().kw_sort_keys(self.h, dev.h, int(time_col), int(block_rows), ctypes.byref(keys_p),
+                                               ctypes.byref(nr), ctypes.byref(body), ctypes.byref(sv),
+                                               ctypes.byref(bad_row), ctypes.byref(bad_col), ctypes.byref(asc), None))
+        keys = None
+        if sv.value == self._n.KW_SORT_OK:
+            keys = np.frombuffer((ctypes.c_int64 * nr.value).from_address(keys_p.value), dtype=np.int64)
+        return sv.value, int(bad_row.value), int(bad_col.value), keys, int(body.value), bool(asc.value)
+
+    def gather(self, order) -> np.ndarray:
+        """kw_sort_gather: the body in ``order`` as a uint8 view of the handle's pinned buffer (valid until the
+        next gather)."""
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        out_p, out_n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._n.lib().kw_sort_gather(self.h, self._n.ptr(order), len(order), ctypes.byref(out_p),
+                                                 ctypes.byref(out_n)))
+        return np.frombuffer((ctypes.c_uint8 * out_n.value).from_address(out_p.value), dtype=np.uint8)
+
+    def last_ms(self) -> dict:
+        v = np.zeros(4, dtype=np.float32)
+        self._check(self._n.lib().kw_sort_last_ms(self.h, self._n.ptr(v), 4))
+        return dict(zip(('keys', 'scan', 'gather', 'copies'), (float(x) for x in v)))
+
+    # ------------------------------------------------------------------ one file
+    def sort_file(self, path: str, next_path: Optional[str] = None) -> bool:
+        """Sort ``path`` on the device; ``False`` (the file untouched): the file is left to the host routes.
+        A ``KW_E*`` error raises ``KwError``, the file untouched."""
+        stats = LAST_STATS
+        n = self._n
+        L = n.lib()
+        job = self._ahead
+        if job is not None and job.path == path:
+            self._ahead = None
+            stats['prefetched'] += 1
+        else:
+            self._drop_ahead()
+            job = self._prepare(path)
+        try:
+            if job.refusal is not None:
+                return self._refuse(job.refusal)
+            stats['wall_s']['read'] += job.future.result() if job.future is not None else job.read()
+        finally:
+            # the next file's body, into the other slot, while this one is on the device
+            if next_path is not None:
+                try:
+                    self._ahead = self._start(next_path)
+                except OSError:   # (that file's own turn reports it)
+                    self._ahead = None
+        t0 = time.perf_counter()
+        dev, nbody = job.dev, job.nbody
+        d_text = dev.upload(job.slot, 0, nbody)
+        max_rows = int(np.count_nonzero(job.view == 0x0A)) + 1     # (while the upload runs)
+        verdict, _bad, n_rows, consumed = dev.parse(d_text, nbody, True, max_rows)
+        if verdict != n.KW_INGEST_OK:
+            return self._refuse('ingest-' + INGEST_VERDICTS[verdict])
+        if n_rows < 1 or consumed != nbody:
+            return self._refuse('ingest-EMPTY')
+        ms = dev.last_ms()
+        sv, bad_row, bad_col, keys, body, asc = self.keys(dev, job.names.index('time_unix'))
+        if sv != n.KW_SORT_OK:
+            stats['last'] = {'verdict': SORT_VERDICTS[sv], 'row': bad_row, 'col': bad_col}
+            return self._refuse('sort-' + SORT_VERDICTS[sv], keep_last=True)
+        t1 = time.perf_counter()
+        order = None
+        if not asc:
+            order = np.argsort(keys, kind='quicksort')       # pandas' own call: its order among equal keys
+            if (order == np.arange(n_rows)).all():
+                order = None
+        t2 = time.perf_counter()
+        raw_head, head = job.head
+        # The file already holds the result when the rows are in order, the header stands as the writer renders
+        # it, the body ends with '\n' and holds the records' bytes + 1 each: with the last record terminated every
+        # record has a terminator of one byte at least, so the equality leaves no room for a "\r\n" or an empty
+        # line.  (Without the last byte's test an extra terminator byte and a missing final '\n' cancel out.)
+        if (order is None and raw_head == head and body == nbody and int(job.view[nbody - 1]) == 0x0A):
+            self._account(stats, ms, nbody, t0, t1, t2, t2, 'unchanged')
+            return True
+        if order is None:
+            order = np.arange(n_rows, dtype=np.int64)
+        out = self.gather(order)
+        t3 = time.perf_counter()
+        # (the whole body is on the host: only now is the file opened for writing)
+        with open(path, 'wb') as fh:
+            fh.write(head)
+            fh.write(out)
+        self._account(stats, ms, nbody, t0, t1, t2, t3, 'device')
+        stats['gather_bytes'] += len(out)
+        stats['wall_s']['write'] += time.perf_counter() - t3
+        return True
+
+    def _account(self, stats, parse_ms, nbody, t0, t1, t2, t3, route):
+        stats[route] += 1
+        stats['bytes'] += nbody
+        stats['ms']['parse'] += parse_ms['all']
+        for name, v in self.last_ms().items():
+            stats['ms'][name] += v
+        stats['wall_s']['device'] += (t1 - t0) + (t3 - t2)
+        stats['wall_s']['argsort'] += t2 - t1
+        stats['last'] = {'verdict': 'OK', 'route': route}
+
+    @staticmethod
+    def _refuse(reason: str, keep_last: bool = False) -> bool:
+        ref = LAST_STATS['refused']
+        ref[reason] = ref.get(reason, 0) + 1
+        if not keep_last:
+            LAST_STATS['last'] = {'verdict': reason}
+        return False
+
+    def close(self):
+        self._drop_ahead()
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+        if self.h is not None and self.h.value:
+            self._n.lib().kw_sort_destroy(self.h)
+        self.h = None
+        for dev in self._ingests.values():
+            dev.close()
+        self._ingests = {}
+
+
+_SORTER: Optional[DeviceSorter] = None
+_AVAILABLE: Optional[bool] = None
+_PLAN: Dict[str, str] = {}          # a file run() is about to sort -> the one it sorts next
+_PLAN_DEVICE: Optional[int] = None
+
+
+def plan(paths, device: Optional[int] = None) -> None:
+    """The files the caller sorts next, in order, one :func:`sort_file` call each: while one is on the device the
+    one after it is read ahead.  :func:`close` forgets the plan."""
+    global _PLAN, _PLAN_DEVICE
+    paths = list(paths)
+    _PLAN = dict(zip(paths, paths[1:]))
+    _PLAN_DEVICE = device
+
+
+def available() -> bool:
+    """The library is built and a device answers (decided once a process)."""
+    global _AVAILABLE
+    if _AVAILABLE is None:
+        try:
+            from . import _native
+            _AVAILABLE = _native.device_count() > 0
+        except Exception:   # noqa: BLE001 - no library, no runtime: the host routes
+            _AVAILABLE = False
+    return _AVAILABLE
+
+
+def sorter(device: Optional[int] = None) -> Optional[DeviceSorter]:
+    """The process's sorter (created on first use, closed by :func:`close` or at exit); ``None``: no device."""
+    global _SORTER
+    if not available():
+        return None
+    device = 0 if device is None else int(device)
+    if _SORTER is not None and _SORTER.device != device:
+        close()
+    if _SORTER is None:
+        _SORTER = DeviceSorter(device)
+    return _SORTER
+
+
+def close() -> None:
+    global _SORTER, _PLAN, _PLAN_DEVICE
+    _PLAN, _PLAN_DEVICE = {}, None
+    s, _SORTER = _SORTER, None
+    if s is not None:
+        s.close()
+
+
+atexit.register(close)
+
+
+def sort_file(path: str, next_path: Optional[str] = None, device: Optional[int] = None) -> bool:
+    """:meth:`DeviceSorter.sort_file` on the process's sorter; ``False`` without a device or the library."""
+    if next_path is None:
+        next_path = _PLAN.pop(path, None)
+    s = sorter(_PLAN_DEVICE if device is None else device)
+    if s is None:
+        return DeviceSorter._refuse('no-device')
+    return s.sort_file(path, next_path)

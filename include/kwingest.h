@@ -113,6 +113,18 @@ int kw_ingest_copy_arena(kw_ingest *h, uint8_t *arena, int64_t *off);
  * (KW_EOVERFLOW when the column holds more than cap bytes; cell_bytes always suffices). */
 int kw_ingest_copy_column(kw_ingest *h, int32_t col, uint8_t *bytes, int64_t cap, int64_t *off, uint8_t *fl);
 
+/* After an OK parse, while its text still stands in device memory: every taken record's byte span in that text as
+ * kwcsv_parse's rspan gives it -- (*d_start)[r] the record's first byte, (*d_end)[r] the byte after its last, the
+ * terminator ("\n" or "\r\n") excluded; records of no bytes are skipped by the take rule, so a start is not the
+ * previous end + 1.  n_rows int64 each, device memory of the handle, written on the parse's stream (asynchronous:
+ * read them on that stream or after synchronising it).  Also the parse's own shape: *n_rows, *ncols, *d_text and
+ * *n_bytes. */
+int kw_ingest_spans(kw_ingest *h, const int64_t **d_start, const int64_t **d_end, int64_t *n_rows, int32_t *ncols,
+                    const uint8_t **d_text, int64_t *n_bytes);
+
+/* kw_ingest_spans into host arrays start[n_rows], end[n_rows]. */
+int kw_ingest_copy_spans(kw_ingest *h, int64_t *start, int64_t *end);
+
 /* Device times (ms) of the last parse, up to 4 values: [0] classify (quote counts, NUL, UTF-8, their scan),
  * [1] cells (counts, scans, offsets and the kept bytes, the verdict, the flags), [2] arena + dates, [3] all. */
 int kw_ingest_last_ms(kw_ingest *h, float *ms, int32_t n);

@@ -1,0 +1,79 @@
+/*
+ * kwsort.h — C-ABI of the output sort on the GPU (libkwmatch.so, advanced_scrapper_amd/csrc/kwsort.hip).
+ *
+ * What it replaces.  sort_matched_csv re-reads a per-ticker CSV file, sorts it by `time_unix` and writes it again
+ * (reference match_keywords.py:195-217).  The host route (match_keywords._sort_native) tokenizes the file and
+ * then slices, converts and joins it row by row in Python.  Here the file's body is parsed by kw_ingest_parse
+ * (kwingest.h), kw_sort_keys reads the keys and decides whether the rewrite is provably a permutation of the
+ * file's own records, the host makes pandas' own np.argsort(kind='quicksort') call on the keys (its order among
+ * equal keys cannot be reproduced by another sort), and kw_sort_gather lays the records out in that order.  No
+ * cell is rendered: a file that would need it is refused and stays with the host routes.
+ *
+ * The take rule (restated in tests/sort_rule.py).  Over the rows of an OK final parse that consumed
+ * the whole text, the verdict is the first of these conditions, in this order, that has an offender:
+ *   KW_SORT_KEY    a row whose time_unix cell is NA or QUOTED, or is not the canonical decimal form `0` or
+ *                  `-?[1-9][0-9]*` (so `-0`, `+1`, `01`, ` 1`, `1.0`, `1e3` and the empty cell offend), or whose
+ *                  value lies outside int64.  bad_row: the first such row; bad_col: the time_unix column.
+ *   KW_SORT_FORM   a row with a cell that lacks KWCSV_CANON, or an NA cell of non-zero length (an unquoted empty
+ *                  cell is NA and CANON and passes: pandas writes NaN back as the empty cell).  bad_row: the first
+ *                  such row; bad_col: its first such cell.
+ *   KW_SORT_DTYPE  over the blocks of block_rows consecutive rows (the last one shorter): a column other than
+ *                  time_unix in which no cell of the block carries KWCSV_TEXT and not every cell of it is NA
+ *                  (pandas infers a column's type block by block and would render such a block's cells again).
+ *                  bad_row: the block's first row, of the first such block; bad_col: its lowest such column.
+ * A row that passes is written by pandas byte for byte as it stands in the file, with "\n" as its terminator.
+ *
+ * Conventions as kwingest.h: 0 or a negative KW_E* code; kw_sort_last_error gives the message; one handle per
+ * device and host thread.  The kw_ingest handle's parse, and the text it parsed, must stand from kw_sort_keys
+ * until the last kw_sort_gather of that file.
+ */
+#ifndef KWSORT_H
+#define KWSORT_H
+
+#include <stdint.h>
+
+#include "kwingest.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct kw_sort kw_sort;
+
+/* verdicts of kw_sort_keys, in the order the conditions are tested */
+#define KW_SORT_OK 0
+#define KW_SORT_KEY 1
+#define KW_SORT_FORM 2
+#define KW_SORT_DTYPE 3
+
+int kw_sort_create(int32_t device, kw_sort **out);
+
+/* The keys and the verdict of the rows of ig's last parse (OK, final, the whole text consumed; at least one row).
+ * time_col: the time_unix column; block_rows >= 1.  Returns after the device finished: *verdict, for another
+ * verdict than KW_SORT_OK *bad_row and *bad_col, and for KW_SORT_OK *keys (n_rows int64 in a pinned host buffer
+ * of the handle, valid until the next kw_sort_keys), *body_bytes (the bytes of the body that holds every row
+ * once: each record's bytes + 1) and *ascending (1: the keys increase strictly from row to row, the rows are in
+ * order as they stand).  stream: the parse's stream. */
+int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t block_rows, const int64_t **keys,
+                 int64_t *n_rows, int64_t *body_bytes, int32_t *verdict, int64_t *bad_row, int32_t *bad_col,
+                 int32_t *ascending, void *stream);
+
+/* After a kw_sort_keys with the verdict KW_SORT_OK: the body whose record j is the text's record order[j] followed
+ * by "\n", j = 0 .. n - 1 (order: a host array; 1 <= n <= n_rows of the parse; an entry may repeat).  Every
+ * entry is checked on the device before anything is copied: one outside [0, n_rows) gives KW_EINVAL, a body of
+ * 2^31 bytes or more KW_EOVERFLOW, and neither writes the output buffer.  *out: a pinned host buffer of the
+ * handle holding *out_bytes bytes, valid until the next kw_sort_gather. */
+int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const uint8_t **out, int64_t *out_bytes);
+
+/* Device times (ms) of the last kw_sort_keys and kw_sort_gather, up to 4 values: [0] keys (the rows' keys and
+ * conditions), [1] scan (the order's range check, the records' lengths and their scan), [2] gather (the copy
+ * kernel), [3] copies (the order to the device, the keys and the body to the host). */
+int kw_sort_last_ms(kw_sort *h, float *ms, int32_t n);
+
+const char *kw_sort_last_error(kw_sort *h);
+int kw_sort_destroy(kw_sort *h);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

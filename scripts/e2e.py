@@ -29,6 +29,15 @@ host threads) and, with ``--parent-tree DIR``, that tree.  OUT.json gets the med
 ingest span per chunk (device: staging, upload and kw_ingest_parse on the main thread; host: the tokenizer on its
 prefetch thread, overlapped with the matching), the ``kw_ingest_last_ms`` sums, the parse rate, and which route the
 standing rule makes the default.
+
+``--sort-ab OUT.json`` compares the routes of the final sort on a re-run: an untimed first ``main()`` over N articles
+fills an output directory; the timed part is a second ``main()`` over another N articles into a copy of that
+directory, so every file the first run left takes sort_matched_csv's re-read, sort and rewrite.  A fresh child per
+run, the configurations in turn (one warm-up each, then the median and range of 5): this tree with
+``KW_SORT_DEVICE=1`` (csrc/kwsort.hip), this tree with ``KW_SORT_DEVICE=0`` (match_keywords._sort_native and pandas)
+and, with ``--parent-tree DIR``, that tree.  OUT.json gets the medians and ranges, the wall time of the final sort
+loop on each route, the ``kw_sort_last_ms`` sums, the parse and gather rates, the gather kernel's share of the HBM
+peak, the route counts, and which route the standing rule makes the default.
 """
 import argparse
 import contextlib
@@ -248,6 +257,48 @@ print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span
 '''
 
 
+SORT_CHILD = r'''
+import contextlib, hashlib, io, json, os, shutil, sys, tempfile, time
+tree, info_dir, csv_path, chunksize, seed_dir = sys.argv[1:6]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import match_keywords as mk
+span = {'sort_calls': 0, 'sort_s': 0.0}
+inner = mk.sort_matched_csv
+def timed_sort(*a, **kw):
+    t = time.perf_counter()
+    out = inner(*a, **kw)
+    span['sort_s'] += time.perf_counter() - t
+    span['sort_calls'] += 1
+    return out
+mk.sort_matched_csv = timed_sort
+work = tempfile.mkdtemp(prefix='e2e_sort_')
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+shutil.copytree(seed_dir, out)                       # (the first run's files: not timed)
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()) as log:
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0 and 'Error processing' not in log.getvalue()
+sf = sys.modules.get('advanced_scrapper_amd.sortfiles')      # (the parent tree has none)
+if sf is not None:
+    st = sf.LAST_STATS
+    span['stats'] = {k: st[k] for k in ('device', 'unchanged', 'native', 'pandas', 'refused', 'bytes', 'gather_bytes',
+                                        'prefetched', 'ms', 'wall_s')}
+    span['loop_s'] = st.get('loop_s')
+h = hashlib.sha256()
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
 def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS_CHILD):
     """main() in a fresh child per run on ``tree``: one warm-up, then ``runs`` timed runs."""
     import statistics
@@ -391,8 +442,89 @@ def ingest_ab(args):
     assert res['same_bytes'], 'the configurations wrote different bytes'
 
 
+def sort_ab(args):
+    import statistics
+    import subprocess
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    csvs = []
+    for part in range(2):
+        corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=part * args.docs)
+        csvs.append(os.path.join(work, f'articles{part}.csv'))
+        synth.to_dataframe(corpus).to_csv(csvs[-1], index=False)
+        del corpus
+    configs = [('device', REPO, {'KW_SORT_DEVICE': '1'}), ('host', REPO, {'KW_SORT_DEVICE': '0'})]
+    if args.parent_tree:
+        configs.append(('parent', os.path.abspath(args.parent_tree), {}))
+    base = {k: v for k, v in os.environ.items() if k not in ('KW_SORT_DEVICE', 'KW_ROWS_DEVICE', 'KW_EMIT_DEVICE',
+                                                             'KW_INGEST_DEVICE', 'KW_INGEST_WINDOW')}
+    res = {'docs_per_run': args.docs, 'chunksize': args.chunksize, 'csv_bytes': [os.path.getsize(c) for c in csvs],
+           'runs_per_config': args.runs,
+           'timed': 'the second match_keywords.main() (another docs_per_run articles) into a copy of the directory an '
+                    'untimed first main() filled; wall time in a fresh child per run, the configurations in turn; '
+                    '1 warm-up + the median of the runs; sort_s: the median run\'s wall time inside sort_matched_csv '
+                    '(the files the first run left), loop_s: that of run()\'s whole final loop; stats: '
+                    'sortfiles.LAST_STATS of that run (ms: device times summed over the files; the copies to and '
+                    'from the host are part of the wall times, not of the gather kernel\'s share of the HBM peak)'}
+    try:
+        # the first run, once: its directory is copied for every timed run
+        seed = os.path.join(work, 'seed')
+        os.makedirs(seed)
+        p = subprocess.run([sys.executable, '-m', 'advanced_scrapper_amd.match_keywords', '--info-dir', info_dir,
+                            '--articles', csvs[0], '--chunksize', str(args.chunksize), '--device', '0'],
+                           env=dict(base, PYTHONPATH=REPO), cwd=seed, capture_output=True, text=True, timeout=1800)
+        if p.returncode != 0:
+            raise RuntimeError(f"the first run failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+        seed_dir = os.path.join(seed, 'yahoo_ticker_matched_articles')
+        res['seed_files'] = len(os.listdir(seed_dir))
+        res['seed_bytes'] = sum(os.path.getsize(os.path.join(seed_dir, f)) for f in os.listdir(seed_dir))
+        got = {name: [] for name, _t, _e in configs}
+        for _ in range(args.runs + 1):
+            for name, tree, extra in configs:
+                p = subprocess.run([sys.executable, '-c', SORT_CHILD, tree, info_dir, csvs[1], str(args.chunksize),
+                                    seed_dir], env=dict(base, **extra), cwd=tree, capture_output=True, text=True,
+                                   timeout=1800)
+                if p.returncode != 0:
+                    raise RuntimeError(f"{name}: child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+                line = [ln for ln in p.stdout.splitlines() if ln.startswith('E2E_ROWS ')][-1]
+                got[name].append(json.loads(line[len('E2E_ROWS '):]))
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    for name, _tree, extra in configs:
+        runs = got[name]
+        assert len({r['sha256'] for r in runs}) == 1, f'{name}: runs wrote different bytes'
+        timed = runs[1:]
+        v = [r['seconds'] for r in timed]
+        mid = sorted(timed, key=lambda r: r['seconds'])[len(timed) // 2]
+        res[name] = {'env': extra, 'sha256': mid['sha256'], 'runs': v, 'median_s': statistics.median(v),
+                     'min_s': min(v), 'max_s': max(v), 'sort': mid['span']}
+    res['same_bytes'] = len({res[name]['sha256'] for name, _t, _e in configs}) == 1
+    st = res['device']['sort']['stats']
+    ms = st['ms']
+    res['routes'] = {k: st[k] for k in ('device', 'unchanged', 'native', 'pandas', 'refused', 'prefetched')}
+    res['parse_GBps'] = round(st['bytes'] / (ms['parse'] * 1e-3) / 1e9, 2) if ms['parse'] else None
+    res['gather_GBps'] = round(st['gather_bytes'] / (ms['gather'] * 1e-3) / 1e9, 2) if ms['gather'] else None
+    # the gather kernel reads every file byte it lays out and writes it once
+    res['gather_share_of_hbm_peak'] = (round(2 * st['gather_bytes'] / (ms['gather'] * 1e-3) / 8e12, 4)
+                                       if ms['gather'] else None)
+    res['sort_wall_s'] = {name: res[name]['sort']['sort_s'] for name, _t, _e in configs}
+    res['device_faster'] = res['device']['median_s'] < res['host']['median_s']
+    res['default'] = 'device' if res['device_faster'] else 'host (the device route behind KW_SORT_DEVICE=1)'
+    with open(args.sort_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['same_bytes'], 'the configurations wrote different bytes'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--sort-ab', metavar='OUT.json', help='compare the final sort\'s routes on a re-run (see the module doc)')
     ap.add_argument('--ingest-ab', metavar='OUT.json', help='compare the article ingest\'s routes (see the module doc)')
     ap.add_argument('--emit-ab', metavar='OUT.json', help='compare the CSV rows\' routes (see the module doc)')
     ap.add_argument('--rows-ab', metavar='OUT.json', help='compare the JSON cells\' routes (see the module doc)')
@@ -413,6 +545,9 @@ def main():
     if args.ingest_ab:
         args.ingest_ab = os.path.abspath(args.ingest_ab)
         return ingest_ab(args)
+    if args.sort_ab:
+        args.sort_ab = os.path.abspath(args.sort_ab)
+        return sort_ab(args)
     import bench
     from advanced_scrapper_amd import ingest, match_keywords as mk, synth
     from advanced_scrapper_amd.kb import compile_kb
