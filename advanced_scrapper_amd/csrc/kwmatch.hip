@@ -1406,7 +1406,7 @@ static int ensure_scratch(kw_handle *h, const ScratchCaps &want)
     h->FS.vrec = (uint4 *)carve((size_t)c.hdr_cap * 16);
     h->FS.tarena = (uint8_t *)carve((size_t)c.tx_cap + 64);
     h->FS.tx_cap = c.tx_cap;
-    size_t small = 1024 + nw * 4 + 256 + (nw + 1) * 8 + 256;
+    size_t small = SMALL_HEAD + nw * 4 + 256 + (nw + 1) * 8 + 256;
     HIPCHK(h, hipMalloc(&h->d_small, small));
     uint8_t *q = (uint8_t *)h->d_small;
     h->S.status = (uint32_t *)q;                        // 4 x u32
@@ -1422,13 +1422,14 @@ static int ensure_scratch(kw_handle *h, const ScratchCaps &want)
     h->FS.res_cnt = (uint32_t *)(q + 392);              // documents left to the resolve kernel
     h->d_total = (unsigned long long *)(q + 400);       // hit records of the scan (kw_offsets_kernel)
     h->FS.gnext = (uint32_t *)(q + 408);                // 2 x u32: the filter's next work unit / the probe's next region
-    uint32_t *cnts = (uint32_t *)(q + 1024);
+    h->FS.tstats = (unsigned long long *)(q + 1024);    // STAT_REP x 16 x u64
+    uint32_t *cnts = (uint32_t *)(q + SMALL_HEAD);
     h->out_cnt_all = cnts;
     h->FS.kout_cnt = cnts;
     h->FS.tout_cnt = cnts + c.nk;
     h->FS.out_cnt = cnts + 2 * (size_t)c.nk;
     h->S.out_cnt = cnts + 2 * (size_t)c.nk + c.nr;
-    h->d_offs = (unsigned long long *)(q + 1024 + ((nw * 4 + 255) & ~(size_t)255));
+    h->d_offs = (unsigned long long *)(q + SMALL_HEAD + ((nw * 4 + 255) & ~(size_t)255));
     h->out_all = outs;
     h->FS.kout = outs;
     h->FS.tout = outs + (size_t)c.nk * c.out_cap;
@@ -1544,7 +1545,7 @@ static int launch_scan(kw_handle *h)
     h->FS.dyn = dyn_groups ? 1 : 0;
     h->FS.chunk_groups = kchunk;
     const int nk = h->nk;   // the allocation may be larger than this launch needs: every region is cleared
-    HIPCHK(h, hipMemsetAsync(h->S.status, 0, 416, st));   // status .. stats, tx_used, res_cnt, total, gnext
+    HIPCHK(h, hipMemsetAsync(h->S.status, 0, SMALL_HEAD, st));   // status .. stats, tx_used, res_cnt, total, gnext, tstats
     HIPCHK(h, hipMemsetAsync(h->out_cnt_all, 0, ((size_t)2 * nk + h->nr + h->ng) * 4, st));
     HIPCHK(h, hipMemsetAsync(h->FS.vcnt, 0, (size_t)nk * 20, st));   // vcnt, ecnt, scnt, xcnt, xmark
     HIPCHK(h, hipMemsetAsync(h->FS.dset, 0, (h->FS.dmask + 1) * 8, st));
@@ -1752,8 +1753,10 @@ static int finish(kw_handle *h)
         HIPCHK(h, hipStreamSynchronize(h->stream));
         // the scan's small results in one copy: status (0), generic stats (64), fast-path stats (128),
         // transcoded-view bytes (384), record count (400)
-        unsigned long long small[51];
+        unsigned long long small[SMALL_HEAD / 8];
         HIPCHK(h, hipMemcpy(small, h->S.status, sizeof(small), hipMemcpyDeviceToHost));
+        for (int r = 0; r < STAT_REP; ++r)   // the task kernels' copies of the fast-path stats
+            for (int i = 0; i < 16; ++i) small[16 + i] += small[128 + 16 * r + i];
         if (kw_env("KW_DEBUG_TASKS") && h->nk > 0) {   // (developer aid) the task regions' queue lengths
             std::vector<uint32_t> tc((size_t)4 * h->nk);
             HIPCHK(h, hipMemcpy(tc.data(), h->FS.vcnt, tc.size() * 4, hipMemcpyDeviceToHost));
@@ -1938,6 +1941,30 @@ extern "C" int kw_doc_routes(kw_handle *h, uint8_t *routes, int64_t n)
                     : (y & DH_TX)                                        ? KW_ROUTE_TRANSCODE
                     : ((y & (DH_NA0 | DH_NA1)) || (dfl[d] & DH_RESOLVE)) ? KW_ROUTE_RESOLVE
                                                                          : KW_ROUTE_SCAN;
+    }
+    return KW_OK;
+}
+
+extern "C" int kw_scan_counts(kw_handle *h, uint32_t *doc_items, int64_t n, int64_t *tasks, int32_t n_tasks)
+{
+    if (!h || (n > 0 && !doc_items) || (n_tasks > 0 && !tasks)) return KW_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = finish(h);
+    if (rc) return rc;
+    if (n != 0 && n != h->n_docs) { h->err = "kw_scan_counts: n differs from the scanned document count"; return KW_EINVAL; }
+    if (n > 0) HIPCHK(h, hipMemcpy(doc_items, h->FS.ncnt, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (n_tasks > 0) {
+        const int nk = h->n_docs > 0 ? h->nk : 0;
+        std::vector<uint32_t> tc((size_t)5 * nk);   // vcnt, ecnt, scnt, xcnt, xmark
+        if (nk > 0) HIPCHK(h, hipMemcpy(tc.data(), h->FS.vcnt, tc.size() * 4, hipMemcpyDeviceToHost));
+        int64_t v[11] = {nk};
+        for (int q = 0; q < 5; ++q)
+            for (int t = 0; t < nk; ++t) {
+                const int64_t c = tc[(size_t)q * nk + t];
+                v[1 + 2 * q] += c;
+                v[2 + 2 * q] = std::max(v[2 + 2 * q], c);
+            }
+        for (int i = 0; i < n_tasks && i < 11; ++i) tasks[i] = v[i];
     }
     return KW_OK;
 }

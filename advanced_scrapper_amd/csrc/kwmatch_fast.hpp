@@ -53,6 +53,8 @@ constexpr int FK_T3_BITS = FK_T3_BITS_CFG;      // stage 2, 3-byte keys: 8 KB
 constexpr int FK_B2_BITS = FK_B2_BITS_CFG;      // stage 2, 2-byte keys: 8 KB (<= 16: fk_b2h_index)
 static_assert(FK_B2_BITS <= 16, "fk_b2h_index takes the high bits of a 16-bit index");
 constexpr int FK_EDGE_BITS = 20;                // edge prefix / suffix 8-byte keys: 2 x 128 KB (global, L2)
+constexpr int STAT_REP = 64;                    // copies of the fast-path stats the task kernels add to (FastScratch::tstats)
+constexpr int SMALL_HEAD = 1024 + STAT_REP * 128;   // bytes of the scan's small results: status, stats, counters, tstats
 constexpr int FK_ITEMS0 = 512;                  // items of field 0 (text) on the fast path (power of 2: LDS sort)
 constexpr int FK_ITEMS1 = 64;                   // items of field 1 (title)
 constexpr int FK_ITEMS_MAX = FK_ITEMS0;         // one field's item buffer in the resolve kernel
@@ -190,6 +192,9 @@ struct FastScratch {
     uint32_t *big_cnt;          //   from the tail end, count in big_cnt[1])
     uint32_t *status;
     unsigned long long *stats;  // see kw_stats
+    unsigned long long *tstats; // STAT_REP copies of stats[0, 16), a 128-byte line each: the task kernels' waves add
+                                //   to their block's copy (thousands of waves' atomics on one address run one
+                                //   after the other and hold the kernel's end back); the host adds them up
     uint4 *rx_tasks;            // per resolve wave: rx_cap regex-position tasks (doc, field|ascii, pattern, n)
     uint32_t rx_cap;
     // flat resolve of all-ASCII documents (scan epilogue -> task kernel)

@@ -26,6 +26,14 @@
 #ifndef RX_MINW
 #define RX_MINW 4   // <= 128 VGPRs (the prefetched task records stay in LDS)
 #endif
+// regex-item tasks decided one per lane: the most items of a field a lane walks itself (a longer field's task
+// goes to the whole wave), and the item loads a lane keeps in flight.  Tuning knobs: results do not depend on them.
+#ifndef RX_LANE_ITEMS
+#define RX_LANE_ITEMS 64
+#endif
+#ifndef RX_LANE_U
+#define RX_LANE_U 8
+#endif
 // waves per SIMD the resolve kernel is compiled for (register budget)
 #ifndef RK_OCC
 #define RK_OCC 4
@@ -1475,12 +1483,13 @@ __device__ __forceinline__ void task_stats(const FastScratch &S, unsigned long l
                                            unsigned long long rxr)
 {
     if (lane_id() == 0) {
-        if (w) atomicAdd(&S.stats[2], w);
-        if (v) atomicAdd(&S.stats[3], v);
-        if (e) atomicAdd(&S.stats[7], e);
-        if (rx) atomicAdd(&S.stats[10], rx);
-        if (rxbt) atomicAdd(&S.stats[11], rxbt);
-        if (rxr) atomicAdd(&S.stats[12], rxr);
+        unsigned long long *st = S.tstats + (size_t)(blockIdx.x % STAT_REP) * 16;
+        if (w) atomicAdd(&st[2], w);
+        if (v) atomicAdd(&st[3], v);
+        if (e) atomicAdd(&st[7], e);
+        if (rx) atomicAdd(&st[10], rx);
+        if (rxbt) atomicAdd(&st[11], rxbt);
+        if (rxr) atomicAdd(&st[12], rxr);
     }
 }
 
@@ -1996,7 +2005,9 @@ __device__ bool fk_rx_items(const FastScratch &S, const DevScratch &GS, const Fi
 
 // Regex-class names decided (by the scan or the task kernels): re.finditer positions or `name: []`.  phase 0:
 // every task of the region; 1: the tasks the epilogue queued (xmark, beside the verify / short kernels); 2: the
-// ones the verify / short kernels queued after them.
+// ones the verify / short kernels queued after them.  Per round of 64 tasks: the records fetched lane-parallel,
+// then the tasks the field's RXM items answer with no position or one, a lane each; the wave takes the rest one
+// by one (fk_rx_items for two or more items of the name, the field search for the others).
 __global__ __launch_bounds__(RK_BLOCK, RX_MINW) void kw_rx_task_kernel(FastTables FT, DevTables T, const uint8_t *__restrict__ arena,
                                                               const int64_t *__restrict__ off, int n_regions, int G,
                                                               FastScratch S, DevScratch GS, int phase)
@@ -2022,6 +2033,7 @@ __global__ __launch_bounds__(RK_BLOCK, RX_MINW) void kw_rx_task_kernel(FastTable
     for (uint32_t k0 = sub; k0 < nx; k0 += (uint32_t)G * WAVE) {
         // lane j fetches task k0 + j G and its document's view record, flags and item range (one dependent
         // round for all 64 instead of two per task)
+        uint64_t todo;   // the round's tasks left to the whole wave
         {
             const uint32_t k = k0 + (uint32_t)lane * (uint32_t)G;
             const bool has = k < nx;
@@ -2040,9 +2052,31 @@ __global__ __launch_bounds__(RK_BLOCK, RX_MINW) void kw_rx_task_kernel(FastTable
             pre[5 * lane + 2] = make_uint4(f ? nc.y : nc.x, (uint32_t)rr, prm.L, 0u);
             pre[5 * lane + 3] = make_uint4(prm.eb, prm.ee, (uint32_t)prm.anym, (uint32_t)(prm.anym >> 32));
             wave_sync();
+            // one lane = one task: a name with an RXM use in an ASCII field of at most RX_LANE_ITEMS items.  The
+            // lane walks the field's items itself (fk_rx_items' predicate); with no match of P or one, that is
+            // the whole answer.  Two or more need the sort and the non-overlap selection: the wave takes them.
+            const uint32_t ib = h.x + (f ? nc.x : 0u), in = f ? nc.y : nc.x;
+            const bool mine = has && !na && L != 0 && in <= RX_LANE_ITEMS;
+            uint32_t cnt = 0, pmin = ~0u;
+            for (uint32_t i0 = 0; __ballot(mine && i0 < in) != 0; i0 += RX_LANE_U) {
+                uint64_t it[RX_LANE_U];
+#pragma unroll
+                for (uint32_t u = 0; u < RX_LANE_U; ++u) it[u] = mine && i0 + u < in ? S.items[ib + i0 + u] : 0ull;
+#pragma unroll
+                for (uint32_t u = 0; u < RX_LANE_U; ++u) {
+                    const bool m = mine && i0 + u < in && it_pat(it[u]) == P && it_kind(it[u]) == FU_RXM &&
+                                   it_use(it[u]) != IT_USE_MASK;
+                    cnt += m;
+                    pmin = m ? min(pmin, it_pos(it[u])) : pmin;
+                }
+            }
+            const bool done = mine && cnt <= 1;
+            emit_hits(O, GS, done, doc, P, cnt ? pmin : KW_NOPOS, f);
+            todo = __ballot(has && !done);
         }
-        const uint32_t nj = min((uint32_t)WAVE, (nx - k0 + (uint32_t)G - 1) / (uint32_t)G);
-        for (uint32_t j = 0; j < nj; ++j) {
+        while (todo) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+            todo &= todo - 1;
             const uint4 vv = pre[5 * j], q = pre[5 * j + 1];
             const uint4 v = make_uint4((uint32_t)__builtin_amdgcn_readfirstlane((int)vv.x),
                                        (uint32_t)__builtin_amdgcn_readfirstlane((int)vv.y),

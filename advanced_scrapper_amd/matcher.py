@@ -174,6 +174,24 @@ class GpuMatcher:
         _native.check(_native.lib().kw_doc_routes(self.h, _native.ptr(out), int(n_docs)), self.h)
         return out[:n_docs]
 
+    def doc_items(self, n_docs: int) -> np.ndarray:
+        """Per document of the last scan: the probe's items of its text and of its title ([n, 2] uint32)."""
+        out = np.zeros((max(n_docs, 1), 2), dtype=np.uint32)
+        _native.check(_native.lib().kw_scan_counts(self.h, _native.ptr(out), int(n_docs), None, 0), self.h)
+        return out[:n_docs]
+
+    TASK_KEYS = ('verify', 'edge', 'short', 'regex', 'regex_early')
+
+    def task_counts(self) -> Dict[str, int]:
+        """Task queues of the last scan: ``regions``, and per queue its total and its largest region's count
+        (``regex_early``: the regex tasks the epilogue queued, which run beside the verify and short kernels)."""
+        v = np.zeros(11, dtype=np.int64)
+        _native.check(_native.lib().kw_scan_counts(self.h, None, 0, _native.ptr(v), 11), self.h)
+        out = {'regions': int(v[0])}
+        for i, k in enumerate(self.TASK_KEYS):
+            out[k], out[k + '_max'] = int(v[1 + 2 * i]), int(v[2 + 2 * i])
+        return out
+
     STAT_KEYS = ('candidates', 'anchor_hits', 'lcs_windows', 'verifications', 'deferred_docs', 'deferred_items',
                  'deferred_long_nonascii', 'edge_items', 'candidates_stage2', 'resolved_docs', 'regex_searches',
                  'regex_backtracking', 'regex_rounds', 'deferred_long_run', 'deferred_item_caps', 'deferred_flagged',

@@ -213,6 +213,13 @@ int kw_last_kernel_times(kw_handle *h, float *ms, int32_t n);
 #define KW_ROUTE_TRANSCODE 3
 int kw_doc_routes(kw_handle *h, uint8_t *routes, int64_t n);
 
+/* Work counts of the last scan (after kw_hits), for tests and tuning.  doc_items (n = the scanned document
+ * count, or 0 for none): the probe's items of document d's text in doc_items[2 d] and of its title in
+ * doc_items[2 d + 1].  tasks (up to 11 values): [0] the task regions, then the total and the largest region's
+ * count of [1, 2] verify, [3, 4] edge, [5, 6] short-field and [7, 8] regex tasks, and [9, 10] of the regex tasks
+ * the epilogue queued (the ones that run beside the verify and short-field kernels). */
+int kw_scan_counts(kw_handle *h, uint32_t *doc_items, int64_t n, int64_t *tasks, int32_t n_tasks);
+
 /* Host-buffer forms of kw_scan / kw_hits_copy for callers with no device allocator of their own (the
  * drop-in driver's single-GPU path runs without torch).  kw_scan_host copies the host arena
  * (arena_bytes bytes) and the 2*n_docs+1 offsets into library-owned device buffers (grown on demand, kept
