@@ -57,7 +57,7 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_ingest_create', 'kw_ingest_destroy', 'kw_ingest_last_error', 'kw_ingest_last_ms',
            'kw_ingest_tile_bytes', 'kw_ingest_parse', 'kw_ingest_cells', 'kw_ingest_arena', 'kw_ingest_dates',
            'kw_ingest_column_flags', 'kw_ingest_copy_cells', 'kw_ingest_copy_column', 'kw_ingest_stage',
-           'kw_ingest_copy_arena',
+           'kw_ingest_copy_arena', 'kw_ingest_dates_iso',
            'kw_ingest_upload', 'kw_ingest_spans', 'kw_ingest_copy_spans',
            'kw_sort_create', 'kw_sort_destroy', 'kw_sort_last_error', 'kw_sort_last_ms', 'kw_sort_keys',
            'kw_sort_gather')
@@ -176,6 +176,8 @@ def lib() -> ctypes.CDLL:
     L.kw_ingest_cells.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
     L.kw_ingest_arena.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
     L.kw_ingest_dates.argtypes = [vp, vp, vp]
+    L.kw_ingest_dates_iso.argtypes = [vp, vp, vp, vp]
+    L.kw_ingest_dates_iso.restype = ctypes.c_int
     L.kw_ingest_column_flags.argtypes = [vp, vp]
     L.kw_ingest_copy_cells.argtypes = [vp, vp, vp, vp]
     L.kw_ingest_copy_column.argtypes = [vp, i32, vp, i64, vp, vp]

@@ -372,6 +372,77 @@ void kwcsv_dates(const uint8_t *out, const int64_t *coff, const uint8_t *cfl, in
 }
 
 /*
+ * kwcsv_dates by the ISO rule (include/kwingest.h, tests/dates_rule.py): a cell is native iff it is, whole,
+ *   YYYY-MM-DD[ T]HH:MM:SS ( '.' 1-9 digits )? ( 'Z' | [+-]HH ( ':'? MM )? )?
+ * (19 to 35 bytes, ASCII digits, year >= 1000, the fields valid as in kwcsv_dates, offset HH <= 23, MM <= 59), which
+ * dateutil parses to those fields, the fraction's first six digits as microseconds (more are dropped) and the
+ * zone as a fixed offset.  kind[r]: 2 NA; 1 the 19-byte layout (us, off_s as kwcsv_dates: wall clock read as UTC,
+ * 0); 4 naive with a fraction (us = the wall clock's epoch microseconds); 3 with a zone (us = the instant's epoch
+ * microseconds, wall clock minus offset; off_s[r] = the offset in seconds, 0 for 'Z'); 0 otherwise (us = off_s
+ * = 0).  The process's time zone is never read: the caller decides what a zero offset means there (dates.py).
+ */
+void kwcsv_dates_iso(const uint8_t *out, const int64_t *coff, const uint8_t *cfl, int64_t nrows, int32_t ncols,
+                     int32_t col, int64_t *us, uint8_t *kind, int32_t *off_s, int32_t nthreads)
+{
+    static const int dim[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
+    static const int8_t digit_at[19] = {1, 1, 1, 1, 0, 1, 1, 0, 1, 1, 0, 1, 1, 0, 1, 1, 0, 1, 1};
+    static const int32_t scale[7] = {0, 100000, 10000, 1000, 100, 10, 1};
+    const int64_t nt = nthreads > 1 ? nthreads : 1;
+    #pragma omp parallel for num_threads(nt) schedule(static)
+    for (int64_t r = 0; r < nrows; ++r) {
+        const int64_t c = r * ncols + col;
+        us[r] = 0;
+        off_s[r] = 0;
+        if (cfl[c] & KWCSV_NA) { kind[r] = 2; continue; }
+        kind[r] = 0;
+        const uint8_t *s = out + coff[c];
+        const int64_t len = coff[c + 1] - coff[c];
+        if (len < 19 || len > 35) continue;
+        int ok = s[4] == '-' && s[7] == '-' && (s[10] == ' ' || s[10] == 'T') && s[13] == ':' && s[16] == ':';
+        for (int i = 0; i < 19 && ok; ++i)
+            if (digit_at[i] && (s[i] < '0' || s[i] > '9')) ok = 0;
+        if (!ok) continue;
+#define D2(i) ((int64_t)(s[i] - '0') * 10 + (s[(i) + 1] - '0'))
+        const int64_t y = D2(0) * 100 + D2(2), mo = D2(5), d = D2(8), hh = D2(11), mi = D2(14), ss = D2(17);
+#undef D2
+        if (y < 1000 || mo < 1 || mo > 12 || hh >= 24 || mi >= 60 || ss >= 60) continue;
+        const int leap = (y % 4 == 0) && (y % 100 != 0 || y % 400 == 0);
+        const int64_t md = (mo == 2 && leap) ? 29 : dim[mo - 1];
+        if (d < 1 || d > md) continue;
+        /* the tail, a byte a step.  st: 0 after the seconds; 1 after '.'; 2 in the fraction; 3 after the sign;
+         * 4 after H; 5 after HH; 6 after HH':'; 7 after M; 8 done ('Z' or MM); 9 refused */
+        int st = 0, nf = 0, sign = 1;
+        int32_t frac = 0, oh = 0, om = 0;
+        for (int64_t i = 19; i < len; ++i) {
+            const int ch = s[i], dg = ch - '0', isd = ch >= '0' && ch <= '9';
+            const int zone = ch == 'Z' ? 8 : (ch == '+' || ch == '-') ? 3 : 9;
+            switch (st) {
+            case 0: st = ch == '.' ? 1 : zone; break;
+            case 1:
+            case 2:
+                if (isd) { if (++nf <= 6) frac = frac * 10 + dg; st = nf <= 9 ? 2 : 9; }
+                else st = st == 2 ? zone : 9;
+                break;
+            case 3: oh = dg * 10; st = isd ? 4 : 9; break;
+            case 4: oh += dg; st = isd ? 5 : 9; break;
+            case 5: if (isd) { om = dg * 10; st = 7; } else st = ch == ':' ? 6 : 9; break;
+            case 6: om = dg * 10; st = isd ? 7 : 9; break;
+            case 7: om += dg; st = isd ? 8 : 9; break;
+            default: st = 9; break;
+            }
+            if (st == 3) sign = ch == '-' ? -1 : 1;
+        }
+        if (!(st == 0 || st == 2 || st == 5 || st == 8) || oh > 23 || om > 59) continue;
+        const int aware = st == 5 || st == 8;
+        const int32_t off = aware ? sign * (oh * 3600 + om * 60) : 0;
+        us[r] = ((days_from_civil(y, mo, d) * 86400) + hh * 3600 + mi * 60 + ss - off) * 1000000 +
+                (nf ? (int64_t)frac * scale[nf < 6 ? nf : 6] : 0);
+        off_s[r] = off;
+        kind[r] = aware ? 3 : nf ? 4 : 1;
+    }
+}
+
+/*
  * Record boundaries only (the --gpus N ingest: every rank finds a chunk's records, then tokenizes just its
  * own byte-balanced share with kwcsv_parse).  The same record split as kwcsv_parse: blank lines skipped,
  * '"' quoting with doubled quotes, "\n" / "\r\n" / "\r" ends.  starts[r] = the first byte of record r

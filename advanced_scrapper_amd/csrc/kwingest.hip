@@ -1,6 +1,6 @@
 // libkwmatch: the article ingest on the device (include/kwingest.h) -- raw article-CSV bytes in device memory
-// become the tokenized cells (kwcsv_parse's layout), the matcher's arena (kwcsv_pack's) and the date fast path
-// (kwcsv_dates') of csrc/kwcsv.c, wherever the take rule of kwingest.h holds.
+// become the tokenized cells (kwcsv_parse's layout), the matcher's arena (kwcsv_pack's) and the date arrays
+// (kwcsv_dates_iso's) of csrc/kwcsv.c, wherever the take rule of kwingest.h holds.
 //
 //   ig_quotes_kernel   a tile's '"' bytes counted (their exclusive scan over the tiles carries the quote parity
 //                      into every tile); the first NUL; UTF-8 validated by the lanes that hold a byte >= 0x80.
@@ -15,7 +15,7 @@
 //   ig_finish_kernel   one thread: n_rows, consumed, the verdict in rule order.  The kernels after it return at
 //                      once unless the verdict is OK (the offsets of a refused text are not all written).
 //   ig_flags_kernel    lane = cell: CANON, the NA compare, the text witness, the columns' witnesses.
-//   ig_rows_kernel     lane = row: the date fast path, the two arena segment lengths.
+//   ig_rows_kernel     lane = row: the date cell by the ISO rule, the two arena segment lengths.
 //   ig_gather_kernel   lane = 16 arena bytes: the segment by binary search in the scanned offsets.
 //   ig_spans_kernel    on request (kw_ingest_spans), after an OK parse: the tile masks once more, for every taken
 //                      record's first byte and the byte after its last.
@@ -582,12 +582,90 @@ __device__ __forceinline__ long long days_from_civil(long long y, long long m, l
     return era * 146097 + doe - 719468;
 }
 
-// lane = row: kwcsv_dates' fast path of the date cell; the lengths of the row's two arena segments
+constexpr int DATE_MAX = 35;   // the longest native date cell: 19 + '.' + 9 digits + sign + HH ':' MM
+
+// One date cell by the ISO rule of kwingest.h (kwcsv_dates_iso's answer).  The cell's bytes are read once, each
+// under its own `i < len` (nothing past the cell's end), into registers; the calendar test reads the first 19,
+// the tail machine the other 16 at most, a byte a step (kwcsv_dates_iso's states).
+__device__ __forceinline__ void date_iso(const uint8_t *__restrict__ s, int len, long long &us, uint8_t &kind, int &off_s)
+{
+    us = 0;
+    kind = 0;
+    off_s = 0;
+    if (len < 19 || len > DATE_MAX) return;
+    int b[DATE_MAX];
+#pragma unroll
+    for (int i = 0; i < DATE_MAX; ++i) b[i] = i < len ? (int)s[i] : 0;
+    bool ok = b[4] == '-' && b[7] == '-' && (b[10] == ' ' || b[10] == 'T') && b[13] == ':' && b[16] == ':';
+#pragma unroll
+    for (int i = 0; i < 19; ++i)
+        if (i != 4 && i != 7 && i != 10 && i != 13 && i != 16) ok = ok && b[i] >= '0' && b[i] <= '9';
+    if (!ok) return;
+#define IG_D2(i) ((long long)(b[i] - '0') * 10 + (b[(i) + 1] - '0'))
+    const long long y = IG_D2(0) * 100 + IG_D2(2), mo = IG_D2(5), d = IG_D2(8), hh = IG_D2(11), mi = IG_D2(14), ss = IG_D2(17);
+#undef IG_D2
+    if (y < 1000 || mo < 1 || mo > 12 || hh >= 24 || mi >= 60 || ss >= 60) return;
+    const bool leap = (y % 4 == 0) && (y % 100 != 0 || y % 400 == 0);
+    const long long md = mo == 2 ? (leap ? 29 : 28) : ((mo == 4 || mo == 6 || mo == 9 || mo == 11) ? 30 : 31);
+    if (d < 1 || d > md) return;
+    // st: 0 after the seconds; 1 after '.'; 2 in the fraction; 3 after the sign; 4 after H; 5 after HH; 6 after
+    // HH':'; 7 after M; 8 done ('Z' or MM); 9 refused
+    int st = 0, nf = 0, sign = 1, frac = 0, oh = 0, om = 0;
+#pragma unroll
+    for (int i = 19; i < DATE_MAX; ++i) {
+        if (i < len) {
+            const int ch = b[i], dg = ch - '0';
+            const bool isd = ch >= '0' && ch <= '9';
+            const int zone = ch == 'Z' ? 8 : (ch == '+' || ch == '-') ? 3 : 9;
+            int nx = 9;
+            if (st == 0) {
+                nx = ch == '.' ? 1 : zone;
+            } else if (st == 1 || st == 2) {
+                if (isd) {
+                    ++nf;
+                    if (nf <= 6) frac = frac * 10 + dg;
+                    nx = nf <= 9 ? 2 : 9;
+                } else {
+                    nx = st == 2 ? zone : 9;
+                }
+            } else if (st == 3) {
+                oh = dg * 10;
+                nx = isd ? 4 : 9;
+            } else if (st == 4) {
+                oh += dg;
+                nx = isd ? 5 : 9;
+            } else if (st == 5) {
+                if (isd) om = dg * 10;
+                nx = isd ? 7 : (ch == ':' ? 6 : 9);
+            } else if (st == 6) {
+                om = dg * 10;
+                nx = isd ? 7 : 9;
+            } else if (st == 7) {
+                om += dg;
+                nx = isd ? 8 : 9;
+            }
+            st = nx;
+            if (st == 3) sign = ch == '-' ? -1 : 1;
+        }
+    }
+    if (!(st == 0 || st == 2 || st == 5 || st == 8) || oh > 23 || om > 59) return;
+    const bool aware = st == 5 || st == 8;
+    const int off = aware ? sign * (oh * 3600 + om * 60) : 0;
+    int f = frac;   // the first min(nf, 6) digits as microseconds
+#pragma unroll
+    for (int k = 1; k < 6; ++k)
+        if (nf <= k) f *= 10;
+    us = ((days_from_civil(y, mo, d) * 86400) + hh * 3600 + mi * 60 + ss - off) * 1000000 + f;
+    off_s = off;
+    kind = aware ? 3 : nf ? 4 : 1;
+}
+
+// lane = row: the date cell by the ISO rule (kwcsv_dates_iso); the lengths of the row's two arena segments
 __global__ __launch_bounds__(BLOCK) void ig_rows_kernel(const Dev *__restrict__ D, const uint8_t *__restrict__ cells,
                                                         const long long *__restrict__ coff,
                                                         const uint8_t *__restrict__ cfl, int ncols, Cols C,
                                                         long long *__restrict__ us, uint8_t *__restrict__ kind,
-                                                        u64 *__restrict__ aoff)
+                                                        int *__restrict__ off_s, u64 *__restrict__ aoff)
 {
     if (D->verdict != KW_INGEST_OK) return;
     const long long nr = D->n_rows;
@@ -599,31 +677,15 @@ __global__ __launch_bounds__(BLOCK) void ig_rows_kernel(const Dev *__restrict__ 
         }
         const long long c = r * ncols + C.c[2];
         long long v = 0;
-        uint8_t kd = 0;
-        if (cfl[c] & F_NA) {
-            kd = 2;
-        } else if (coff[c + 1] - coff[c] == 19) {
-            const uint8_t *__restrict__ s = cells + coff[c];
-            bool ok = s[4] == '-' && s[7] == '-' && (s[10] == ' ' || s[10] == 'T') && s[13] == ':' && s[16] == ':';
-            for (int i = 0; i < 19 && ok; ++i)
-                if (i != 4 && i != 7 && i != 10 && i != 13 && i != 16 && (s[i] < '0' || s[i] > '9')) ok = false;
-            if (ok) {
-#define IG_D2(i) ((long long)(s[i] - '0') * 10 + (s[(i) + 1] - '0'))
-                const long long y = IG_D2(0) * 100 + IG_D2(2), mo = IG_D2(5), d = IG_D2(8), hh = IG_D2(11), mi = IG_D2(14),
-                                ss = IG_D2(17);
-#undef IG_D2
-                if (!(y < 1000 || mo < 1 || mo > 12 || hh >= 24 || mi >= 60 || ss >= 60)) {
-                    const bool leap = (y % 4 == 0) && (y % 100 != 0 || y % 400 == 0);
-                    const long long md = mo == 2 ? (leap ? 29 : 28) : ((mo == 4 || mo == 6 || mo == 9 || mo == 11) ? 30 : 31);
-                    if (d >= 1 && d <= md) {
-                        v = ((days_from_civil(y, mo, d) * 86400) + hh * 3600 + mi * 60 + ss) * 1000000;
-                        kd = 1;
-                    }
-                }
-            }
+        uint8_t kd = 2;
+        int off = 0;
+        if (!(cfl[c] & F_NA)) {
+            const long long lo = coff[c], len = coff[c + 1] - lo;
+            date_iso(cells + lo, len > DATE_MAX ? DATE_MAX + 1 : (int)len, v, kd, off);
         }
         us[r] = v;
         kind[r] = kd;
+        off_s[r] = off;
     }
 }
 
@@ -701,7 +763,7 @@ struct kw_ingest {
     int n_na = 0;
     ig::Dev *D = nullptr;          // device
     ig::Dev *H = nullptr;          // pinned host copy
-    ig::Buf tiles, cells, coff, cflw, cfl, arena, aoff, us, kind, col_buf, col_off, col_fl;
+    ig::Buf tiles, cells, coff, cflw, cfl, arena, aoff, us, kind, doff, col_buf, col_off, col_fl;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms[4] = {0, 0, 0, 0};
     bool have = false;             // an OK parse whose buffers stand
@@ -807,7 +869,7 @@ extern "C" int kw_ingest_destroy(kw_ingest *h)
 {
     if (!h) return KW_OK;
     (void)hipSetDevice(h->device);
-    Buf *bufs[] = {&h->tiles, &h->cells, &h->coff, &h->cflw, &h->cfl, &h->arena, &h->aoff, &h->us, &h->kind,
+    Buf *bufs[] = {&h->tiles, &h->cells, &h->coff, &h->cflw, &h->cfl, &h->arena, &h->aoff, &h->us, &h->kind, &h->doff,
                    &h->col_buf, &h->col_off, &h->col_fl, &h->spans};
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -855,7 +917,7 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
         (rc = ensure(h, h->cfl, (size_t)cells_cap)) ||
         (rc = ensure(h, h->arena, (size_t)n + 6 * (size_t)rows_cap + ARENA_PAD + 32)) ||
         (rc = ensure(h, h->aoff, (size_t)(2 * rows_cap + 1) * 8)) || (rc = ensure(h, h->us, (size_t)rows_cap * 8)) ||
-        (rc = ensure(h, h->kind, (size_t)rows_cap)))
+        (rc = ensure(h, h->kind, (size_t)rows_cap)) || (rc = ensure(h, h->doff, (size_t)rows_cap * 4)))
         return rc;
     Dev init;
     memset(&init, 0, sizeof(init));
@@ -913,7 +975,7 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     // arena + dates
     hipLaunchKernelGGL(ig_rows_kernel, grid_for(rows_cap, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
                        (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p, (int)ncols, h->cols,
-                       (long long *)h->us.p, (uint8_t *)h->kind.p, (u64 *)h->aoff.p);
+                       (long long *)h->us.p, (uint8_t *)h->kind.p, (int *)h->doff.p, (u64 *)h->aoff.p);
     {
         ScanArgs S{};
         S.a[0] = (u64 *)h->aoff.p;
@@ -1010,17 +1072,37 @@ extern "C" int kw_ingest_arena(kw_ingest *h, const uint8_t **d_arena, const int6
     return KW_OK;
 }
 
+// the date arrays of the last parse into host arrays (off_s may be null)
+static int copy_dates(kw_ingest *h, size_t nr, int64_t *us, uint8_t *kind, int32_t *off_s)
+{
+    IGCHK(h, hipSetDevice(h->device));
+    IGCHK(h, hipMemcpyAsync(us, h->us.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
+    IGCHK(h, hipMemcpyAsync(kind, h->kind.p, nr, hipMemcpyDeviceToHost, h->stream));
+    if (off_s) IGCHK(h, hipMemcpyAsync(off_s, h->doff.p, nr * 4, hipMemcpyDeviceToHost, h->stream));
+    IGCHK(h, hipStreamSynchronize(h->stream));
+    return KW_OK;
+}
+
 extern "C" int kw_ingest_dates(kw_ingest *h, int64_t *us, uint8_t *kind)
 {
     IG_NEED_PARSE(h, "kw_ingest_dates");
     const size_t nr = (size_t)h->H->n_rows;
     if (nr && (!us || !kind)) { h->err = "kw_ingest_dates: bad arguments"; return KW_EINVAL; }
     if (!nr) return KW_OK;
-    IGCHK(h, hipSetDevice(h->device));
-    IGCHK(h, hipMemcpyAsync(us, h->us.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipMemcpyAsync(kind, h->kind.p, nr, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipStreamSynchronize(h->stream));
+    const int rc = copy_dates(h, nr, us, kind, nullptr);
+    if (rc) return rc;
+    for (size_t r = 0; r < nr; ++r)   // kwcsv_dates knows the 19-byte layout alone: the ISO rule's other kinds are its 0
+        if (kind[r] > 2) { kind[r] = 0; us[r] = 0; }
     return KW_OK;
+}
+
+extern "C" int kw_ingest_dates_iso(kw_ingest *h, int64_t *us, uint8_t *kind, int32_t *off_s)
+{
+    IG_NEED_PARSE(h, "kw_ingest_dates_iso");
+    const size_t nr = (size_t)h->H->n_rows;
+    if (nr && (!us || !kind || !off_s)) { h->err = "kw_ingest_dates_iso: bad arguments"; return KW_EINVAL; }
+    if (!nr) return KW_OK;
+    return copy_dates(h, nr, us, kind, off_s);
 }
 
 extern "C" int kw_ingest_column_flags(kw_ingest *h, int32_t *witness)

@@ -52,6 +52,8 @@ def _lib():
         L.kwcsv_pack_mt.argtypes = [P, P, P, i64, i32, i32, i32, P, i64, P, i32]
         L.kwcsv_dates.restype = None
         L.kwcsv_dates.argtypes = [P, P, P, i64, i32, i32, P, P, i32]
+        L.kwcsv_dates_iso.restype = None
+        L.kwcsv_dates_iso.argtypes = [P, P, P, i64, i32, i32, P, P, P, i32]
         _LIB = L
     return _LIB
 
@@ -107,6 +109,8 @@ class Cells:
 class NativeChunk:
     """One chunk read by the native tokenizer (the columns the path reads, decoded on demand)."""
 
+    stats = None      # the counters of the read this chunk belongs to (read_chunks_device's; dates() adds dates_slow)
+
     def __init__(self, cells: Cells, columns: Sequence[str], index0: int):
         self.cells = cells
         self.columns = list(columns)
@@ -144,27 +148,53 @@ class NativeChunk:
     def dates(self):
         """The reference's per-row ``dateutil.parse(str(v)) if notna(v) else None`` (match_keywords.py:152) of
         the ``date_time`` column up to the first row that raises: (:class:`dates.Dates`, that exception or
-        ``None``).  Cells of the dataset's layout are parsed in C (kwcsv_dates), the others by
-        dates.parse_date (dateutil)."""
-        from .dates import Dates, parse_date
+        ``None``).  Cells of the ISO rule are parsed in C (kwcsv_dates_iso; with ``KW_DATES_ISO=0`` the 19-byte
+        layout alone, kwcsv_dates), the others by dates.parse_date (dateutil)."""
+        from .dates import iso_enabled
         c = self.cells
         n = c.nrows
         us = np.empty(max(n, 1), dtype=np.int64)
         kind = np.empty(max(n, 1), dtype=np.uint8)
-        _lib().kwcsv_dates(_p(c.buf), _p(c.off), _p(c.flags), n, c.ncols, self.col['date_time'], _p(us), _p(kind),
-                           host_threads())
-        slow = {}
-        for r in np.flatnonzero(kind[:n] == 0).tolist():
-            try:
-                slow[r] = parse_date(str(self.value(r, 'date_time')))
-            except Exception as exc:   # noqa: BLE001 - match_keywords.py:152 raises here for this row
-                return Dates(us[:r], kind[:r], {k: v for k, v in slow.items() if k < r}), exc
-        return Dates(us[:n], kind[:n], slow), None
+        off = np.zeros(max(n, 1), dtype=np.int32)
+        if iso_enabled():
+            _lib().kwcsv_dates_iso(_p(c.buf), _p(c.off), _p(c.flags), n, c.ncols, self.col['date_time'], _p(us),
+                                   _p(kind), _p(off), host_threads())
+        else:
+            _lib().kwcsv_dates(_p(c.buf), _p(c.off), _p(c.flags), n, c.ncols, self.col['date_time'], _p(us), _p(kind),
+                               host_threads())
+        return _dates_of(us[:n], kind[:n], off[:n], lambda rows: (str(self.value(r, 'date_time')) for r in rows),
+                         self.stats)
 
     def frame(self) -> pd.DataFrame:
         """The chunk as pandas would give it (object columns; for the drop-in process_chunk API)."""
         data = {name: self.column_list(name) for name in self.columns}
         return pd.DataFrame(data, index=pd.RangeIndex(self.index0, self.index0 + len(self)))
+
+
+def _dates_of(us, kind, off, strings, stats=None):
+    """(:class:`dates.Dates`, the first parse error or ``None``) from the date arrays of a chunk's rows
+    (kwcsv_dates_iso's or kwcsv_dates').  A kind-3 row with a zero offset becomes kind 0 where dateutil reads such a
+    zone as the local one and that is not UTC (dates.zero_offset_is_local, asked on every call); the kind-0 rows
+    go through dates.parse_date, ``strings(rows)`` yielding their cells; ``stats['dates_slow']`` (the counters of the
+    read the chunk came from, if it keeps any) grows by the rows that went there, the one that raised included."""
+    from .dates import Dates, parse_date, zero_offset_is_local
+    if zero_offset_is_local():
+        back = (kind == 3) & (off == 0)
+        if back.any():
+            kind[back] = 0
+            us[back] = 0
+    rows = np.flatnonzero(kind == 0).tolist()
+    slow = {}
+    for i, (r, s) in enumerate(zip(rows, strings(rows))):
+        try:
+            slow[r] = parse_date(s)
+        except Exception as exc:   # noqa: BLE001 - match_keywords.py:152 raises here for this row
+            if stats is not None:
+                stats['dates_slow'] = stats.get('dates_slow', 0) + i + 1
+            return Dates(us[:r], kind[:r], {k: v for k, v in slow.items() if k < r}, off[:r]), exc
+    if stats is not None and rows:
+        stats['dates_slow'] = stats.get('dates_slow', 0) + len(rows)
+    return Dates(us, kind, slow, off), None
 
 
 def _split_header(buf: bytes):
@@ -392,7 +422,7 @@ def parse_all(data: bytes):
 INGEST_DEVICE_DEFAULT = '1'
 DEFAULT_WINDOW = 32 << 20          # the least bytes of CSV uploaded at once (KW_INGEST_WINDOW sets them)
 MAX_WINDOW = (1 << 31) - (1 << 20)
-LAST_STATS = None                  # the counters of the last read_chunks_device
+LAST_STATS = None                  # the counters of the last read_chunks_device (its chunks count into them)
 
 
 def ingest_on_device() -> bool:
@@ -488,6 +518,14 @@ class DeviceIngest:
         kind = np.zeros(max(self.n_rows, 1), dtype=np.uint8)
         self._check(self._n.lib().kw_ingest_dates(self.h, _p(us), _p(kind)))
         return us[:self.n_rows], kind[:self.n_rows]
+
+    def dates_iso(self):
+        """kw_ingest_dates_iso: ``(us int64[n], kind uint8[n], off_s int32[n])`` by the ISO rule (include/kwingest.h)."""
+        us = np.zeros(max(self.n_rows, 1), dtype=np.int64)
+        kind = np.zeros(max(self.n_rows, 1), dtype=np.uint8)
+        off = np.zeros(max(self.n_rows, 1), dtype=np.int32)
+        self._check(self._n.lib().kw_ingest_dates_iso(self.h, _p(us), _p(kind), _p(off)))
+        return us[:self.n_rows], kind[:self.n_rows], off[:self.n_rows]
 
     def column_flags(self) -> np.ndarray:
         w = np.zeros(6, dtype=np.int32)
@@ -596,20 +634,20 @@ class DeviceChunk(NativeChunk):
         return [math.nan if fl[r] & NA else bytes(mv[o[r]:o[r + 1]]).decode('utf-8') for r in range(k)]
 
     def dates(self):
-        from .dates import Dates, parse_date
-        us, kind = self._live().dates()
-        n = self.n
-        slow = {}
-        rows = np.flatnonzero(kind == 0).tolist()
-        if rows:
-            buf, off, _fl = self._live().copy_column(self.col['date_time'])
-            mv, o = memoryview(buf), off.tolist()
-            for r in rows:
-                try:
-                    slow[r] = parse_date(bytes(mv[o[r]:o[r + 1]]).decode('utf-8'))
-                except Exception as exc:   # noqa: BLE001 - match_keywords.py:152 raises here for this row
-                    return Dates(us[:r], kind[:r], {k: v for k, v in slow.items() if k < r}), exc
-        return Dates(us[:n], kind[:n], slow), None
+        from .dates import iso_enabled
+        dev = self._live()
+        if iso_enabled():
+            us, kind, off = dev.dates_iso()
+        else:
+            us, kind = dev.dates()
+            off = np.zeros(len(kind), dtype=np.int32)
+
+        def strings(rows):
+            buf, o, _fl = dev.copy_column(self.col['date_time'])
+            mv, o = memoryview(buf), o.tolist()
+            return (bytes(mv[o[r]:o[r + 1]]).decode('utf-8') for r in rows)
+
+        return _dates_of(us, kind, off, strings, self.stats)
 
 
 def _host_chunk(data, buf, pos, chunksize, ncols, names, need_idx, index0, head_end, starts):
@@ -634,12 +672,13 @@ def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[U
     window holds beyond the chunk serves the next one; while a chunk is at work a background thread fills the
     other staging buffer.  A chunk the device refuses (the take rule, include/kwingest.h) goes through the host
     route alone, with its own pandas decisions, and the device resumes where that ended; a chunk without a
-    text witness in a needed column is parsed by pandas, as on the host route.  ``LAST_STATS`` counts the routes."""
+    text witness in a needed column is parsed by pandas, as on the host route.  ``LAST_STATS`` counts the routes and, as
+    ``dates_slow``, the rows of this read's chunks that went to dateutil (a read on the host route keeps no counters)."""
     global LAST_STATS
     from . import _native
     from concurrent.futures import ThreadPoolExecutor
     stats = LAST_STATS = {'device': 0, 'host': 0, 'pandas': 0, 'grown': 0, 'reused': 0, 'routes': [], 'ms': [],
-                          'bytes': 0, 'wall_s': 0.0, 'wall_ms': []}
+                          'bytes': 0, 'wall_s': 0.0, 'wall_ms': [], 'dates_slow': 0}
     data = _map(path)
     names, head, pos = _split_header(data)
     ncols = len(names)
@@ -724,6 +763,8 @@ def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[U
                     return
                 stats['host'] += 1
                 stats['routes'].append('host')
+                if isinstance(item, NativeChunk):
+                    item.stats = stats
                 yield item
                 index0 += rows
                 pos = end
@@ -747,7 +788,9 @@ def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[U
                 stats['bytes'] += consumed
                 stats['wall_s'] += time.perf_counter() - t0
                 stats['wall_ms'].append(round(1e3 * (time.perf_counter() - t0), 3))
-                yield DeviceChunk(dev, n_rows, names, index0)
+                chunk = DeviceChunk(dev, n_rows, names, index0)
+                chunk.stats = stats
+                yield chunk
             else:
                 stats['pandas'] += 1
                 stats['routes'].append('pandas')

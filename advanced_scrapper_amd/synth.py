@@ -162,7 +162,11 @@ def generate(n_docs: int, names: Sequence[str], kinds: Sequence[int], seed: int 
     return Corpus(arena, off, flags, doc_base, seed)
 
 
-def to_dataframe(corpus: Corpus, source: str = 'yahoo', span_docs: int = None, date_perm=None):
+_MIXED_OFFSET_MINUTES = np.array([-720, -480, -300, -210, -60, 60, 120, 330, 345, 540, 765, 840], dtype=np.int64)
+
+
+def to_dataframe(corpus: Corpus, source: str = 'yahoo', span_docs: int = None, date_perm=None,
+                 date_layout: str = 'naive'):
     """The article CSV schema the reference reads (match_keywords.py:150-152, :139-143).
 
     NaN flags become missing values (the CSV round trip turns them into NaN,
@@ -173,6 +177,9 @@ def to_dataframe(corpus: Corpus, source: str = 'yahoo', span_docs: int = None, d
     ``date_perm = (a, b)`` (with ``span_docs``; gcd(a, span_docs) = 1): document g
     gets the date of slot (a g + b) mod span_docs instead -- the same unique dates,
     in an order that is not the documents' (the output sort then has work to do).
+    ``date_layout`` spells the same instants (the naive dates read as UTC) the way a scraper stores them:
+    ``'z_ms'`` ``YYYY-MM-DDTHH:MM:SS.000Z``, ``'offset'`` ``YYYY-MM-DD HH:MM:SS+00:00``, ``'mixed'`` seeded
+    non-zero UTC offsets in several spellings with the wall clock shifted by the offset.
     """
     import pandas as pd
     n = corpus.n_docs
@@ -193,7 +200,30 @@ def to_dataframe(corpus: Corpus, source: str = 'yahoo', span_docs: int = None, d
         didx = (gidx * a + b) % span_docs
     jitter = (didx * 2654435761) % step
     stamps = start + (didx * step + jitter).astype('timedelta64[s]')
-    dates = [str(s).replace('T', ' ') for s in stamps]
+    if date_layout == 'naive':
+        dates = [str(s).replace('T', ' ') for s in stamps]
+    elif date_layout == 'z_ms':
+        dates = [str(s) + '.000Z' for s in stamps]
+    elif date_layout == 'offset':
+        dates = [str(s).replace('T', ' ') + '+00:00' for s in stamps]
+    elif date_layout == 'mixed':
+        rng = np.random.default_rng(corpus.seed * 1000003 + corpus.doc_base)
+        mins = rng.choice(_MIXED_OFFSET_MINUTES, size=n)
+        form = rng.integers(0, 4, size=n)
+        wall = stamps + (mins * 60).astype('timedelta64[s]')
+        dates = []
+        for s, m, f in zip(wall, mins.tolist(), form.tolist()):
+            sign, a = ('-' if m < 0 else '+'), abs(m)
+            if f == 0:
+                dates.append('%s%s%02d:%02d' % (str(s).replace('T', ' '), sign, a // 60, a % 60))
+            elif f == 1:
+                dates.append('%s.000%s%02d%02d' % (s, sign, a // 60, a % 60))
+            elif f == 2 and a % 60 == 0:
+                dates.append('%s%s%02d' % (s, sign, a // 60))
+            else:
+                dates.append('%s.%06d%s%02d:%02d' % (s, 0, sign, a // 60, a % 60))
+    else:
+        raise ValueError(f'date_layout: {date_layout!r}')
     urls = [f"https://finance.yahoo.com/news/synthetic-{corpus.seed}-{g}.html" for g in gidx]
     return pd.DataFrame({
         'article_text': texts, 'title': titles, 'date_time': dates, 'url': urls,

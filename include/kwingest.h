@@ -33,6 +33,19 @@
  * A cell's bytes are its record bytes without the field and record separators, the opening and closing quote
  * and the first '"' of every "" pair.
  *
+ * The ISO rule of the date cell (restated in tests/dates_rule.py).  A date cell that is not NA is
+ * native iff its bytes are, as a whole cell,
+ *   YYYY-MM-DD[ T]HH:MM:SS ( '.' 1-9 digits )? ( 'Z' | [+-]HH ( ':'? MM )? )?
+ * with ASCII digits, year >= 1000, month, day, hour, minute and second valid by the calendar, offset HH <= 23 and
+ * MM <= 59: 19 to 35 bytes.  dateutil parses such a cell to those fields, the fraction's first six digits as
+ * microseconds (further digits dropped, not rounded) and the zone as a fixed offset.  Its kind is
+ *   1  the 19-byte layout:       us = the wall clock's epoch microseconds read as UTC, off_s = 0
+ *   4  naive with a fraction:    us = the wall clock's epoch microseconds, off_s = 0
+ *   3  with 'Z' or an offset:    us = the instant's epoch microseconds (wall clock minus offset),
+ *                                off_s = +-(HH * 3600 + MM * 60), 0 for 'Z'
+ * an NA cell's is 2 and every other cell's 0 (us = off_s = 0: the caller asks dateutil).  The rule never reads
+ * the process's time zone: what a zero offset means to dateutil there is the caller's to decide (dates.py).
+ *
  * Conventions as kwmatch.h: 0 or a negative KW_E* code; kw_ingest_last_error gives the message; one handle
  * per device and host thread.  Every device buffer a call returns belongs to the handle and stays valid until
  * the next kw_ingest_parse or kw_ingest_destroy.
@@ -99,6 +112,10 @@ int kw_ingest_arena(kw_ingest *h, const uint8_t **d_arena, const int64_t **d_off
 /* After an OK parse: kwcsv_dates' arrays of the date_time column into host arrays us[n_rows], kind[n_rows]
  * (2: NA; 1: the layout 'YYYY-MM-DD[ T]HH:MM:SS', us = its epoch microseconds; 0: neither). */
 int kw_ingest_dates(kw_ingest *h, int64_t *us, uint8_t *kind);
+
+/* After an OK parse: kwcsv_dates_iso's arrays of the date_time column, the ISO rule above, into host arrays
+ * us[n_rows], kind[n_rows], off_s[n_rows].  (kw_ingest_dates is this with kinds 3 and 4 given as kind 0, us 0.) */
+int kw_ingest_dates_iso(kw_ingest *h, int64_t *us, uint8_t *kind, int32_t *off_s);
 
 /* After an OK parse: witness[k] = 1 iff some taken row's cell of column cols[k] carries KWCSV_TEXT. */
 int kw_ingest_column_flags(kw_ingest *h, int32_t *witness);

@@ -30,6 +30,13 @@ ingest span per chunk (device: staging, upload and kw_ingest_parse on the main t
 prefetch thread, overlapped with the matching), the ``kw_ingest_last_ms`` sums, the parse rate, and which route the
 standing rule makes the default.
 
+``--dates-ab OUT.json`` compares the routes of the article dates the same way on N articles whose dates are written
+``YYYY-MM-DDTHH:MM:SS.000Z`` (synth.to_dataframe's ``'z_ms'``): this tree (the ISO rule on the device), this tree with
+``KW_DATES_ISO=0`` (every such row through dateutil) and, with ``--parent-tree DIR``, that tree; then the ``'naive'``
+layout on this tree against the parent, which guards the 19-byte path.  OUT.json gets the medians and ranges, the
+wall time inside ``chunk.dates()``, ``dates_slow`` and the ``kw_ingest_last_ms`` sums, the ``dates`` and ``arena``
+spans also per timed run (their own run-to-run spread).
+
 ``--sort-ab OUT.json`` compares the routes of the final sort on a re-run: an untimed first ``main()`` over N articles
 fills an output directory; the timed part is a second ``main()`` over another N articles into a copy of that
 directory, so every file the first run left takes sort_matched_csv's re-read, sort and rewrite.  A fresh child per
@@ -257,6 +264,52 @@ print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span
 '''
 
 
+DATES_CHILD = r'''
+import contextlib, hashlib, io, json, os, sys, tempfile, time
+tree, info_dir, csv_path, chunksize = sys.argv[1:5]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import ingest, match_keywords as mk
+span = {'dates_s': 0.0, 'dates_calls': 0, 'dates_slow': None, 'arena': 0.0, 'all': 0.0, 'chunks': 0}
+def timed(cls):
+    inner = cls.dates
+    def dates(self):
+        t = time.perf_counter()
+        out = inner(self)
+        span['dates_s'] += time.perf_counter() - t
+        span['dates_calls'] += 1
+        return out
+    cls.dates = dates
+timed(ingest.NativeChunk)
+timed(ingest.DeviceChunk)
+work = tempfile.mkdtemp(prefix='e2e_dates_')
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()):
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0
+st = ingest.LAST_STATS
+span['dates_slow'] = st.get('dates_slow')      # (the parent tree does not count them)
+span['chunks'] = st['device'] + st['host'] + st['pandas']
+assert st['device'] == span['chunks'] > 0
+for m in st['ms']:
+    for k in ('arena', 'all'):
+        span[k] += m[k]
+h = hashlib.sha256()
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+import shutil
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
 SORT_CHILD = r'''
 import contextlib, hashlib, io, json, os, shutil, sys, tempfile, time
 tree, info_dir, csv_path, chunksize, seed_dir = sys.argv[1:6]
@@ -299,7 +352,7 @@ print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span
 '''
 
 
-def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS_CHILD):
+def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS_CHILD, span_runs=()):
     """main() in a fresh child per run on ``tree``: one warm-up, then ``runs`` timed runs."""
     import statistics
     import subprocess
@@ -321,8 +374,11 @@ def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS
     assert len({r['sha256'] for r in got}) == 1, 'runs of one configuration wrote different bytes'
     v = [r['seconds'] for r in timed]
     mid = sorted(timed, key=lambda r: r['seconds'])[len(timed) // 2]      # the median run's spans
-    return {'env': env_extra, 'sha256': mid['sha256'], 'runs': v, 'median_s': statistics.median(v), 'min_s': min(v),
-            'max_s': max(v), 'cells': mid['span']}
+    out = {'env': env_extra, 'sha256': mid['sha256'], 'runs': v, 'median_s': statistics.median(v), 'min_s': min(v),
+           'max_s': max(v), 'cells': mid['span']}
+    for k in span_runs:                # these spans of every timed run, for their own run-to-run spread
+        out[k + '_runs'] = [r['span'][k] for r in timed]
+    return out
 
 
 def rows_ab(args):
@@ -442,6 +498,48 @@ def ingest_ab(args):
     assert res['same_bytes'], 'the configurations wrote different bytes'
 
 
+def dates_ab(args):
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=0)
+    paths = {}
+    for layout in ('z_ms', 'naive'):
+        paths[layout] = os.path.join(work, f'articles_{layout}.csv')
+        synth.to_dataframe(corpus, date_layout=layout).to_csv(paths[layout], index=False)
+    del corpus
+    res = {'docs': args.docs, 'chunksize': args.chunksize, 'runs_per_config': args.runs,
+           'csv_bytes': {k: os.path.getsize(p) for k, p in paths.items()},
+           'timed': 'match_keywords.main() wall time in a fresh child per run; 1 warm-up + the median of the runs, the '
+                    'configurations in turn in one call; cells: the median run\'s wall time inside chunk.dates() '
+                    '(dates_s), the rows that went to dateutil (dates_slow; the parent does not count them) and the '
+                    'device times (ms) of kw_ingest_last_ms summed over the chunks (arena: arena + dates; all)'}
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    try:
+        for layout in ('z_ms', 'naive'):
+            r = res[layout] = {}
+            r['iso'] = rows_config(REPO, {}, info_dir, paths[layout], args.chunksize, args.runs, DATES_CHILD, ('arena', 'dates_s'))
+            if layout == 'z_ms':
+                r['iso_off'] = rows_config(REPO, {'KW_DATES_ISO': '0'}, info_dir, paths[layout], args.chunksize, args.runs,
+                                           DATES_CHILD, ('arena', 'dates_s'))
+            if parent:
+                r['parent'] = rows_config(parent, {}, info_dir, paths[layout], args.chunksize, args.runs, DATES_CHILD, ('arena', 'dates_s'))
+            r['same_bytes'] = len({v['sha256'] for v in r.values()}) == 1
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    assert res['z_ms']['iso']['cells']['dates_slow'] == 0 == res['naive']['iso']['cells']['dates_slow']
+    assert res['z_ms']['iso_off']['cells']['dates_slow'] == args.docs
+    with open(args.dates_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['z_ms']['same_bytes'] and res['naive']['same_bytes'], 'the configurations wrote different bytes'
+
+
 def sort_ab(args):
     import statistics
     import subprocess
@@ -526,6 +624,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sort-ab', metavar='OUT.json', help='compare the final sort\'s routes on a re-run (see the module doc)')
     ap.add_argument('--ingest-ab', metavar='OUT.json', help='compare the article ingest\'s routes (see the module doc)')
+    ap.add_argument('--dates-ab', metavar='OUT.json', help='compare the date routes on ISO-8601 layouts (see the module doc)')
     ap.add_argument('--emit-ab', metavar='OUT.json', help='compare the CSV rows\' routes (see the module doc)')
     ap.add_argument('--rows-ab', metavar='OUT.json', help='compare the JSON cells\' routes (see the module doc)')
     ap.add_argument('--parent-tree', help='--rows-ab / --emit-ab: a built checkout of the parent commit')
@@ -545,6 +644,9 @@ def main():
     if args.ingest_ab:
         args.ingest_ab = os.path.abspath(args.ingest_ab)
         return ingest_ab(args)
+    if args.dates_ab:
+        args.dates_ab = os.path.abspath(args.dates_ab)
+        return dates_ab(args)
     if args.sort_ab:
         args.sort_ab = os.path.abspath(args.sort_ab)
         return sort_ab(args)
