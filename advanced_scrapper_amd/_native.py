@@ -59,6 +59,7 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_ingest_column_flags', 'kw_ingest_copy_cells', 'kw_ingest_copy_column', 'kw_ingest_stage',
            'kw_ingest_copy_arena', 'kw_ingest_dates_iso',
            'kw_ingest_upload', 'kw_ingest_spans', 'kw_ingest_copy_spans',
+           'kw_ingest_zone', 'kw_ingest_stamps', 'kw_ingest_stamps_device', 'kw_rows_emit_stamps_device',
            'kw_sort_create', 'kw_sort_destroy', 'kw_sort_last_error', 'kw_sort_last_ms', 'kw_sort_keys',
            'kw_sort_gather')
 
@@ -193,6 +194,12 @@ def lib() -> ctypes.CDLL:
     L.kw_ingest_spans.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i32),
                                   ctypes.POINTER(vp), ctypes.POINTER(i64)]
     L.kw_ingest_copy_spans.argtypes = [vp, vp, vp]
+    L.kw_ingest_zone.argtypes = [vp, vp, vp, i32]
+    L.kw_ingest_stamps.argtypes = [vp, vp, vp]
+    L.kw_ingest_stamps_device.argtypes = [vp, ctypes.POINTER(vp)]
+    L.kw_rows_emit_stamps_device.argtypes = [vp, vp, vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i32), vp]
+    for f in ('kw_ingest_zone', 'kw_ingest_stamps', 'kw_ingest_stamps_device', 'kw_rows_emit_stamps_device'):
+        getattr(L, f).restype = ctypes.c_int
     L.kw_sort_create.argtypes = [i32, ctypes.POINTER(vp)]
     L.kw_sort_destroy.argtypes = [vp]
     L.kw_sort_keys.argtypes = [vp, vp, i32, i64, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64),

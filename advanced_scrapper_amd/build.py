@@ -47,6 +47,7 @@ def _kw_sources():
     srcs.append(os.path.join(HERE, '..', 'include', 'kwrows.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwingest.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwsort.h'))
+    srcs.append(os.path.join(HERE, '..', 'include', 'kwstamps.h'))
     return srcs
 
 
@@ -88,7 +89,7 @@ def build_kwcsv(force: bool = False) -> str:
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, 'libkwcsv.so')
     src = os.path.join(CSRC, 'kwcsv.c')
-    if force or _stale(out, [src]):
+    if force or _stale(out, [src, os.path.join(HERE, '..', 'include', 'kwstamps.h')]):
         _run(['gcc', '-O2', '-fopenmp', '-fPIC', '-shared', '-Wall', '-o', out, src])
     return out
 

@@ -22,10 +22,14 @@
  * ranges in parallel and compacts them into kwcsv_parse's exact layout, kwcsv_utf8_ok_mt checks several
  * columns at once, kwcsv_pack_mt packs the arena, kwcsv_dates parses the dataset's date layout.
  */
+#define _GNU_SOURCE   /* tm_gmtoff */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <omp.h>
+
+#include "../../include/kwstamps.h"
 
 #define KWCSV_QUOTED 1u   /* the cell was quoted */
 #define KWCSV_NA 2u       /* the cell is one of the NA strings: NaN */
@@ -783,4 +787,82 @@ int64_t kwcsv_emit_mt(const uint8_t *cells, const int64_t *coff, const uint8_t *
     free(dfl);
     free(used);
     return 0;
+}
+
+/*
+ * The process's zone table (include/kwstamps.h) over [1970-01-01, 2100-01-01) UTC from localtime_r's tm_gmtoff --
+ * the libc state Python's time module reads after time.tzset(): the offset sampled every step_s seconds, every
+ * change between two samples bisected to the second.  (Two changes inside one step that end on the offset the step
+ * began with are not seen: DESIGN.md §1.)  utc != 0: the one unbounded entry of a process in UTC.  at[cap + 1],
+ * off[cap]; returns the entries, or -1 when the zone has more than cap or localtime_r fails at an instant it was
+ * asked (nothing usable is left in at / off: no table rather than a wrong entry).
+ */
+#define GMTOFF_FAILED INT32_MIN
+
+static int32_t gmtoff_at(int64_t u)     /* GMTOFF_FAILED when localtime_r gives no answer */
+{
+    struct tm tm;
+    const time_t tt = (time_t)u;
+    memset(&tm, 0, sizeof(tm));
+    if (!localtime_r(&tt, &tm)) return GMTOFF_FAILED;
+    return (int32_t)tm.tm_gmtoff;
+}
+
+int32_t kwcsv_zone_table(int32_t utc, int64_t step_s, int64_t *at, int32_t *off, int32_t cap)
+{
+    const int64_t lo = 0, hi = 4102444800LL;
+    if (cap < 1 || step_s < 1) return -1;
+    if (utc) {
+        at[0] = INT64_MIN;
+        at[1] = INT64_MAX;
+        off[0] = 0;
+        return 1;
+    }
+    int32_t n = 1;
+    at[0] = lo;
+    off[0] = gmtoff_at(lo);
+    if (off[0] == GMTOFF_FAILED) return -1;
+    for (int64_t u = lo; u < hi;) {
+        int64_t v = u + step_s < hi ? u + step_s : hi;
+        const int32_t ov = gmtoff_at(v);
+        if (ov == GMTOFF_FAILED) return -1;
+        if (ov != off[n - 1]) {
+            int64_t a = u, b = v;              /* the offset at a is off[n - 1], at b another */
+            while (b - a > 1) {
+                const int64_t m = a + (b - a) / 2;
+                const int32_t om = gmtoff_at(m);
+                if (om == GMTOFF_FAILED) return -1;
+                if (om == off[n - 1]) a = m; else b = m;
+            }
+            if (n == cap) return -1;
+            at[n] = b;
+            off[n] = gmtoff_at(b);
+            if (off[n] == GMTOFF_FAILED) return -1;
+            ++n;
+            v = b;                             /* the next step starts at the change */
+        }
+        u = v;
+    }
+    at[n] = hi;
+    return n;
+}
+
+/*
+ * time_unix of n date rows (kwcsv_dates_iso's arrays) under the zone table at[n_trans + 1] / off[n_trans], by the
+ * rule of include/kwstamps.h: stamps[r] and native[r] (1 = the value is final; 0 = the caller asks timestamp(),
+ * stamps[r] = 0).  off_s is not read (a kind-3 row's us is its instant already); it keeps the arrays together.
+ */
+void kwcsv_stamps_local(const int64_t *us, const uint8_t *kind, const int32_t *off_s, int64_t n, const int64_t *at,
+                        const int32_t *off, int32_t n_trans, int64_t *stamps, uint8_t *native, int32_t nthreads)
+{
+    (void)off_s;
+    const int64_t nt = nthreads > 1 ? nthreads : 1;
+    kwst_zone z;
+    z.at = at;
+    z.off = off;
+    z.n = n_trans;
+    z.lo = n_trans > 0 ? at[0] + KWST_MARGIN : 0;
+    z.hi = n_trans > 0 ? at[n_trans] - KWST_MARGIN : 0;
+    #pragma omp parallel for num_threads(nt) schedule(static)
+    for (int64_t r = 0; r < n; ++r) native[r] = (uint8_t)kwst_row(&z, us[r], kind[r], &stamps[r]);
 }

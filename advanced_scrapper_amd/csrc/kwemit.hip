@@ -523,29 +523,30 @@ extern "C" int kw_rows_cells_device(kw_rows *h, const uint8_t *d_cells, const in
     return KW_OK;
 }
 
-extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stamp_by_doc, int64_t n_docs,
-                            int64_t n_rows_use, int64_t *n_out_bytes, int32_t *verdict, void *stream)
+// kw_rows_emit (stamp_by_doc: a host array, uploaded) and kw_rows_emit_stamps_device (d_stamp_by_doc: borrowed)
+static int emit_rows(const char *who, kw_rows *h, const int32_t *cols, const int64_t *stamp_by_doc, const int64_t *d_stamp_by_doc,
+                     int64_t n_docs, int64_t n_rows_use, int64_t *n_out_bytes, int32_t *verdict, void *stream)
 {
     using namespace rw;
     typedef unsigned long long u64;
     if (!h) return KW_EINVAL;
     if (h->emit) h->emit->have = false;
-    if (!cols || !n_out_bytes || !verdict || (n_docs > 0 && !stamp_by_doc)) {
-        h->err = "kw_rows_emit: bad arguments";
+    if (!cols || !n_out_bytes || !verdict || (n_docs > 0 && !stamp_by_doc && !d_stamp_by_doc)) {
+        h->err = std::string(who) + ": bad arguments";
         return KW_EINVAL;
     }
     *n_out_bytes = 0;
     *verdict = KW_EMIT_OK;
     Emit *E = h->emit;
-    if (!h->have_run || !h->run_rows) { h->err = "kw_rows_emit: no run that left rows"; return KW_ESTATE; }
-    if (!E || E->cells_docs < 0) { h->err = "kw_rows_emit: no cells (kw_rows_cells)"; return KW_ESTATE; }
+    if (!h->have_run || !h->run_rows) { h->err = std::string(who) + ": no run that left rows"; return KW_ESTATE; }
+    if (!E || E->cells_docs < 0) { h->err = std::string(who) + ": no cells (kw_rows_cells)"; return KW_ESTATE; }
     if (n_docs != h->run_docs || n_docs != E->cells_docs) {
-        h->err = "kw_rows_emit: n_docs differs from the run's or the cells'";
+        h->err = std::string(who) + ": n_docs differs from the run's or the cells'";
         return KW_ESTATE;
     }
     for (int c = 0; c < 6; ++c)
-        if (cols[c] < 0 || cols[c] >= E->ncols) { h->err = "kw_rows_emit: a column index outside the cells"; return KW_EINVAL; }
-    if (n_rows_use < 0 || n_rows_use > h->n_rows) { h->err = "kw_rows_emit: n_rows_use outside [0, n_rows]"; return KW_EINVAL; }
+        if (cols[c] < 0 || cols[c] >= E->ncols) { h->err = std::string(who) + ": a column index outside the cells"; return KW_EINVAL; }
+    if (n_rows_use < 0 || n_rows_use > h->n_rows) { h->err = std::string(who) + ": n_rows_use outside [0, n_rows]"; return KW_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     RWCHK(h, hipSetDevice(h->device));
     for (auto &m : E->ms) m = 0.f;
@@ -561,7 +562,7 @@ extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stam
         return KW_OK;
     }
     const size_t ncell = (size_t)nd * 6;
-    if ((rc = ensure(h, E->stamps, (size_t)nd * 8)) || (rc = ensure(h, E->tcnt, ((size_t)nt + 1) * 8)) ||
+    if ((!d_stamp_by_doc && (rc = ensure(h, E->stamps, (size_t)nd * 8))) || (rc = ensure(h, E->tcnt, ((size_t)nt + 1) * 8)) ||
         (rc = ensure(h, E->tcur, (size_t)nt * 4)) || (rc = ensure(h, E->seg, (size_t)nu * 4)) ||
         (rc = ensure(h, E->ord, (size_t)nu * 4)) || (rc = ensure(h, E->used, nd)) ||
         (rc = ensure(h, E->dfl, (size_t)nd * 4)) || (rc = ensure(h, E->slen, (ncell + 1) * 8)) ||
@@ -578,13 +579,13 @@ extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stam
     const uint8_t *cbuf = E->borrowed ? E->b_cells : (const uint8_t *)E->c_buf.p;
     const uint8_t *cfl = E->borrowed ? E->b_cfl : (const uint8_t *)E->c_fl.p;
     const int64_t *coff = E->borrowed ? E->b_coff : (const int64_t *)E->c_off.p;
-    const int64_t *stamps = (const int64_t *)E->stamps.p;
+    const int64_t *stamps = d_stamp_by_doc ? d_stamp_by_doc : (const int64_t *)E->stamps.p;
     u64 *tcnt = (u64 *)E->tcnt.p, *slen = (u64 *)E->slen.p, *llen = (u64 *)E->llen.p, *jl = (u64 *)E->jl.p;
     uint32_t *seg = (uint32_t *)E->seg.p, *ord = (uint32_t *)E->ord.p, *dfl = (uint32_t *)E->dfl.p;
     uint8_t *used = (uint8_t *)E->used.p, *cq = (uint8_t *)E->cq.p;
 
     RWCHK(h, hipEventRecord(E->ev[0], st));
-    RWCHK(h, hipMemcpyAsync(E->stamps.p, stamp_by_doc, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+    if (!d_stamp_by_doc) RWCHK(h, hipMemcpyAsync(E->stamps.p, stamp_by_doc, (size_t)nd * 8, hipMemcpyHostToDevice, st));
     RWCHK(h, hipMemsetAsync(E->tot, 0, E_WORDS * 8, st));
     RWCHK(h, hipMemsetAsync(tcnt, 0, ((size_t)nt + 1) * 8, st));
     if (nt) RWCHK(h, hipMemsetAsync(E->tcur.p, 0, (size_t)nt * 4, st));
@@ -619,7 +620,7 @@ extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stam
     RWCHK(h, hipMemcpyAsync(tot, E->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     RWCHK(h, hipStreamSynchronize(st));
     RWCHK(h, hipGetLastError());
-    if (tot[E_BAD]) { h->err = "kw_rows_emit: a row's ticker or document is beyond the tables"; return KW_EINVAL; }
+    if (tot[E_BAD]) { h->err = std::string(who) + ": a row's ticker or document is beyond the tables"; return KW_EINVAL; }
     for (int k = 0; k < 2; ++k) RWCHK(h, hipEventElapsedTime(&E->ms[k], E->ev[k], E->ev[k + 1]));
     if (tot[E_NUL]) {
         *verdict = KW_EMIT_NUL;
@@ -653,6 +654,18 @@ extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stam
     *n_out_bytes = (int64_t)nbytes;
     E->have = true;
     return KW_OK;
+}
+
+extern "C" int kw_rows_emit(kw_rows *h, const int32_t *cols, const int64_t *stamp_by_doc, int64_t n_docs,
+                            int64_t n_rows_use, int64_t *n_out_bytes, int32_t *verdict, void *stream)
+{
+    return emit_rows("kw_rows_emit", h, cols, stamp_by_doc, nullptr, n_docs, n_rows_use, n_out_bytes, verdict, stream);
+}
+
+extern "C" int kw_rows_emit_stamps_device(kw_rows *h, const int32_t *cols, const int64_t *d_stamp_by_doc, int64_t n_docs,
+                                          int64_t n_rows_use, int64_t *n_out_bytes, int32_t *verdict, void *stream)
+{
+    return emit_rows("kw_rows_emit_stamps_device", h, cols, nullptr, d_stamp_by_doc, n_docs, n_rows_use, n_out_bytes, verdict, stream);
 }
 
 extern "C" int kw_rows_emit_result(kw_rows *h, const uint8_t **out, const int64_t **line_off, const uint32_t **flags,

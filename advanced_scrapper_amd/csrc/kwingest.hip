@@ -16,6 +16,8 @@
 //                      once unless the verdict is OK (the offsets of a refused text are not all written).
 //   ig_flags_kernel    lane = cell: CANON, the NA compare, the text witness, the columns' witnesses.
 //   ig_rows_kernel     lane = row: the date cell by the ISO rule, the two arena segment lengths.
+//   ig_stamps_kernel   lane = row, once a zone table is set (kw_ingest_zone): time_unix from the date arrays by the
+//                      rule of kwstamps.h, the table staged in LDS.
 //   ig_gather_kernel   lane = 16 arena bytes: the segment by binary search in the scanned offsets.
 //   ig_spans_kernel    on request (kw_ingest_spans), after an OK parse: the tile masks once more, for every taken
 //                      record's first byte and the byte after its last.
@@ -27,6 +29,8 @@
 #include <string>
 
 #include "../../include/kwingest.h"
+#define KWST_FN __device__ __forceinline__ static
+#include "../../include/kwstamps.h"
 #include "kwenv.hpp"
 
 namespace ig {
@@ -689,6 +693,38 @@ __global__ __launch_bounds__(BLOCK) void ig_rows_kernel(const Dev *__restrict__ 
     }
 }
 
+// lane = row: time_unix of the row's date under the zone table zat[zn + 1] / zoff[zn] (kwstamps.h: the solve's up to
+// four utcoff lookups are ten-step binary searches over the table's copy in LDS, staged once a block; 64-bit integer
+// arithmetic only).  stamps[r] and native[r] for every taken row; a block without rows stages nothing.
+__global__ __launch_bounds__(BLOCK) void ig_stamps_kernel(const Dev *__restrict__ D, const long long *__restrict__ us,
+                                                          const uint8_t *__restrict__ kind,
+                                                          const int64_t *__restrict__ zat, const int32_t *__restrict__ zoff,
+                                                          int zn, int64_t *__restrict__ stamps, uint8_t *__restrict__ native)
+{
+    __shared__ int64_t s_at[KWST_CAPACITY];
+    __shared__ int32_t s_off[KWST_CAPACITY];
+    if (D->verdict != KW_INGEST_OK) return;
+    const long long nr = D->n_rows;
+    if ((long long)blockIdx.x * BLOCK >= nr) return;   // (the whole block)
+    for (int k = threadIdx.x; k < zn; k += BLOCK) {
+        s_at[k] = zat[k];
+        s_off[k] = zoff[k];
+    }
+    __syncthreads();
+    kwst_zone z;
+    z.at = s_at;
+    z.off = s_off;
+    z.n = zn;
+    z.lo = zat[0] + KWST_MARGIN;
+    z.hi = zat[zn] - KWST_MARGIN;
+    for (long long r = (long long)blockIdx.x * BLOCK + threadIdx.x; r < nr; r += (long long)gridDim.x * BLOCK) {
+        int64_t v;
+        const int nat = kwst_row(&z, (int64_t)us[r], (int)kind[r], &v);
+        stamps[r] = v;
+        native[r] = (uint8_t)nat;
+    }
+}
+
 // lane = row: the length and the flags of column col's cell
 __global__ __launch_bounds__(BLOCK) void ig_collen_kernel(const Dev *__restrict__ D, const long long *__restrict__ coff,
                                                           const uint8_t *__restrict__ cfl, int ncols, int col,
@@ -764,9 +800,12 @@ struct kw_ingest {
     ig::Dev *D = nullptr;          // device
     ig::Dev *H = nullptr;          // pinned host copy
     ig::Buf tiles, cells, coff, cflw, cfl, arena, aoff, us, kind, doff, col_buf, col_off, col_fl;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    float ms[4] = {0, 0, 0, 0};
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4], [5]: around the stamps kernel
+    float ms[5] = {0, 0, 0, 0, 0};
     bool have = false;             // an OK parse whose buffers stand
+    ig::Buf zat, zoff, stamps, native;   // the zone table (kw_ingest_zone) and the rows' stamps under it
+    int zn = 0;                    // the table's entries, 0: none
+    bool have_stamps = false;      // the last OK parse computed stamps
     void *stage[2] = {nullptr, nullptr};   // pinned staging windows (kw_ingest_stage)
     size_t stage_cap[2] = {0, 0};
     ig::Buf text;                  // kw_ingest_upload's device copy of a window
@@ -870,7 +909,7 @@ extern "C" int kw_ingest_destroy(kw_ingest *h)
     if (!h) return KW_OK;
     (void)hipSetDevice(h->device);
     Buf *bufs[] = {&h->tiles, &h->cells, &h->coff, &h->cflw, &h->cfl, &h->arena, &h->aoff, &h->us, &h->kind, &h->doff,
-                   &h->col_buf, &h->col_off, &h->col_fl, &h->spans};
+                   &h->col_buf, &h->col_off, &h->col_fl, &h->spans, &h->zat, &h->zoff, &h->stamps, &h->native};
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (h->d_na) (void)hipFree(h->d_na);
@@ -894,6 +933,7 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     if (!h) return KW_EINVAL;
     h->have = false;
     h->have_spans = false;
+    h->have_stamps = false;
     if (!n_rows || !consumed || !verdict || !bad_pos || n_bytes < 0 || n_bytes >= (int64_t)1 << 31 || max_rows < 1 ||
         (n_bytes > 0 && !d_text) || ((uintptr_t)d_text & 15u)) {
         h->err = "kw_ingest_parse: bad arguments";
@@ -919,6 +959,8 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
         (rc = ensure(h, h->aoff, (size_t)(2 * rows_cap + 1) * 8)) || (rc = ensure(h, h->us, (size_t)rows_cap * 8)) ||
         (rc = ensure(h, h->kind, (size_t)rows_cap)) || (rc = ensure(h, h->doff, (size_t)rows_cap * 4)))
         return rc;
+    const int zn = h->zn;
+    if (zn && ((rc = ensure(h, h->stamps, (size_t)rows_cap * 8)) || (rc = ensure(h, h->native, (size_t)rows_cap)))) return rc;
     Dev init;
     memset(&init, 0, sizeof(init));
     init.errs.nul = init.errs.utf8 = init.errs.quote = init.errs.cr = init.errs.blank = init.errs.fields = NONE;
@@ -976,6 +1018,13 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     hipLaunchKernelGGL(ig_rows_kernel, grid_for(rows_cap, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
                        (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p, (int)ncols, h->cols,
                        (long long *)h->us.p, (uint8_t *)h->kind.p, (int *)h->doff.p, (u64 *)h->aoff.p);
+    if (zn) {
+        IGCHK(h, hipEventRecord(h->ev[4], st));
+        hipLaunchKernelGGL(ig_stamps_kernel, grid_for(rows_cap, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
+                           (const long long *)h->us.p, (const uint8_t *)h->kind.p, (const int64_t *)h->zat.p,
+                           (const int32_t *)h->zoff.p, zn, (int64_t *)h->stamps.p, (uint8_t *)h->native.p);
+        IGCHK(h, hipEventRecord(h->ev[5], st));
+    }
     {
         ScanArgs S{};
         S.a[0] = (u64 *)h->aoff.p;
@@ -995,11 +1044,14 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     IGCHK(h, hipGetLastError());
     for (int k = 0; k < 3; ++k) IGCHK(h, hipEventElapsedTime(&h->ms[k], h->ev[k], h->ev[k + 1]));
     IGCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[3]));
+    h->ms[4] = 0.f;
+    if (zn) IGCHK(h, hipEventElapsedTime(&h->ms[4], h->ev[4], h->ev[5]));
     *verdict = h->H->verdict;
     *bad_pos = h->H->bad_pos;
     *n_rows = h->H->n_rows;
     *consumed = h->H->consumed;
     h->have = h->H->verdict == KW_INGEST_OK;
+    h->have_stamps = h->have && zn > 0;
     h->ptext = d_text;
     h->pn = n;
     h->pfinal = A.final_;
@@ -1103,6 +1155,53 @@ extern "C" int kw_ingest_dates_iso(kw_ingest *h, int64_t *us, uint8_t *kind, int
     if (nr && (!us || !kind || !off_s)) { h->err = "kw_ingest_dates_iso: bad arguments"; return KW_EINVAL; }
     if (!nr) return KW_OK;
     return copy_dates(h, nr, us, kind, off_s);
+}
+
+extern "C" int kw_ingest_zone(kw_ingest *h, const int64_t *at, const int32_t *off, int32_t n_trans)
+{
+    if (!h) return KW_EINVAL;
+    if (n_trans < 0 || n_trans > KWST_CAPACITY || (n_trans > 0 && (!at || !off))) {
+        h->err = "kw_ingest_zone: bad arguments";
+        return KW_EINVAL;
+    }
+    for (int32_t k = 0; k < n_trans; ++k)
+        if (at[k] >= at[k + 1]) { h->err = "kw_ingest_zone: the instants do not ascend"; return KW_EINVAL; }
+    if (n_trans > 0 && (at[0] > INT64_MAX - KWST_MARGIN || at[n_trans] < INT64_MIN + KWST_MARGIN)) {
+        h->err = "kw_ingest_zone: bad arguments";
+        return KW_EINVAL;
+    }
+    h->zn = 0;
+    if (n_trans == 0) return KW_OK;
+    IGCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->zat, ((size_t)n_trans + 1) * 8)) || (rc = ensure(h, h->zoff, (size_t)n_trans * 4))) return rc;
+    IGCHK(h, hipMemcpy(h->zat.p, at, ((size_t)n_trans + 1) * 8, hipMemcpyHostToDevice));
+    IGCHK(h, hipMemcpy(h->zoff.p, off, (size_t)n_trans * 4, hipMemcpyHostToDevice));
+    h->zn = n_trans;
+    return KW_OK;
+}
+
+extern "C" int kw_ingest_stamps(kw_ingest *h, int64_t *stamps, uint8_t *native)
+{
+    IG_NEED_PARSE(h, "kw_ingest_stamps");
+    if (!h->have_stamps) { h->err = "kw_ingest_stamps: the parse had no zone table"; return KW_ESTATE; }
+    const size_t nr = (size_t)h->H->n_rows;
+    if (nr && (!stamps || !native)) { h->err = "kw_ingest_stamps: bad arguments"; return KW_EINVAL; }
+    if (!nr) return KW_OK;
+    IGCHK(h, hipSetDevice(h->device));
+    IGCHK(h, hipMemcpyAsync(stamps, h->stamps.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
+    IGCHK(h, hipMemcpyAsync(native, h->native.p, nr, hipMemcpyDeviceToHost, h->stream));
+    IGCHK(h, hipStreamSynchronize(h->stream));
+    return KW_OK;
+}
+
+extern "C" int kw_ingest_stamps_device(kw_ingest *h, const int64_t **d_stamps)
+{
+    IG_NEED_PARSE(h, "kw_ingest_stamps_device");
+    if (!h->have_stamps) { h->err = "kw_ingest_stamps_device: the parse had no zone table"; return KW_ESTATE; }
+    if (!d_stamps) { h->err = "kw_ingest_stamps_device: bad arguments"; return KW_EINVAL; }
+    *d_stamps = (const int64_t *)h->stamps.p;
+    return KW_OK;
 }
 
 extern "C" int kw_ingest_column_flags(kw_ingest *h, int32_t *witness)
@@ -1239,6 +1338,6 @@ extern "C" int kw_ingest_copy_spans(kw_ingest *h, int64_t *start, int64_t *end)
 extern "C" int kw_ingest_last_ms(kw_ingest *h, float *ms, int32_t n)
 {
     if (!h || !ms || n < 0) return KW_EINVAL;
-    for (int k = 0; k < n && k < 4; ++k) ms[k] = h->ms[k];
+    for (int k = 0; k < n && k < 5; ++k) ms[k] = h->ms[k];
     return KW_OK;
 }

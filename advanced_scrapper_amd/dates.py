@@ -33,6 +33,7 @@ import re
 import time
 from datetime import datetime, timedelta
 
+import numpy as np
 from dateutil import parser as _dparser
 
 _ISO = re.compile(r'([0-9]{4})-([0-9]{2})-([0-9]{2})[ T]([0-9]{2}):([0-9]{2}):([0-9]{2})'
@@ -117,15 +118,17 @@ class Dates:
     ``None`` / dateutil results like the list ``[parse_date(str(v)) if notna(v) else None]``, held as arrays for
     the rows of the ISO rule (kind 1: the 19-byte layout, epoch µs, naive read as UTC; kind 4: the same with a
     fraction; kind 3: aware, the instant's epoch µs and ``off`` its UTC offset in seconds; kind 2: None) and as
-    objects for the others (kind 0: ``slow[row]``, dateutil's result).  ``epoch_us_arrays`` and ``utc_stamps``
-    give the write path integer forms without building a ``datetime`` per row."""
+    objects for the others (kind 0: ``slow[row]``, dateutil's result).  ``epoch_us_arrays``, ``utc_stamps`` and
+    ``local_stamps`` give the write path integer forms without building a ``datetime`` per row.  ``stats``: the
+    counters of the read the chunk came from, if it keeps any (``stamps_slow``); ``device``: the rows' stamps as the
+    ingest's device computed them, ``(stamps, native, pointer getter)`` (ingest.DeviceChunk.dates), or ``None``."""
 
-    __slots__ = ('us', 'kind', 'slow', 'off')
+    __slots__ = ('us', 'kind', 'slow', 'off', 'stats', 'device', 'stamps_slow')
 
-    def __init__(self, us, kind, slow, off=None):
+    def __init__(self, us, kind, slow, off=None, stats=None):
         self.us, self.kind, self.slow = us, kind, slow
+        self.stats, self.device, self.stamps_slow = stats, None, 0
         if off is None:
-            import numpy as np
             off = np.zeros(len(kind), dtype=np.int32)
         self.off = off
 
@@ -152,7 +155,6 @@ class Dates:
         instant's, which is what kind 3 holds); raises TypeError for a date whose tzinfo has no UTC offset, as
         epoch_us does."""
         from .kb import epoch_us
-        import numpy as np
         us = np.array(self.us, dtype=np.int64, copy=True)
         ok = (self.kind != 2).astype(np.uint8)
         for r, d in self.slow.items():
@@ -168,7 +170,6 @@ class Dates:
         second is possible); the others call timestamp(), and the first of them that raises (e.g. a year-1 date)
         stops there: ``k`` is its index in ``rows`` and ``exc`` the exception (``k = len(rows)``, ``exc = None``
         when none raises; ``stamps[:k]`` are valid)."""
-        import numpy as np
         rows = np.asarray(rows, dtype=np.int64)
         kind = self.kind[rows]
         if not local_zone_is_utc() and not (len(rows) and bool((kind == 3).all())):
@@ -182,3 +183,44 @@ class Dates:
             except Exception as exc:   # noqa: BLE001 - the reference's append_to_csv raises here (:131-132)
                 return out, j, exc
         return out, len(rows), None
+
+    def _count_slow(self, n: int) -> None:
+        self.stamps_slow += n
+        if self.stats is not None and n:
+            self.stats['stamps_slow'] = self.stats.get('stamps_slow', 0) + n
+
+    def finish_stamps(self, rows, out, native):
+        """``out`` with the rows that are not ``native`` filled by ``timestamp()``, one by one, in order: the
+        ``(stamps, k, exc)`` of :meth:`utc_stamps`.  Counts those rows (``stamps_slow``), the raising one included."""
+        slow = np.flatnonzero(~native).tolist()
+        for i, j in enumerate(slow):
+            try:
+                out[j] = int(self[int(rows[j])].timestamp())
+            except Exception as exc:   # noqa: BLE001 - the reference's append_to_csv raises here (:131-132)
+                self._count_slow(i + 1)
+                return out, j, exc
+        self._count_slow(len(slow))
+        return out, len(rows), None
+
+    def local_stamps(self, rows):
+        """``(stamps, k, exc)`` as :meth:`utc_stamps` gives them, in every local time zone: ``int(d.timestamp())`` of
+        the given rows' dates, the rows of the ISO rule from the integer arrays under the process's zone table
+        (zone.table, ``kwcsv_stamps_local``: include/kwstamps.h), the others -- kinds 0, and dates the table does not
+        answer for -- by ``timestamp()`` itself, one by one, in order; the first of them that raises stops there
+        (``k`` its index in ``rows``, ``stamps[:k]`` valid).  Without a table (``KW_STAMPS_NATIVE=0``, a zone over
+        the table's capacity) the routing before it: :meth:`utc_stamps` where that answers, else every row's
+        ``timestamp()``.  ``stamps_slow`` (here and in ``stats``) grows by the rows that called ``timestamp()``."""
+        from . import zone
+        from .ingest import host_threads
+        rows = np.asarray(rows, dtype=np.int64)
+        tab = zone.table()
+        if tab is not None:
+            out, native = zone.stamps_local(self.us[rows], self.kind[rows], self.off[rows], tab, host_threads())
+            return self.finish_stamps(rows, out, native.astype(bool))
+        fast = self.utc_stamps(rows)
+        if fast is not None:
+            kind, us = self.kind[rows], self.us[rows]
+            direct = ((kind == 1) | (kind == 3) | (kind == 4)) & ((us % 1000000 == 0) | ((us >= 0) & (us < STAMP_BOUND)))
+            self._count_slow(int((~direct[:fast[1] + (fast[2] is not None)]).sum()))
+            return fast
+        return self.finish_stamps(rows, np.zeros(len(rows), dtype=np.int64), np.zeros(len(rows), dtype=bool))

@@ -343,12 +343,14 @@ def render_native(chunk, raw_rows, stamps_by_doc, tickers):
              flags[a:b], rd[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
 
 
-def render_device(chunk, matcher, stamps_by_doc, n_rows_use: int):
+def render_device(chunk, matcher, stamps_by_doc, n_rows_use: int, d_stamps=None):
     """:func:`render_native`'s list of 6-tuples for the first ``n_rows_use`` rows of ``matcher``'s last
     ``rows_device``, rendered on the GPU from the chunk's tokenized cells and the JSON cells still in device
     memory (csrc/kwemit.hip, ``kw_rows_emit``): the line bytes are memoryviews over the handle's pinned host
     buffer, valid until the next call.  ``None`` as :func:`render_native` (a NUL cell, a platform line end
-    other than "\n"); a library error raises ``KwError``."""
+    other than "\n"); a library error raises ``KwError``.  ``d_stamps`` (an ingest.DeviceChunk only): the chunk's
+    stamps as the ingest computed them in device memory (``kw_rows_emit_stamps_device``); ``stamps_by_doc`` is then
+    not read and may be ``None``."""
     if n_rows_use == 0:
         return []
     if not (_FAST_OK and _NL_ONLY):
@@ -356,7 +358,7 @@ def render_device(chunk, matcher, stamps_by_doc, n_rows_use: int):
     cols = np.asarray([chunk.col[k] for k in ('date_time', 'title', 'url', 'source', 'source_url', 'article_text')],
                       dtype=np.int32)
     if hasattr(chunk, 'device_cells'):       # an ingest.DeviceChunk: the cells are in device memory already
-        got = matcher.rows_emit_device(chunk, cols, stamps_by_doc, int(n_rows_use))
+        got = matcher.rows_emit_device(chunk, cols, stamps_by_doc, int(n_rows_use), d_stamps)
     else:
         got = matcher.rows_emit(chunk.cells, cols, stamps_by_doc, int(n_rows_use))
     if got is None:

@@ -191,10 +191,10 @@ def _dates_of(us, kind, off, strings, stats=None):
         except Exception as exc:   # noqa: BLE001 - match_keywords.py:152 raises here for this row
             if stats is not None:
                 stats['dates_slow'] = stats.get('dates_slow', 0) + i + 1
-            return Dates(us[:r], kind[:r], {k: v for k, v in slow.items() if k < r}, off[:r]), exc
+            return Dates(us[:r], kind[:r], {k: v for k, v in slow.items() if k < r}, off[:r], stats), exc
     if stats is not None and rows:
         stats['dates_slow'] = stats.get('dates_slow', 0) + len(rows)
-    return Dates(us, kind, slow, off), None
+    return Dates(us, kind, slow, off, stats), None
 
 
 def _split_header(buf: bytes):
@@ -463,6 +463,7 @@ class DeviceIngest:
         self.h = h
         self.gen = 0               # parses so far: a DeviceChunk belongs to one
         self.n_rows = 0
+        self.zone_key = None       # the table kw_ingest_zone holds (set_zone), None: none
         self._stage = [None, None]
 
     def _check(self, rc: int) -> None:
@@ -527,6 +528,36 @@ class DeviceIngest:
         self._check(self._n.lib().kw_ingest_dates_iso(self.h, _p(us), _p(kind), _p(off)))
         return us[:self.n_rows], kind[:self.n_rows], off[:self.n_rows]
 
+    def set_zone(self, tab) -> None:
+        """kw_ingest_zone: the zone table ``(at, off)`` (zone.table) the parses from now on compute the rows' stamps
+        under; ``None`` takes it away.  The same table again is not uploaded twice."""
+        key = None if tab is None else (tab[0].tobytes(), tab[1].tobytes())
+        if key == self.zone_key:
+            return
+        if tab is None:
+            self._check(self._n.lib().kw_ingest_zone(self.h, None, None, 0))
+        else:
+            at = np.ascontiguousarray(tab[0], dtype=np.int64)
+            off = np.ascontiguousarray(tab[1], dtype=np.int32)
+            if len(at) != len(off) + 1:
+                raise ValueError('zone table: n + 1 instants for n offsets')
+            self._check(self._n.lib().kw_ingest_zone(self.h, _p(at), _p(off), len(off)))
+        self.zone_key = key
+
+    def stamps(self):
+        """kw_ingest_stamps: ``(stamps int64[n], native uint8[n])`` of the last parse's rows under the handle's zone
+        table (include/kwstamps.h); only after a parse that had one."""
+        st = np.zeros(max(self.n_rows, 1), dtype=np.int64)
+        na = np.zeros(max(self.n_rows, 1), dtype=np.uint8)
+        self._check(self._n.lib().kw_ingest_stamps(self.h, _p(st), _p(na)))
+        return st[:self.n_rows], na[:self.n_rows]
+
+    def stamps_device(self):
+        """kw_ingest_stamps_device: the device pointer of the last parse's stamps, valid until the next parse."""
+        p = ctypes.c_void_p()
+        self._check(self._n.lib().kw_ingest_stamps_device(self.h, ctypes.byref(p)))
+        return p
+
     def column_flags(self) -> np.ndarray:
         w = np.zeros(6, dtype=np.int32)
         self._check(self._n.lib().kw_ingest_column_flags(self.h, _p(w)))
@@ -572,6 +603,13 @@ class DeviceIngest:
         v = np.zeros(4, dtype=np.float32)
         self._check(self._n.lib().kw_ingest_last_ms(self.h, _p(v), 4))
         return dict(zip(('classify', 'cells', 'arena', 'all'), (float(x) for x in v)))
+
+    def stamps_ms(self) -> float:
+        """kw_ingest_last_ms' fifth value: the device time (ms) of the last parse's stamps kernel (0 without a zone
+        table; a part of ``arena`` and of ``all``)."""
+        v = np.zeros(5, dtype=np.float32)
+        self._check(self._n.lib().kw_ingest_last_ms(self.h, _p(v), 5))
+        return float(v[4])
 
     def close(self):
         if self.h is not None and self.h.value:
@@ -624,6 +662,10 @@ class DeviceChunk(NativeChunk):
     def device_cells(self):
         return self._live().cells_device()
 
+    def device_stamps(self):
+        """The device pointer of the rows' stamps (kw_ingest_stamps_device), while the chunk's buffers stand."""
+        return self._live().stamps_device()
+
     def column_values(self, name: str, limit: Optional[int] = None) -> List:
         """The first ``limit`` cells of one column as pandas gives them (``str`` / NaN), from that column alone."""
         if self._cells is not None:
@@ -647,7 +689,15 @@ class DeviceChunk(NativeChunk):
             mv, o = memoryview(buf), o.tolist()
             return (bytes(mv[o[r]:o[r + 1]]).decode('utf-8') for r in rows)
 
-        return _dates_of(us, kind, off, strings, self.stats)
+        dates, error = _dates_of(us, kind, off, strings, self.stats)
+        if dev.zone_key is not None:
+            # the device's stamps of these rows; native only where the host's kinds still say so (the zero-offset
+            # guard and KW_DATES_ISO=0 hand rows back to dateutil)
+            st, na = dev.stamps()
+            n = len(dates)
+            k = dates.kind
+            dates.device = (st[:n], (na[:n] != 0) & ((k == 1) | (k == 3) | (k == 4)), self.device_stamps)
+        return dates, error
 
 
 def _host_chunk(data, buf, pos, chunksize, ncols, names, need_idx, index0, head_end, starts):
@@ -673,12 +723,15 @@ def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[U
     other staging buffer.  A chunk the device refuses (the take rule, include/kwingest.h) goes through the host
     route alone, with its own pandas decisions, and the device resumes where that ended; a chunk without a
     text witness in a needed column is parsed by pandas, as on the host route.  ``LAST_STATS`` counts the routes and, as
-    ``dates_slow``, the rows of this read's chunks that went to dateutil (a read on the host route keeps no counters)."""
+    ``dates_slow``, the rows of this read's chunks that went to dateutil, as ``stamps_slow`` the rendered documents whose
+    ``time_unix`` came from a per-row ``timestamp()`` (a read on the host route keeps no counters).  The rows' stamps
+    are computed on the device under the process's zone table (zone.table) as it is when the read starts."""
     global LAST_STATS
     from . import _native
     from concurrent.futures import ThreadPoolExecutor
     stats = LAST_STATS = {'device': 0, 'host': 0, 'pandas': 0, 'grown': 0, 'reused': 0, 'routes': [], 'ms': [],
-                          'bytes': 0, 'wall_s': 0.0, 'wall_ms': [], 'dates_slow': 0}
+                          'bytes': 0, 'wall_s': 0.0, 'wall_ms': [], 'dates_slow': 0, 'stamps_slow': 0,
+                          'stamps_ms': []}
     data = _map(path)
     names, head, pos = _split_header(data)
     ncols = len(names)
@@ -705,6 +758,8 @@ def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[U
         per_row = len(probe) / max(1, ends)
         window = int(min(MAX_WINDOW, max(DEFAULT_WINDOW, 1.34 * chunksize * per_row)))
     dev = DeviceIngest(device, ncols, need_idx)
+    from . import zone
+    dev.set_zone(zone.table())
     pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='kw-ingest')
     import time
 
@@ -785,6 +840,7 @@ def read_chunks_device(path: str, chunksize: int, device: int = 0) -> Iterator[U
                 stats['device'] += 1
                 stats['routes'].append('device')
                 stats['ms'].append(dev.last_ms())
+                stats['stamps_ms'].append(round(dev.stamps_ms(), 4))
                 stats['bytes'] += consumed
                 stats['wall_s'] += time.perf_counter() - t0
                 stats['wall_ms'].append(round(1e3 * (time.perf_counter() - t0), 3))

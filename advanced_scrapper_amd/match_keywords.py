@@ -341,27 +341,40 @@ def _native_rows(chunk, matcher, hits, dates, error, device_emit: bool = True):
     if raw is None:
         return None
     row_doc = raw[0]
-    stamps = np.zeros(max(len(dates), 1), dtype=np.int64)
     exc, row = None, None
-    docs = np.unique(row_doc)
-    fast = dates.utc_stamps(docs) if hasattr(dates, 'utc_stamps') else None
-    if fast is not None:                       # a UTC process: naive dates' timestamp() = their epoch seconds
-        st, k, e = fast
-        stamps[docs[:k]] = st[:k]
-        if e is not None:                      # that article's append raises in the reference: rows before it
-            exc, row = e, int(docs[k])
+    dev = getattr(dates, 'device', None)       # (stamps, native, pointer): the ingest computed them on the device
+    d_stamps = None
+    if on_device and dev is not None and isinstance(chunk, DeviceChunk) and bool(dev[1][row_doc].all()):
+        d_stamps, stamps = dev[2](), None      # every rendered document's stamp is final there: no host array
     else:
-        for d in docs.tolist():                # time_unix = int(parse(date_time).timestamp()), :131-132
-            try:
-                stamps[d] = int(dates[d].timestamp())
-            except Exception as e:   # noqa: BLE001 - that article's append raises in the reference
-                exc, row = e, d
-                break
+        stamps = np.zeros(max(len(dates), 1), dtype=np.int64)
+        docs = np.unique(row_doc)
+        if dev is not None:                    # the device's stamps, the others patched in by timestamp()
+            fast = dates.finish_stamps(docs, dev[0][docs], dev[1][docs])
+        elif hasattr(dates, 'local_stamps'):   # the zone table, or the routing before it (dates.Dates.local_stamps)
+            fast = dates.local_stamps(docs)
+        else:
+            fast = None
+        if fast is not None:
+            st, k, e = fast
+            stamps[docs[:k]] = st[:k]
+            if e is not None:                      # that article's append raises in the reference: rows before it
+                exc, row = e, int(docs[k])
+        else:
+            for d in docs.tolist():                # time_unix = int(parse(date_time).timestamp()), :131-132
+                try:
+                    stamps[d] = int(dates[d].timestamp())
+                except Exception as e:   # noqa: BLE001 - that article's append raises in the reference
+                    exc, row = e, d
+                    break
     k = len(row_doc)
     if exc is not None:
         k = int(np.searchsorted(row_doc, row))   # rows are in document order
     if on_device:
-        rendered = egress.render_device(chunk, matcher, stamps, k)
+        if d_stamps is not None:
+            rendered = egress.render_device(chunk, matcher, None, k, d_stamps)
+        else:
+            rendered = egress.render_device(chunk, matcher, stamps, k)
     else:
         if exc is not None:
             raw = (raw[0][:k], raw[1][:k], raw[2], raw[3][:2 * k + 1])
@@ -732,8 +745,17 @@ def _prefetch(chunks, depth: int = 1):
 def _warm_device(device):
     """Start the HIP runtime and create the device context on a background thread (libkwmatch's
     kw_device_init, in C with the GIL released: the runtime's start-up costs a fixed fraction of a second)
-    while the KB loads and the first chunk is tokenized."""
+    while the KB loads and the first chunk is tokenized.  The process's zone table (zone.table: kwcsv_zone_table, in
+    C with the GIL released too) is built meanwhile on a thread of its own, so it delays neither the runtime's start
+    nor the main thread."""
     import threading
+
+    def table():
+        try:
+            from . import zone
+            zone.table()
+        except Exception:   # noqa: BLE001 - the first chunk's own call reports any error
+            pass
 
     def warm():
         try:
@@ -744,6 +766,7 @@ def _warm_device(device):
 
     th = threading.Thread(target=warm, name='kw-device-init', daemon=True)
     th.start()
+    threading.Thread(target=table, name='kw-zone-table', daemon=True).start()
     return th
 
 

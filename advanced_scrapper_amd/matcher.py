@@ -283,12 +283,15 @@ class GpuMatcher:
         handle.cells(cells, handle.n_docs)
         return handle.emit(cols, np.asarray(stamp_by_doc, dtype=np.int64)[:handle.n_docs], n_rows_use)
 
-    def rows_emit_device(self, chunk, cols, stamp_by_doc: np.ndarray, n_rows_use: int):
+    def rows_emit_device(self, chunk, cols, stamp_by_doc, n_rows_use: int, d_stamps=None):
         """:meth:`rows_emit` from the cells of an ingest.DeviceChunk where they lie in device memory
-        (``kw_rows_cells_device``: no download, no upload)."""
+        (``kw_rows_cells_device``: no download, no upload); with ``d_stamps`` (the chunk's stamps in device memory,
+        ingest.DeviceChunk.device_stamps) the stamps are read there too and ``stamp_by_doc`` is not."""
         handle = self.rows_handle()
         d_cells, d_coff, d_cfl, _nb = chunk.device_cells()
         handle.cells_device(d_cells, d_coff, d_cfl, handle.n_docs, len(chunk.columns))
+        if d_stamps is not None:
+            return handle.emit(cols, None, n_rows_use, d_stamps=d_stamps)
         return handle.emit(cols, np.asarray(stamp_by_doc, dtype=np.int64)[:handle.n_docs], n_rows_use)
 
     def match_device(self, texts: Sequence[str], titles: Sequence[str]):

@@ -208,21 +208,27 @@ class DeviceRows:
         must stay valid through the next :meth:`emit`."""
         self._check(_native.lib().kw_rows_cells_device(self.h, d_cells, d_coff, d_cfl, int(n_docs), int(ncols), stream))
 
-    def emit(self, cols, stamp_by_doc: np.ndarray, n_rows_use: int, stream=None):
+    def emit(self, cols, stamp_by_doc, n_rows_use: int, stream=None, d_stamps=None):
         """The first ``n_rows_use`` rows of the last :meth:`run` as CSV lines, rendered on the device from the cells
         of :meth:`cells` (``cols``: their columns of date_time, title, url, source, source_url, article_text;
         ``stamp_by_doc[d]`` = article d's time_unix), in the stable order by KB ticker index: ``(lines, line_off
         int64[n + 1], flags uint32[n], row_doc int32[n], row_ti int32[n], stamps int64[n])``, or ``None`` on the
         verdict KW_EMIT_NUL.  ``lines`` is a memoryview over the handle's pinned buffer, valid until the next
-        emit; the arrays are copies."""
+        emit; the arrays are copies.  ``d_stamps``: the stamps of the run's documents in device memory instead (a raw
+        pointer to int64[n_docs], e.g. ``kw_ingest_stamps_device``'s; ``kw_rows_emit_stamps_device``: nothing is
+        uploaded, ``stamp_by_doc`` is not read)."""
         cols = np.ascontiguousarray(cols, dtype=np.int32)
         if cols.shape != (6,):
             raise ValueError('cols: six column indexes')
-        stamps = np.ascontiguousarray(stamp_by_doc, dtype=np.int64)
         nb, verdict = ctypes.c_int64(), ctypes.c_int32()
         L = _native.lib()
-        self._check(L.kw_rows_emit(self.h, _ptr(cols), _ptr(stamps), len(stamps), int(n_rows_use), ctypes.byref(nb),
-                                   ctypes.byref(verdict), stream))
+        if d_stamps is not None:
+            self._check(L.kw_rows_emit_stamps_device(self.h, _ptr(cols), d_stamps, self.n_docs, int(n_rows_use),
+                                                     ctypes.byref(nb), ctypes.byref(verdict), stream))
+        else:
+            stamps = np.ascontiguousarray(stamp_by_doc, dtype=np.int64)
+            self._check(L.kw_rows_emit(self.h, _ptr(cols), _ptr(stamps), len(stamps), int(n_rows_use), ctypes.byref(nb),
+                                       ctypes.byref(verdict), stream))
         if verdict.value == _native.KW_EMIT_NUL:
             return None
         p = [ctypes.c_void_p() for _ in range(6)]

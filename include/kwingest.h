@@ -142,8 +142,27 @@ int kw_ingest_spans(kw_ingest *h, const int64_t **d_start, const int64_t **d_end
 /* kw_ingest_spans into host arrays start[n_rows], end[n_rows]. */
 int kw_ingest_copy_spans(kw_ingest *h, int64_t *start, int64_t *end);
 
-/* Device times (ms) of the last parse, up to 4 values: [0] classify (quote counts, NUL, UTF-8, their scan),
- * [1] cells (counts, scans, offsets and the kept bytes, the verdict, the flags), [2] arena + dates, [3] all. */
+/* The process's zone table (kwstamps.h: at[n_trans + 1] ascending instants, off[n_trans] UTC offsets in seconds,
+ * 1 <= n_trans <= 1024; host arrays, copied to the device and kept across parses).  Every OK parse from now on
+ * also computes each row's time_unix = int(datetime.timestamp()) under it (ig_stamps_kernel, after the dates, on
+ * the parse's stream): the rule of kwstamps.h on the row's us / kind, native[r] = 1 where the value is final
+ * (kinds 1, 3, 4 inside the table's range), 0 where the caller must ask timestamp() itself (stamps[r] = 0).  The
+ * rule never reads the process's zone: the caller masks the rows it hands back to dateutil (the zero-offset
+ * guard, dates.py).  Calling it again replaces the table; n_trans == 0 (at, off may be null) takes it away.
+ * KW_EINVAL: n_trans outside [0, 1024], a null array, instants that do not ascend. */
+int kw_ingest_zone(kw_ingest *h, const int64_t *at, const int32_t *off, int32_t n_trans);
+
+/* After an OK parse that had a zone table: the rows' stamps into host arrays stamps[n_rows], native[n_rows].
+ * KW_ESTATE: no such parse. */
+int kw_ingest_stamps(kw_ingest *h, int64_t *stamps, uint8_t *native);
+
+/* After an OK parse that had a zone table: *d_stamps = the stamps in device memory (n_rows int64; for
+ * kw_rows_emit_stamps_device, kwrows.h).  KW_ESTATE: no such parse. */
+int kw_ingest_stamps_device(kw_ingest *h, const int64_t **d_stamps);
+
+/* Device times (ms) of the last parse, up to 5 values: [0] classify (quote counts, NUL, UTF-8, their scan),
+ * [1] cells (counts, scans, offsets and the kept bytes, the verdict, the flags), [2] arena + dates + stamps,
+ * [3] all, [4] the stamps kernel alone (0 without a zone table; a part of [2] and [3]). */
 int kw_ingest_last_ms(kw_ingest *h, float *ms, int32_t n);
 
 const char *kw_ingest_last_error(kw_ingest *h);

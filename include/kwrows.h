@@ -109,6 +109,12 @@ int kw_rows_cells_device(kw_rows *r, const uint8_t *d_cells, const int64_t *d_co
 int kw_rows_emit(kw_rows *r, const int32_t *cols, const int64_t *stamp_by_doc, int64_t n_docs, int64_t n_rows_use,
                  int64_t *n_out_bytes, int32_t *verdict, void *stream);
 
+/* kw_rows_emit with the per-document stamps already in device memory: d_stamp_by_doc, device int64[n_docs] (e.g.
+ * kw_ingest_stamps_device's, kwingest.h), borrowed through the call and complete on `stream`.  No host array is
+ * uploaded; the same checks, verdicts and result buffers as kw_rows_emit. */
+int kw_rows_emit_stamps_device(kw_rows *r, const int32_t *cols, const int64_t *d_stamp_by_doc, int64_t n_docs,
+                               int64_t n_rows_use, int64_t *n_out_bytes, int32_t *verdict, void *stream);
+
 /* The last emit's result in pinned host memory owned by the handle, valid until the next kw_rows_emit or
  * kw_rows_destroy: n = n_rows_use rows (0 after KW_EMIT_NUL) in output order; row i's line is
  * out[line_off[i], line_off[i + 1]) (line_off[0] = 0 always), flags[i] as above, row_doc / row_ti / stamps[i] its

@@ -37,6 +37,12 @@ layout on this tree against the parent, which guards the 19-byte path.  OUT.json
 wall time inside ``chunk.dates()``, ``dates_slow`` and the ``kw_ingest_last_ms`` sums, the ``dates`` and ``arena``
 spans also per timed run (their own run-to-run spread).
 
+``--tz-ab OUT.json`` compares the routes of ``time_unix`` the same way on N articles in the 19-byte naive layout, in
+children that run under ``TZ=EST5EDT,M3.2.0,M11.1.0``: this tree (the stamps from the zone table, on the device),
+this tree with ``KW_STAMPS_NATIVE=0`` (one ``timestamp()`` per rendered document) and, with ``--parent-tree DIR``, that
+tree; then under ``TZ=UTC`` this tree against the parent.  OUT.json gets the medians and ranges, the sha256 of the
+output, the wall time of the stamp step, ``stamps_slow``, the stamps kernel's time and the table's build time.
+
 ``--sort-ab OUT.json`` compares the routes of the final sort on a re-run: an untimed first ``main()`` over N articles
 fills an output directory; the timed part is a second ``main()`` over another N articles into a copy of that
 directory, so every file the first run left takes sort_matched_csv's re-read, sort and rewrite.  A fresh child per
@@ -175,9 +181,9 @@ def timed_host(*a):
 egress.render_native = timed_host
 device = getattr(egress, 'render_device', None)      # (the parent tree has none)
 if device is not None:
-    def timed_device(chunk, matcher, stamps, k):
+    def timed_device(chunk, matcher, stamps, k, *more):
         t = time.perf_counter()
-        out = device(chunk, matcher, stamps, k)
+        out = device(chunk, matcher, stamps, k, *more)
         span['device_s'] += time.perf_counter() - t
         span['device_calls'] += 1
         if k and out is not None:
@@ -297,6 +303,58 @@ assert st['device'] == span['chunks'] > 0
 for m in st['ms']:
     for k in ('arena', 'all'):
         span[k] += m[k]
+h = hashlib.sha256()
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+import shutil
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
+TZ_CHILD = r'''
+import contextlib, hashlib, io, json, os, sys, tempfile, time
+tree, info_dir, csv_path, chunksize = sys.argv[1:5]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import egress, ingest, match_keywords as mk
+span = {'rows_s': 0.0, 'inner_s': 0.0, 'calls': 0}
+def timed(mod, name, key):
+    inner = getattr(mod, name)
+    def fn(*a, **kw):
+        t = time.perf_counter()
+        try:
+            return inner(*a, **kw)
+        finally:
+            span[key] += time.perf_counter() - t
+    setattr(mod, name, fn)
+# the stamp step = _native_rows without the calls that build the JSON cells and render the rows
+timed(mk, '_native_rows', 'rows_s')
+for mod, name in ((mk, 'assemble_json_device'), (mk, '_json_raw'), (egress, 'render_device'), (egress, 'render_native')):
+    timed(mod, name, 'inner_s')
+work = tempfile.mkdtemp(prefix='e2e_tz_')
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()):
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0
+st = ingest.LAST_STATS
+span['chunks'] = st['device'] + st['host'] + st['pandas']
+assert st['device'] == span['chunks'] > 0
+span['stamp_step_s'] = span['rows_s'] - span['inner_s']
+span['stamps_slow'] = st.get('stamps_slow')          # (the parent tree does not count them)
+span['stamps_kernel_ms'] = sum(st['stamps_ms']) if 'stamps_ms' in st else None      # kw_ingest_last_ms[4] over the chunks
+span['arena_ms'] = sum(m['arena'] for m in st['ms'])
+zone = sys.modules.get('advanced_scrapper_amd.zone')      # (the parent tree has none)
+span['zone_build_ms'] = zone.LAST_BUILD_MS if zone is not None else None
+span['zone_entries'] = (len(zone.table()[1]) if zone.table() is not None else 0) if zone is not None else None
+span['tz'] = os.environ['TZ']
 h = hashlib.sha256()
 out = os.path.join(work, 'yahoo_ticker_matched_articles')
 for fn in sorted(os.listdir(out)):
@@ -540,6 +598,61 @@ def dates_ab(args):
     assert res['z_ms']['same_bytes'] and res['naive']['same_bytes'], 'the configurations wrote different bytes'
 
 
+TZ_AB_ZONE = 'EST5EDT,M3.2.0,M11.1.0'
+
+
+def tz_ab(args):
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=0)
+    csv_path = os.path.join(work, 'articles.csv')
+    synth.to_dataframe(corpus, date_layout='naive').to_csv(csv_path, index=False)
+    del corpus
+    res = {'docs': args.docs, 'chunksize': args.chunksize, 'runs_per_config': args.runs, 'zone': TZ_AB_ZONE,
+           'csv_bytes': os.path.getsize(csv_path),
+           'timed': 'match_keywords.main() wall time in a fresh child per run; 1 warm-up + the median of the runs, the '
+                    'configurations in turn in one call; cells: the median run\'s wall time of the stamp step '
+                    '(stamp_step_s: match_keywords._native_rows without the calls that build the JSON cells and '
+                    'render the rows), the rendered documents whose time_unix came from a per-row timestamp() '
+                    '(stamps_slow; the parent does not count them), kw_ingest_last_ms[4] summed over the chunks '
+                    '(stamps_kernel_ms) and the zone table\'s build time (zone_build_ms, on the start-up thread)'}
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    spans = ('stamp_step_s',)
+
+    def config(tree, env):
+        out = rows_config(tree, env, info_dir, csv_path, args.chunksize, args.runs, TZ_CHILD, spans)
+        print('tz-ab', os.path.relpath(tree, REPO), env, round(out['median_s'], 3), file=sys.stderr, flush=True)
+        return out
+
+    try:
+        r = res['zone_runs'] = {}
+        r['native'] = config(REPO, {'TZ': TZ_AB_ZONE})
+        r['native_off'] = config(REPO, {'TZ': TZ_AB_ZONE, 'KW_STAMPS_NATIVE': '0'})
+        if parent:
+            r['parent'] = config(parent, {'TZ': TZ_AB_ZONE})
+        r['same_bytes'] = len({v['sha256'] for v in r.values()}) == 1
+        u = res['utc_runs'] = {}
+        u['native'] = config(REPO, {'TZ': 'UTC'})
+        if parent:
+            u['parent'] = config(parent, {'TZ': 'UTC'})
+        u['same_bytes'] = len({v['sha256'] for v in u.values()}) == 1
+        if parent:
+            u['inside_parent_spread'] = u['parent']['min_s'] <= u['native']['median_s'] <= u['parent']['max_s']
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    with open(args.tz_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['zone_runs']['native']['cells']['stamps_slow'] == 0
+    assert res['zone_runs']['same_bytes'] and res['utc_runs']['same_bytes'], 'the configurations wrote different bytes'
+
+
 def sort_ab(args):
     import statistics
     import subprocess
@@ -624,6 +737,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sort-ab', metavar='OUT.json', help='compare the final sort\'s routes on a re-run (see the module doc)')
     ap.add_argument('--ingest-ab', metavar='OUT.json', help='compare the article ingest\'s routes (see the module doc)')
+    ap.add_argument('--tz-ab', metavar='OUT.json', help='compare the time_unix routes in a zone that is not UTC (see the module doc)')
     ap.add_argument('--dates-ab', metavar='OUT.json', help='compare the date routes on ISO-8601 layouts (see the module doc)')
     ap.add_argument('--emit-ab', metavar='OUT.json', help='compare the CSV rows\' routes (see the module doc)')
     ap.add_argument('--rows-ab', metavar='OUT.json', help='compare the JSON cells\' routes (see the module doc)')
@@ -647,6 +761,9 @@ def main():
     if args.dates_ab:
         args.dates_ab = os.path.abspath(args.dates_ab)
         return dates_ab(args)
+    if args.tz_ab:
+        args.tz_ab = os.path.abspath(args.tz_ab)
+        return tz_ab(args)
     if args.sort_ab:
         args.sort_ab = os.path.abspath(args.sort_ab)
         return sort_ab(args)
