@@ -46,6 +46,7 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_comm_destroy',
            'kw_dedup_create', 'kw_dedup_run', 'kw_dedup_counts', 'kw_dedup_kept_size', 'kw_dedup_kept_copy',
            'kw_dedup_last_ms', 'kw_dedup_last_error', 'kw_dedup_destroy', 'dedup_urls',
+           'kw_dedup_geometry', 'kw_dedup_route_counts',
            'kw_cdx_begin', 'kw_cdx_append', 'kw_cdx_rows', 'kw_cdx_store_copy', 'kw_cdx_run', 'kw_cdx_csv_size',
            'kw_cdx_csv_copy', 'kw_cdx_last_ms', 'kw_cdx_tile_bytes',
            'kw_csv_append', 'kw_cdx_run_exclude', 'kw_cdx_exclude_codes', 'kw_cdx_exclude_counts',
@@ -125,8 +126,10 @@ def lib() -> ctypes.CDLL:
     L.kw_dedup_last_error.restype = ctypes.c_char_p
     L.kw_dedup_destroy.argtypes = [vp]
     L.dedup_urls.argtypes = [vp, vp, i64, vp, vp]
+    L.kw_dedup_geometry.argtypes = [vp, i32]
+    L.kw_dedup_route_counts.argtypes = [vp, vp, i32]
     for f in ('kw_dedup_create', 'kw_dedup_run', 'kw_dedup_counts', 'kw_dedup_kept_size', 'kw_dedup_kept_copy',
-              'kw_dedup_last_ms', 'kw_dedup_destroy', 'dedup_urls'):
+              'kw_dedup_last_ms', 'kw_dedup_destroy', 'dedup_urls', 'kw_dedup_geometry', 'kw_dedup_route_counts'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_cdx_begin.argtypes = [vp]
     L.kw_cdx_append.argtypes = [vp, vp, i64, ctypes.POINTER(CdxDialect), ctypes.POINTER(i64), ctypes.POINTER(i32),

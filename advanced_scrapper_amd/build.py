@@ -44,6 +44,7 @@ def build_kwmatch(force: bool = False) -> str:
 def _kw_sources():
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.hpp')))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwmatch.h'))
+    srcs.append(os.path.join(HERE, '..', 'include', 'kwdedup.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwrows.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwingest.h'))
     srcs.append(os.path.join(HERE, '..', 'include', 'kwsort.h'))

@@ -862,8 +862,8 @@ __device__ __forceinline__ uint64_t row_hash(const Scratch &S, const RowGen &g)
 // CODE_COLLIDE, which the host resolves exactly among those rows (every row of a URL other than the first
 // row's gets it, so their keep-first is complete).
 //
-// dd_pairs_kernel: 8 lanes a pair, lane s comparing words s, s + 8, ... of the two regenerated rows, so each load
-// instruction touches a few lines of 8 rows (lane = row made every load touch 64 rows' lines: 37.8 ms at 500M
+// dd_pairs_kernel: 4 lanes a pair (PAIR_LANES), lane s comparing words s, s + 4, ... of the two regenerated rows,
+// PAIR_UNROLL of them in flight per row, so each load instruction touches a few lines of 16 rows (lane = row made every load touch 64 rows' lines: 37.8 ms at 500M
 // rows, 123M pairs)
 #ifndef DD_PAIR_LANES
 #define DD_PAIR_LANES 4
@@ -961,9 +961,9 @@ struct NormRow {
 };
 __device__ __forceinline__ int64_t desc_start(uint4 r) { return (int64_t)(((uint64_t)(r.y & 0xFFu) << 32) | r.x); }
 
-// pairs e[0, m) (m <= 64, wave-uniform): lane t loads pair t's two descriptors, then 8 rounds of 8 pairs, lane s
-// of a pair's group comparing words s, s + 8, ... of the two regenerated rows (each load instruction touches a
-// few lines of 8 rows; the descriptors' dependent loads are paid once per 64 pairs)
+// pairs e[0, m) (m <= 64, wave-uniform): lane t loads pair t's two descriptors, then 4 rounds of 16 pairs, lane s
+// of a pair's group of 4 comparing words s, s + 4, ... of the two regenerated rows (each load instruction touches
+// a few lines of 16 rows; the descriptors' dependent loads are paid once per 64 pairs)
 __device__ __forceinline__ void compare_pairs(const uint8_t *__restrict__ arena, uint8_t *__restrict__ code,
                                               const Scratch &S, const uint2 *__restrict__ e, uint32_t m,
                                               uint32_t &n_dup)
@@ -1726,6 +1726,7 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
     h->n_kept = h->n_kept_bytes = 0;
     h->collide_first.clear();
     h->ex_serial = 0;
+    for (auto &r : h->route) r = 0;
     if (n == 0) return KW_OK;
     // ---- scratch (grown on demand)
     uint64_t tsize = 1024;
@@ -1808,7 +1809,7 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
         DDCHK(h, hipGetLastError());
     }
     DDCHK(h, hipEventRecord(h->ev[2], st));
-    // decide: the pairs compared (8 lanes a pair), then the later rows of the differing ones against the table
+    // decide: the pairs compared (4 lanes a pair), then the later rows of the differing ones against the table
     hipLaunchKernelGGL(dd_pairs_kernel, dim3((int)std::min<int64_t>((n_claims + 3) / 4, (int64_t)h->cus * h->pairs_bpc)),
                        dim3(BLOCK), 0, st, d_arena, d_code, S, n_claims, (uint64_t)ns2[0]);
     hipLaunchKernelGGL(dd_recheck_kernel, dim3(h->cus * 4), dim3(BLOCK), 0, st, d_arena, d_code, S);
@@ -1816,6 +1817,10 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
     unsigned long long cnt[10];
     DDCHK(h, hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
     DDCHK(h, hipStreamSynchronize(st));
+    h->route[0] = (int64_t)ns2[0];
+    h->route[1] = (int64_t)cnt[5];
+    h->route[2] = (int64_t)cnt[CODE_COLLIDE];
+    h->route[3] = (int64_t)cnt[9];
     if (S.stats)
         fprintf(stderr, "kw_dedup: table lookups: %llu differing pairs\n", cnt[5]);
     // per code (the CODE_COLLIDE rows are added by resolve_collisions); KEPT: the rest
@@ -1843,6 +1848,23 @@ extern "C" int kw_dedup_counts(kw_dedup *h, int64_t *counts)
     if (!h || !counts) return KW_EINVAL;
     if (!h->have_run) { h->err = "kw_dedup_counts: no run"; return KW_ESTATE; }
     for (int k = 0; k < 4; ++k) counts[k] = h->counts[k];
+    return KW_OK;
+}
+
+extern "C" int kw_dedup_geometry(int32_t *out, int32_t n)
+{
+    if (!out || n < 0) return KW_EINVAL;
+    const int32_t v[10] = {STAGE_BYTES, TCLAIM, SCAN_TILE, PAIR_LANES, PAIR_UNROLL,
+                           CPS_ROWS,    CPS_IN, CPS_OUT,   CP_STAGE,   (int32_t)COLLIDE_CAP};
+    for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+    return KW_OK;
+}
+
+extern "C" int kw_dedup_route_counts(kw_dedup *h, int64_t *out, int32_t n)
+{
+    if (!h || !out || n < 0) return KW_EINVAL;
+    if (!h->have_run) { h->err = "kw_dedup_route_counts: no run"; return KW_ESTATE; }
+    for (int i = 0; i < n && i < 4; ++i) out[i] = h->route[i];
     return KW_OK;
 }
 

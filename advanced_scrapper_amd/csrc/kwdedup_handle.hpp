@@ -69,6 +69,7 @@ struct kw_dedup {
     uint64_t table_slots = 0;
     uint32_t epoch = 0;
     int64_t counts[4] = {0, 0, 0, 0};
+    int64_t route[4] = {0, 0, 0, 0};   // the last run's slow rows, differing pairs, CODE_COLLIDE rows, rows listed
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool have_run = false;
     uint64_t run_serial = 0;       // kw_dedup_run calls so far (the renderer checks the kept rows are its run's)

@@ -52,6 +52,18 @@ int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *d_off, int6
 /* Row counts per code of the last run: counts[KW_URL_*] (4 values). */
 int kw_dedup_counts(kw_dedup *h, int64_t *counts);
 
+/* The kernels' compile-time geometry, for tests that aim at its edges (no handle, no device): out[0..10) =
+ * the transform's LDS stage (bytes a wave), the groups of 64 rows a wave claims at once, the rows of a scan tile,
+ * the lanes a compared pair takes, the words a lane has in flight per row, the kept rows of a copy task, the copy's
+ * input and output stages (bytes), the lane-per-row copy's stage (bytes), the rows the collision list holds;
+ * n <= 10 values. */
+int kw_dedup_geometry(int32_t *out, int32_t n);
+
+/* Routes of the last run: out[0] rows that took the byte-serial rewrite, [1] compared pairs that differed, [2] rows
+ * that shared a hash tag with a different URL (decided by the exact host pass), [3] such rows as the device listed
+ * them; n <= 4 values. */
+int kw_dedup_route_counts(kw_dedup *h, int64_t *out, int32_t n);
+
 /* Size of the last run's kept rows: their number and the bytes of their normalised URLs. */
 int kw_dedup_kept_size(kw_dedup *h, int64_t *n_kept, int64_t *n_bytes);
 

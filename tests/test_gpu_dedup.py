@@ -15,6 +15,7 @@ import pandas as pd
 import pytest
 
 from oracle import dedup_oracle as dd
+from tests.dedup_geometry import oracle_codes   # the KW_URL_* code of every row, from the oracle
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), 'golden', 'dedup_golden.json.gz')
@@ -153,12 +154,7 @@ def test_scale_determinism_and_sample_parity(gpu):
     c1 = gpu.run(d_a, d_o, u.n).cpu().numpy()
     c2 = gpu.run(d_a, d_o, u.n).cpu().numpy()
     assert np.array_equal(c1, c2)
-    urls = u.urls()
-    keys = [dd.url_transform(x) for x in urls]
-    kept = set(dd.keep_first(keys))
-    want = np.array([1 if i in kept else (0 if keys[i] is None and dd._HTML.search(urls[i]) is None
-                                          else (2 if keys[i] is None else 3)) for i in range(u.n)], dtype=np.uint8)
-    assert np.array_equal(c1, want)
+    assert np.array_equal(c1, oracle_codes(u.urls()))
 
 
 def test_table_epochs_across_runs(gpu):
@@ -171,11 +167,7 @@ def test_table_epochs_across_runs(gpu):
     b = synth.generate_urls(2000, seed=6)
     want = {}
     for k, u in (('a', a), ('b', b)):
-        urls = u.urls()
-        keys = [dd.url_transform(x) for x in urls]
-        kept = set(dd.keep_first(keys))
-        want[k] = np.array([1 if i in kept else (0 if keys[i] is None and dd._HTML.search(urls[i]) is None
-                                                 else (2 if keys[i] is None else 3)) for i in range(u.n)], np.uint8)
+        want[k] = oracle_codes(u.urls())
     dev = {k: gpu.upload(u.arena, u.off) + (u.n,) for k, u in (('a', a), ('b', b))}
     for r in range(300):
         k = 'a' if r < 280 or r % 2 else 'b'   # 280 runs on one table (through the wrap), then alternating
