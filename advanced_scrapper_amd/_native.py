@@ -62,7 +62,8 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_ingest_upload', 'kw_ingest_spans', 'kw_ingest_copy_spans',
            'kw_ingest_zone', 'kw_ingest_stamps', 'kw_ingest_stamps_device', 'kw_rows_emit_stamps_device',
            'kw_sort_create', 'kw_sort_destroy', 'kw_sort_last_error', 'kw_sort_last_ms', 'kw_sort_keys',
-           'kw_sort_gather')
+           'kw_sort_gather', 'kw_sort_begin', 'kw_sort_window', 'kw_sort_finish', 'kw_sort_gather_begin',
+           'kw_sort_gather_slab')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -209,8 +210,15 @@ def lib() -> ctypes.CDLL:
                                ctypes.POINTER(i32), ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.kw_sort_gather.argtypes = [vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
     L.kw_sort_last_ms.argtypes = [vp, vp, i32]
+    L.kw_sort_begin.argtypes = [vp, i32, i64, i64]
+    L.kw_sort_window.argtypes = [vp, vp, i64, vp]
+    L.kw_sort_finish.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                 ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.kw_sort_gather_begin.argtypes = [vp, vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.kw_sort_gather_slab.argtypes = [vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
     for f in ('kw_ingest_spans', 'kw_ingest_copy_spans', 'kw_sort_create', 'kw_sort_destroy', 'kw_sort_keys',
-              'kw_sort_gather', 'kw_sort_last_ms'):
+              'kw_sort_gather', 'kw_sort_last_ms', 'kw_sort_begin', 'kw_sort_window', 'kw_sort_finish',
+              'kw_sort_gather_begin', 'kw_sort_gather_slab'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_sort_last_error.argtypes = [vp]
     L.kw_sort_last_error.restype = ctypes.c_char_p

@@ -17,6 +17,14 @@
 //                     first and last byte, and only a lane that holds a record's end goes byte by byte.
 // kw_sort_keys synchronises once; kw_sort_gather twice (the body's size is known after the scan, and with it the
 // range check's result: nothing is copied for a bad order).
+//
+// A file of several windows (kw_sort_begin / kw_sort_window / kw_sort_finish): ks_rows_kernel takes a row base and
+// a text base, so a window's keys, offenders and witnesses land at the file's own row and block numbers and its
+// spans at the store's positions; ks_check_kernel takes a row range, so a window's first key is held against the
+// last key of the window before, and runs over the blocks once, at the end.  The state (Dev), the keys and the
+// witnesses stay on the device from window to window, in buffers that keep their contents when they grow.
+// kw_sort_gather_slab runs ks_copy_kernel over one slab's byte range of the scanned offsets; every position in
+// the store and in the output is 64-bit.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -90,7 +98,8 @@ __global__ __launch_bounds__(BLOCK) void ks_rows_kernel(const uint8_t *__restric
                                                         const long long *__restrict__ re, long long n, int ncols, int ti,
                                                         long long block_rows, long long *__restrict__ keys,
                                                         uint8_t *__restrict__ btext, uint8_t *__restrict__ bnonna,
-                                                        Dev *__restrict__ D)
+                                                        Dev *__restrict__ D, long long base, long long tbase,
+                                                        long long *__restrict__ srs, long long *__restrict__ sre)
 {
     const long long rounds = (n + BLOCK - 1) / BLOCK;   // (every lane of a wave makes the same trips)
     for (long long q = blockIdx.x; q < rounds; q += gridDim.x) {
@@ -101,20 +110,24 @@ __global__ __launch_bounds__(BLOCK) void ks_rows_kernel(const uint8_t *__restric
             long long key = 0;
             {
                 const long long c = c0 + ti, s = coff[c];
-                if ((cfl[c] & (F_NA | F_QUOTED)) || !parse_key(cells + s, coff[c + 1] - s, &key)) ek = (u64)r;
+                if ((cfl[c] & (F_NA | F_QUOTED)) || !parse_key(cells + s, coff[c + 1] - s, &key)) ek = (u64)(base + r);
             }
-            keys[r] = key;
-            const long long blk = (r / block_rows) * ncols;
+            keys[base + r] = key;
+            const long long blk = ((base + r) / block_rows) * ncols;
             for (int c = 0; c < ncols; ++c) {
                 const uint32_t fl = cfl[c0 + c];
                 if (ef == NONE && (!(fl & F_CANON) || ((fl & F_NA) && coff[c0 + c + 1] != coff[c0 + c])))
-                    ef = ((u64)r << COL_BITS) | (u64)c;
+                    ef = ((u64)(base + r) << COL_BITS) | (u64)c;
                 if (c != ti) {
                     if ((fl & F_TEXT) && !btext[blk + c]) btext[blk + c] = 1;
                     if (!(fl & F_NA) && !bnonna[blk + c]) bnonna[blk + c] = 1;
                 }
             }
             bytes = (u64)(re[r] - rs[r] + 1);
+            if (srs) {   // (a window: the record's span at its place in the store)
+                srs[base + r] = tbase + rs[r];
+                sre[base + r] = tbase + re[r];
+            }
         }
         if (__any((ek & ef) != NONE)) {   // (rare: one atomic a wave and condition)
             ek = wave_min(ek);
@@ -129,13 +142,13 @@ __global__ __launch_bounds__(BLOCK) void ks_rows_kernel(const uint8_t *__restric
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void ks_check_kernel(const long long *__restrict__ keys, long long n,
+__global__ __launch_bounds__(BLOCK) void ks_check_kernel(const long long *__restrict__ keys, long long r0, long long n,
                                                          const uint8_t *__restrict__ btext,
                                                          const uint8_t *__restrict__ bnonna, long long nbc, int ncols,
                                                          int ti, Dev *__restrict__ D)
 {
     const long long step = (long long)gridDim.x * BLOCK, t = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    for (long long r = t + 1; r < n; r += step)
+    for (long long r = r0 + t; r < n; r += step)   // (r0 >= 1: rows [r0, n) against the row before)
         if (keys[r] <= keys[r - 1] && !D->not_asc) D->not_asc = 1;
     for (long long i = t; i < nbc; i += step)
         if ((int)(i % ncols) != ti && !btext[i] && bnonna[i]) atomicMin(&D->first_dtype, (u64)i);
@@ -259,16 +272,22 @@ __global__ __launch_bounds__(BLOCK) void ks_copy_kernel(const uint8_t *__restric
                                                         const long long *__restrict__ rs,
                                                         const long long *__restrict__ order,
                                                         const u64 *__restrict__ doff, long long n,
-                                                        uint8_t *__restrict__ out, int iters)
+                                                        uint8_t *__restrict__ out, int iters, u64 x_lo, u64 x_hi)
 {
-    const u64 total = doff[n];
+    // the bytes [x_lo, total) of the body, total = min(x_hi, doff[n]), to out[0, total - x_lo): x_lo is a multiple
+    // of 1024, and x_hi is one or lies at doff[n] or beyond
+    const u64 total = x_hi < doff[n] ? x_hi : doff[n];
     const u64 wspan = (u64)iters << 10;
-    const u64 nspans = (total + wspan - 1) / wspan;
+    const u64 nspans = total > x_lo ? (total - x_lo + wspan - 1) / wspan : 0;
     const u64 wv = (u64)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (a scalar)
     const u64 lane16 = (u64)(threadIdx.x & 63) << 4;
+    out -= x_lo;                                  // (out + x: the place of the body's byte x)
     for (u64 sp = (u64)blockIdx.x * (BLOCK / 64) + wv; sp < nspans; sp += (u64)gridDim.x * (BLOCK / 64)) {
-        u64 w0 = sp * wspan;                      // the first byte of the wave's next KiB (wave-uniform, as all below)
-        const u64 send = w0 + wspan, wend = send < total ? send : total;
+        u64 w0 = x_lo + sp * wspan;               // the first byte of the wave's next KiB (wave-uniform, as all below)
+        // (a record may go on past a range's end: the whole KiBs stop at the range's end rounded up to a KiB, which
+        // is the end itself unless the body ends there, and then no record goes on)
+        const u64 tend = (total + 1023) & ~1023ull;
+        const u64 send = w0 + wspan < tend ? w0 + wspan : tend, wend = send < total ? send : total;
         long long lo = 0, hi = n;                 // the last record with doff[lo] <= w0
         while (hi - lo > 1) {
             const long long mid = (lo + hi) >> 1;
@@ -336,18 +355,32 @@ struct kw_sort {
     std::string err;
     ks::Dev *D = nullptr;          // device
     ks::Dev *H = nullptr;          // pinned host copy
-    ks::Buf keys, bflags, order, doff, tsum, out;
+    ks::Buf keys, btext, bnonna, order, doff, tsum, out;
     void *h_keys = nullptr, *h_out = nullptr;   // pinned
     size_t h_keys_cap = 0, h_out_cap = 0;
     hipEvent_t ev[9] = {};
     float ms[4] = {0, 0, 0, 0};
     float ms_keys_copy = 0;
-    // what the last taken kw_sort_keys saw (kw_sort_gather)
+    // what the last taken kw_sort_keys or kw_sort_finish saw (kw_sort_gather, kw_sort_gather_begin)
     bool have = false;
     const uint8_t *text = nullptr;
     const int64_t *rs = nullptr, *re = nullptr;
     long long n_rows = 0;
     hipStream_t stream = nullptr;
+    // a file of several windows (kw_sort_begin .. kw_sort_finish): the store of its body's text, its records'
+    // spans in the store, and what the windows so far have added
+    ks::Buf store, srs, sre;
+    bool open = false;
+    int time_col = 0, ncols = 0;
+    long long block_rows = 0, expect = 0, used = 0, rows = 0;
+    // the slabs of kw_sort_gather_begin: the last scan's shape, two device and two pinned host slabs in turn
+    bool scanned = false;
+    long long g_n = 0, slab_bytes = 0, n_slabs = 0, pre_k = -1;
+    unsigned long long g_total = 0;
+    int last_slot = 1;
+    ks::Buf slab[2];
+    void *h_slab[2] = {nullptr, nullptr};
+    size_t h_slab_cap[2] = {0, 0};
 };
 
 #define KSCHK(h, x)                                                                    \
@@ -374,6 +407,29 @@ static int ensure(kw_sort *h, Buf &b, size_t bytes)
     return KW_OK;
 }
 
+// a device buffer of at least `bytes` that keeps its first `keep` bytes when it grows (to twice the bytes asked
+// for: a file's windows ask for a little more each); what a grown buffer holds beyond them is zero
+static int ensure_keep(kw_sort *h, Buf &b, size_t bytes, size_t keep, hipStream_t st)
+{
+    if (b.cap >= bytes && b.p) return KW_OK;
+    const size_t want = 2 * bytes + 256;
+    void *p = nullptr;
+    KSCHK(h, hipMalloc(&p, want));
+    if (keep > b.cap) keep = b.cap;
+    hipError_t e = hipSuccess;
+    if (b.p && keep) e = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)p + keep, 0, want - keep, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        KSCHK(h, e);
+    }
+    if (b.p) (void)hipFree(b.p);
+    b.p = p;
+    b.cap = want;
+    return KW_OK;
+}
+
 static int ensure_pinned(kw_sort *h, void **p, size_t *cap, size_t bytes)
 {
     if (*cap >= bytes && *p) return KW_OK;
@@ -396,6 +452,17 @@ static int grid_cap()
         if (end != e && *end == '\0' && g >= 1 && g <= MAX_GRID) return (int)g;
     }
     return MAX_GRID;
+}
+
+// The most bytes a store may hold: the tests' KW_TEST_SORT_STORE_MAX (through kw_env), else no cap of its own.
+static long long store_cap()
+{
+    if (const char *e = kw_env("KW_TEST_SORT_STORE_MAX")) {
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        if (end != e && *end == '\0' && v >= 0) return v;
+    }
+    return INT64_MAX;
 }
 
 static dim3 grid_for(long long items, int cap)
@@ -433,9 +500,12 @@ extern "C" int kw_sort_destroy(kw_sort *h)
 {
     if (!h) return KW_OK;
     (void)hipSetDevice(h->device);
-    Buf *bufs[] = {&h->keys, &h->bflags, &h->order, &h->doff, &h->tsum, &h->out};
+    Buf *bufs[] = {&h->keys,  &h->btext, &h->bnonna, &h->order,   &h->doff,   &h->tsum,
+                   &h->out,   &h->store, &h->srs,    &h->sre,     &h->slab[0], &h->slab[1]};
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
+    for (void *p : h->h_slab)
+        if (p) (void)hipHostFree(p);
     if (h->D) (void)hipFree(h->D);
     if (h->H) (void)hipHostFree(h->H);
     if (h->h_keys) (void)hipHostFree(h->h_keys);
@@ -448,12 +518,61 @@ extern "C" int kw_sort_destroy(kw_sort *h)
 
 extern "C" const char *kw_sort_last_error(kw_sort *h) { return h ? h->err.c_str() : "null handle"; }
 
+// the device's state as a file starts: no offender, no bytes
+static int reset_state(kw_sort *h, hipStream_t st)
+{
+    Dev init;
+    memset(&init, 0, sizeof(init));
+    init.first_key = init.first_form = init.first_dtype = NONE;
+    *h->H = init;   // (pinned: the copy below reads it in stream order; the last call's copy back has finished)
+    KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
+    return KW_OK;
+}
+
+// after ev[1]: the n keys and the state to the host; the copies' time to ms_keys_copy
+static int fetch_state(kw_sort *h, long long n, hipStream_t st)
+{
+    KSCHK(h, hipMemcpyAsync(h->h_keys, h->keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipEventRecord(h->ev[2], st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    KSCHK(h, hipEventElapsedTime(&h->ms_keys_copy, h->ev[1], h->ev[2]));
+    return KW_OK;
+}
+
+// the verdict of the fetched state: the first of KEY, FORM, DTYPE with an offender; true: KW_SORT_OK
+static bool report(kw_sort *h, int32_t time_col, int32_t ncols, int64_t block_rows, const int64_t **keys,
+                   int64_t *body_bytes, int32_t *verdict, int64_t *bad_row, int32_t *bad_col, int32_t *ascending)
+{
+    const Dev &R = *h->H;
+    if (R.first_key != NONE) {
+        *verdict = KW_SORT_KEY;
+        *bad_row = (int64_t)R.first_key;
+        *bad_col = time_col;
+    } else if (R.first_form != NONE) {
+        *verdict = KW_SORT_FORM;
+        *bad_row = (int64_t)(R.first_form >> COL_BITS);
+        *bad_col = (int32_t)(R.first_form & ((1u << COL_BITS) - 1u));
+    } else if (R.first_dtype != NONE) {
+        *verdict = KW_SORT_DTYPE;
+        *bad_row = (int64_t)(R.first_dtype / (u64)ncols) * block_rows;
+        *bad_col = (int32_t)(R.first_dtype % (u64)ncols);
+    } else {
+        *keys = (const int64_t *)h->h_keys;
+        *body_bytes = (int64_t)R.body_bytes;
+        *ascending = R.not_asc ? 0 : 1;
+        return true;
+    }
+    return false;
+}
+
 extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t block_rows, const int64_t **keys,
                             int64_t *n_rows, int64_t *body_bytes, int32_t *verdict, int64_t *bad_row, int32_t *bad_col,
                             int32_t *ascending, void *stream)
 {
     if (!h) return KW_EINVAL;
-    h->have = false;
+    h->have = h->scanned = h->open = false;
     if (!ig || !keys || !n_rows || !body_bytes || !verdict || !bad_row || !bad_col || !ascending || block_rows < 1) {
         h->err = "kw_sort_keys: bad arguments";
         return KW_EINVAL;
@@ -480,51 +599,28 @@ extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t
     }
     const long long nblk = (n + block_rows - 1) / block_rows, nbc = nblk * ncols;
     int rc;
-    if ((rc = ensure(h, h->keys, (size_t)n * 8)) || (rc = ensure(h, h->bflags, (size_t)nbc * 2)) ||
-        (rc = ensure_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8)))
+    if ((rc = ensure(h, h->keys, (size_t)n * 8)) || (rc = ensure(h, h->btext, (size_t)nbc)) ||
+        (rc = ensure(h, h->bnonna, (size_t)nbc)) || (rc = ensure_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8)))
         return rc;
-    uint8_t *btext = (uint8_t *)h->bflags.p, *bnonna = btext + nbc;
-    Dev init;
-    memset(&init, 0, sizeof(init));
-    init.first_key = init.first_form = init.first_dtype = NONE;
-    *h->H = init;   // (pinned: the copy below reads it in stream order; the last call's copy back has finished)
+    uint8_t *btext = (uint8_t *)h->btext.p, *bnonna = (uint8_t *)h->bnonna.p;
     const int gcap = grid_cap();
-    KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
-    KSCHK(h, hipMemsetAsync(btext, 0, (size_t)nbc * 2, st));
+    if ((rc = reset_state(h, st))) return rc;
+    KSCHK(h, hipMemsetAsync(btext, 0, (size_t)nbc, st));
+    KSCHK(h, hipMemsetAsync(bnonna, 0, (size_t)nbc, st));
     hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
                        (const long long *)rs, (const long long *)re, (long long)n, (int)ncols, (int)time_col,
-                       (long long)block_rows, (long long *)h->keys.p, btext, bnonna, h->D);
+                       (long long)block_rows, (long long *)h->keys.p, btext, bnonna, h->D, 0ll, 0ll,
+                       (long long *)nullptr, (long long *)nullptr);
     hipLaunchKernelGGL(ks_check_kernel, grid_for(n > nbc ? n : nbc, gcap), dim3(BLOCK), 0, st,
-                       (const long long *)h->keys.p, (long long)n, (const uint8_t *)btext, (const uint8_t *)bnonna, nbc,
-                       (int)ncols, (int)time_col, h->D);
+                       (const long long *)h->keys.p, 1ll, (long long)n, (const uint8_t *)btext, (const uint8_t *)bnonna,
+                       nbc, (int)ncols, (int)time_col, h->D);
     KSCHK(h, hipEventRecord(h->ev[1], st));
-    KSCHK(h, hipMemcpyAsync(h->h_keys, h->keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipEventRecord(h->ev[2], st));
-    KSCHK(h, hipStreamSynchronize(st));
-    KSCHK(h, hipGetLastError());
+    if ((rc = fetch_state(h, n, st))) return rc;
     KSCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[0], h->ev[1]));
-    KSCHK(h, hipEventElapsedTime(&h->ms_keys_copy, h->ev[1], h->ev[2]));
     h->ms[1] = h->ms[2] = 0;
     h->ms[3] = h->ms_keys_copy;
     *n_rows = n;
-    const Dev &R = *h->H;
-    if (R.first_key != NONE) {
-        *verdict = KW_SORT_KEY;
-        *bad_row = (int64_t)R.first_key;
-        *bad_col = time_col;
-    } else if (R.first_form != NONE) {
-        *verdict = KW_SORT_FORM;
-        *bad_row = (int64_t)(R.first_form >> COL_BITS);
-        *bad_col = (int32_t)(R.first_form & ((1u << COL_BITS) - 1u));
-    } else if (R.first_dtype != NONE) {
-        *verdict = KW_SORT_DTYPE;
-        *bad_row = (int64_t)(R.first_dtype / (u64)ncols) * block_rows;
-        *bad_col = (int32_t)(R.first_dtype % (u64)ncols);
-    } else {
-        *keys = (const int64_t *)h->h_keys;
-        *body_bytes = (int64_t)R.body_bytes;
-        *ascending = R.not_asc ? 0 : 1;
+    if (report(h, time_col, ncols, block_rows, keys, body_bytes, verdict, bad_row, bad_col, ascending)) {
         h->have = true;
         h->text = text;
         h->rs = rs;
@@ -535,21 +631,180 @@ extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t
     return KW_OK;
 }
 
-extern "C" int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const uint8_t **out, int64_t *out_bytes)
+// ------------------------------------------------------------------ a file of several windows
+extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, int64_t expect_bytes)
 {
     if (!h) return KW_EINVAL;
-    if (!h->have) {
-        h->err = "kw_sort_gather: no kw_sort_keys that was taken";
-        return KW_ESTATE;
-    }
-    if (!order || !out || !out_bytes || n < 1 || n > h->n_rows) {
-        h->err = "kw_sort_gather: bad arguments";
+    h->have = h->scanned = h->open = false;
+    if (time_col < 0 || block_rows < 1 || expect_bytes < 1) {
+        h->err = "kw_sort_begin: bad arguments";
         return KW_EINVAL;
     }
-    *out = nullptr;
-    *out_bytes = 0;
+    KSCHK(h, hipSetDevice(h->device));
+    if (expect_bytes > store_cap()) {
+        h->err = "kw_sort_begin: a store of " + std::to_string(expect_bytes) + " bytes is over the cap";
+        return KW_EOVERFLOW;
+    }
+    const size_t want = (size_t)expect_bytes + 64;   // (a lane's 16-byte load may read past a record's end)
+    if (h->store.cap < want) {
+        // the store itself, and a quarter of it again for what is kept per row -- the key, the span, the order entry
+        // and its offset, 40 bytes, at the 160 bytes and more of a per-ticker file's record -- and a margin for
+        // the slabs; a store that is replaced gives its own bytes back first
+        size_t free_b = 0, total_b = 0;
+        KSCHK(h, hipMemGetInfo(&free_b, &total_b));
+        const size_t need = want + want / 4 + ((size_t)64 << 20);
+        if (need > free_b + h->store.cap) {
+            h->err = "kw_sort_begin: a store of " + std::to_string(expect_bytes) + " bytes does not fit in the " +
+                     std::to_string(free_b) + " free bytes of the device";
+            return KW_EOVERFLOW;
+        }
+        if (h->store.p) (void)hipFree(h->store.p);
+        h->store.p = nullptr;
+        h->store.cap = 0;
+        if (hipMalloc(&h->store.p, want) != hipSuccess) {
+            (void)hipGetLastError();
+            h->store.p = nullptr;
+            h->err = "kw_sort_begin: no device memory for a store of " + std::to_string(expect_bytes) + " bytes";
+            return KW_EOVERFLOW;
+        }
+        h->store.cap = want;
+    }
+    h->time_col = time_col;
+    h->block_rows = block_rows;
+    h->expect = expect_bytes;
+    h->used = h->rows = 0;
+    h->ncols = 0;
+    h->ms[0] = h->ms[1] = h->ms[2] = h->ms[3] = h->ms_keys_copy = 0;
+    int rc;
+    if ((rc = reset_state(h, nullptr))) return rc;
+    KSCHK(h, hipStreamSynchronize(nullptr));
+    h->open = true;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_window(kw_sort *h, kw_ingest *ig, int64_t consumed, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->open) {
+        h->err = "kw_sort_window: no kw_sort_begin";
+        return KW_ESTATE;
+    }
+    h->open = false;   // (an error below ends the file)
+    hipStream_t st = (hipStream_t)stream;
+    KSCHK(h, hipSetDevice(h->device));
+    const int64_t *rs, *re, *coff;
+    const uint8_t *text, *cells, *cfl;
+    int64_t n, n_bytes, cell_bytes;
+    int32_t ncols;
+    if (!ig || kw_ingest_spans(ig, &rs, &re, &n, &ncols, &text, &n_bytes) != KW_OK ||
+        kw_ingest_cells(ig, &cells, &coff, &cfl, &cell_bytes) != KW_OK) {
+        h->err = std::string("kw_sort_window: ") + (ig ? kw_ingest_last_error(ig) : "no ingest handle");
+        return KW_ESTATE;
+    }
+    if (n < 1 || consumed < 1 || consumed > n_bytes || h->time_col >= ncols || (h->ncols && h->ncols != ncols)) {
+        h->err = "kw_sort_window: no rows, bytes outside the text, or another shape than the file's first window";
+        return KW_EINVAL;
+    }
+    if (consumed > h->expect - h->used) {
+        h->err = "kw_sort_window: the store holds " + std::to_string(h->used) + " of " + std::to_string(h->expect) +
+                 " bytes, the window has " + std::to_string(consumed);
+        return KW_EOVERFLOW;
+    }
+    h->ncols = ncols;
+    const long long base = h->rows, rows = base + n;
+    const long long nbc = ((rows + h->block_rows - 1) / h->block_rows) * ncols;
+    const long long nbc0 = ((base + h->block_rows - 1) / h->block_rows) * ncols;
+    int rc;
+    if ((rc = ensure_keep(h, h->keys, (size_t)rows * 8, (size_t)base * 8, st)) ||
+        (rc = ensure_keep(h, h->srs, (size_t)rows * 8, (size_t)base * 8, st)) ||
+        (rc = ensure_keep(h, h->sre, (size_t)rows * 8, (size_t)base * 8, st)) ||
+        (rc = ensure_keep(h, h->btext, (size_t)nbc, (size_t)nbc0, st)) ||
+        (rc = ensure_keep(h, h->bnonna, (size_t)nbc, (size_t)nbc0, st)))
+        return rc;
+    uint8_t *btext = (uint8_t *)h->btext.p, *bnonna = (uint8_t *)h->bnonna.p;
+    const int gcap = grid_cap();
+    KSCHK(h, hipEventRecord(h->ev[0], st));
+    // (the witnesses of the blocks this window opens: a buffer that did not grow holds an earlier file's)
+    if (nbc > nbc0) {
+        KSCHK(h, hipMemsetAsync(btext + nbc0, 0, (size_t)(nbc - nbc0), st));
+        KSCHK(h, hipMemsetAsync(bnonna + nbc0, 0, (size_t)(nbc - nbc0), st));
+    }
+    hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
+                       (const long long *)rs, (const long long *)re, (long long)n, (int)ncols, h->time_col, h->block_rows,
+                       (long long *)h->keys.p, btext, bnonna, h->D, base, h->used, (long long *)h->srs.p,
+                       (long long *)h->sre.p);
+    // (the first row of a later window against the last row of the window before)
+    hipLaunchKernelGGL(ks_check_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, (const long long *)h->keys.p,
+                       base > 0 ? base : 1ll, rows, (const uint8_t *)btext, (const uint8_t *)bnonna, 0ll, (int)ncols,
+                       h->time_col, h->D);
+    KSCHK(h, hipEventRecord(h->ev[1], st));
+    KSCHK(h, hipMemcpyAsync((uint8_t *)h->store.p + h->used, text, (size_t)consumed, hipMemcpyDeviceToDevice, st));
+    KSCHK(h, hipEventRecord(h->ev[2], st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    float a = 0, b = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    KSCHK(h, hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    h->ms[0] += a;
+    h->ms[3] += b;
+    h->ms_keys_copy = h->ms[3];
+    h->used += consumed;
+    h->rows = rows;
+    h->stream = st;
+    h->open = true;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_finish(kw_sort *h, const int64_t **keys, int64_t *n_rows, int64_t *body_bytes, int32_t *verdict,
+                              int64_t *bad_row, int32_t *bad_col, int32_t *ascending)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->open || h->rows < 1) {
+        h->err = "kw_sort_finish: no kw_sort_begin, or no window since";
+        h->open = false;
+        return KW_ESTATE;
+    }
+    h->open = false;
+    if (!keys || !n_rows || !body_bytes || !verdict || !bad_row || !bad_col || !ascending) {
+        h->err = "kw_sort_finish: bad arguments";
+        return KW_EINVAL;
+    }
+    *keys = nullptr;
+    *n_rows = *body_bytes = *bad_row = 0;
+    *verdict = KW_SORT_OK;
+    *bad_col = *ascending = 0;
     hipStream_t st = h->stream;
     KSCHK(h, hipSetDevice(h->device));
+    const long long n = h->rows, nbc = ((n + h->block_rows - 1) / h->block_rows) * h->ncols;
+    int rc;
+    if ((rc = ensure_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8))) return rc;
+    KSCHK(h, hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(ks_check_kernel, grid_for(nbc, grid_cap()), dim3(BLOCK), 0, st, (const long long *)h->keys.p, 1ll,
+                       0ll, (const uint8_t *)h->btext.p, (const uint8_t *)h->bnonna.p, nbc, h->ncols, h->time_col, h->D);
+    KSCHK(h, hipEventRecord(h->ev[1], st));
+    const float copies = h->ms[3];
+    if ((rc = fetch_state(h, n, st))) return rc;
+    float a = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    h->ms[0] += a;
+    h->ms[3] = h->ms_keys_copy = copies + h->ms_keys_copy;
+    *n_rows = n;
+    if (report(h, h->time_col, h->ncols, h->block_rows, keys, body_bytes, verdict, bad_row, bad_col, ascending)) {
+        h->have = true;
+        h->text = (const uint8_t *)h->store.p;
+        h->rs = (const int64_t *)h->srs.p;
+        h->re = (const int64_t *)h->sre.p;
+        h->n_rows = n;
+    }
+    return KW_OK;
+}
+
+// The order's range check, the records' lengths and their scan (ev[3] .. ev[5]); synchronises.  *total: the
+// body's bytes; KW_EINVAL for an entry outside [0, n_rows).
+static int gather_scan(kw_sort *h, const int64_t *order, int64_t n, u64 *total)
+{
+    hipStream_t st = h->stream;
+    h->scanned = false;
     int rc;
     const long long ntiles = (n + BLOCK - 1) / BLOCK;
     if ((rc = ensure(h, h->order, (size_t)n * 8)) || (rc = ensure(h, h->doff, (size_t)(n + 1) * 8)) ||
@@ -576,36 +831,154 @@ extern "C" int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const
         h->err = "kw_sort_gather: an order entry outside [0, n_rows)";
         return KW_EINVAL;
     }
-    const u64 total = h->H->total;
+    *total = h->H->total;
+    float a = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->ev[3], h->ev[4]));
+    KSCHK(h, hipEventElapsedTime(&h->ms[1], h->ev[4], h->ev[5]));
+    h->ms[2] = 0;
+    h->ms[3] = h->ms_keys_copy + a;
+    return KW_OK;
+}
+
+// The body's bytes [x_lo, x_hi) (x_lo a multiple of 1024, x_hi one or the body's size) to d_out, then to h_out, on
+// the stream: ev[6] .. ev[8].  No synchronisation.
+static int gather_range(kw_sort *h, long long n, u64 x_lo, u64 x_hi, void *d_out, void *h_out)
+{
+    hipStream_t st = h->stream;
+    const int gcap = grid_cap();
+    KSCHK(h, hipEventRecord(h->ev[6], st));
+    // the KiB a wave lays out: one while the range gives every wave of a full grid something to do, up to 16 beyond
+    const long long kib = (long long)((x_hi - x_lo + 1023) >> 10), waves = (long long)gcap * (BLOCK / 64);
+    long long iters = (kib + waves - 1) / waves;
+    iters = iters < 1 ? 1 : (iters > 16 ? 16 : iters);
+    const long long spans = (kib + iters - 1) / iters;
+    hipLaunchKernelGGL(ks_copy_kernel, grid_for(spans * 64, gcap), dim3(BLOCK), 0, st, h->text,
+                       (const long long *)h->rs, (const long long *)h->order.p, (const u64 *)h->doff.p, n,
+                       (uint8_t *)d_out, (int)iters, x_lo, x_hi);
+    KSCHK(h, hipEventRecord(h->ev[7], st));
+    KSCHK(h, hipMemcpyAsync(h_out, d_out, (size_t)(x_hi - x_lo), hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipEventRecord(h->ev[8], st));
+    return KW_OK;
+}
+
+// after the stream that ran gather_range was synchronised: its times onto ms[2] (gather) and ms[3] (copies)
+static int gather_times(kw_sort *h)
+{
+    float a = 0, b = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->ev[6], h->ev[7]));
+    KSCHK(h, hipEventElapsedTime(&b, h->ev[7], h->ev[8]));
+    h->ms[2] += a;
+    h->ms[3] += b;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const uint8_t **out, int64_t *out_bytes)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->have) {
+        h->err = "kw_sort_gather: no kw_sort_keys or kw_sort_finish that was taken";
+        return KW_ESTATE;
+    }
+    if (!order || !out || !out_bytes || n < 1 || n > h->n_rows) {
+        h->err = "kw_sort_gather: bad arguments";
+        return KW_EINVAL;
+    }
+    *out = nullptr;
+    *out_bytes = 0;
+    KSCHK(h, hipSetDevice(h->device));
+    u64 total = 0;
+    int rc;
+    if ((rc = gather_scan(h, order, n, &total))) return rc;
     if (total >= 1ull << 31) {
         h->err = "kw_sort_gather: the body holds " + std::to_string(total) + " bytes";
         return KW_EOVERFLOW;
     }
     if ((rc = ensure(h, h->out, (size_t)total + 32)) ||
-        (rc = ensure_pinned(h, &h->h_out, &h->h_out_cap, (size_t)total + 16)))
+        (rc = ensure_pinned(h, &h->h_out, &h->h_out_cap, (size_t)total + 16)) ||
+        (rc = gather_range(h, n, 0, total, h->out.p, h->h_out)))
         return rc;
-    KSCHK(h, hipEventRecord(h->ev[6], st));
-    // the KiB a wave lays out: one while the body gives every wave of a full grid something to do, up to 16 beyond
-    const long long kib = (long long)((total + 1023) >> 10), waves = (long long)gcap * (BLOCK / 64);
-    long long iters = (kib + waves - 1) / waves;
-    iters = iters < 1 ? 1 : (iters > 16 ? 16 : iters);
-    const long long spans = (kib + iters - 1) / iters;
-    hipLaunchKernelGGL(ks_copy_kernel, grid_for(spans * 64, gcap), dim3(BLOCK), 0, st, h->text,
-                       (const long long *)h->rs, (const long long *)h->order.p, (const u64 *)h->doff.p, (long long)n,
-                       (uint8_t *)h->out.p, (int)iters);
-    KSCHK(h, hipEventRecord(h->ev[7], st));
-    KSCHK(h, hipMemcpyAsync(h->h_out, h->out.p, (size_t)total, hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipEventRecord(h->ev[8], st));
-    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipStreamSynchronize(h->stream));
     KSCHK(h, hipGetLastError());
-    float a = 0, b = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->ev[3], h->ev[4]));
-    KSCHK(h, hipEventElapsedTime(&h->ms[1], h->ev[4], h->ev[5]));
-    KSCHK(h, hipEventElapsedTime(&h->ms[2], h->ev[6], h->ev[7]));
-    KSCHK(h, hipEventElapsedTime(&b, h->ev[7], h->ev[8]));
-    h->ms[3] = h->ms_keys_copy + a + b;
+    if ((rc = gather_times(h))) return rc;
     *out = (const uint8_t *)h->h_out;
     *out_bytes = (int64_t)total;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_gather_begin(kw_sort *h, const int64_t *order, int64_t n, int64_t slab_bytes,
+                                    int64_t *total_bytes, int64_t *n_slabs)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->have) {
+        h->err = "kw_sort_gather_begin: no kw_sort_keys or kw_sort_finish that was taken";
+        return KW_ESTATE;
+    }
+    h->scanned = false;
+    if (!order || !total_bytes || !n_slabs || n < 1 || n > h->n_rows || slab_bytes < 1024 || slab_bytes % 1024 ||
+        slab_bytes >= 1ll << 31) {
+        h->err = "kw_sort_gather_begin: bad arguments";
+        return KW_EINVAL;
+    }
+    *total_bytes = *n_slabs = 0;
+    KSCHK(h, hipSetDevice(h->device));
+    u64 total = 0;
+    int rc;
+    if ((rc = gather_scan(h, order, n, &total))) return rc;
+    for (int s = 0; s < 2; ++s)
+        if ((rc = ensure(h, h->slab[s], (size_t)slab_bytes + 32)) ||
+            (rc = ensure_pinned(h, &h->h_slab[s], &h->h_slab_cap[s], (size_t)slab_bytes)))
+            return rc;
+    h->g_n = n;
+    h->g_total = total;
+    h->slab_bytes = slab_bytes;
+    h->n_slabs = (long long)((total + (u64)slab_bytes - 1) / (u64)slab_bytes);
+    h->pre_k = -1;
+    h->last_slot = 1;
+    h->scanned = true;
+    *total_bytes = (int64_t)total;
+    *n_slabs = h->n_slabs;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_gather_slab(kw_sort *h, int64_t k, const uint8_t **out, int64_t *out_bytes)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->have || !h->scanned) {
+        h->err = "kw_sort_gather_slab: no kw_sort_gather_begin that succeeded";
+        return KW_ESTATE;
+    }
+    if (!out || !out_bytes || k < 0 || k >= h->n_slabs) {
+        h->err = "kw_sort_gather_slab: bad arguments";
+        return KW_EINVAL;
+    }
+    *out = nullptr;
+    *out_bytes = 0;
+    KSCHK(h, hipSetDevice(h->device));
+    const u64 sb = (u64)h->slab_bytes;
+    auto hi_of = [&](long long j) { return (u64)(j + 1) * sb < h->g_total ? (u64)(j + 1) * sb : h->g_total; };
+    int rc;
+    // the slab this call asks for: laid out ahead by the call before, or now, into the slab the caller gave up
+    const int slot = 1 - h->last_slot;
+    if (h->pre_k != k) {
+        if (h->pre_k >= 0) {   // (another one is under way into this slab)
+            KSCHK(h, hipStreamSynchronize(h->stream));
+            if ((rc = gather_times(h))) return rc;
+        }
+        if ((rc = gather_range(h, h->g_n, (u64)k * sb, hi_of(k), h->slab[slot].p, h->h_slab[slot]))) return rc;
+    }
+    h->pre_k = -1;
+    KSCHK(h, hipStreamSynchronize(h->stream));
+    KSCHK(h, hipGetLastError());
+    if ((rc = gather_times(h))) return rc;
+    *out = (const uint8_t *)h->h_slab[slot];
+    *out_bytes = (int64_t)(hi_of(k) - (u64)k * sb);
+    h->last_slot = slot;
+    // the next slab, into the other one, while the caller writes this one out
+    if (k + 1 < h->n_slabs) {
+        if ((rc = gather_range(h, h->g_n, (u64)(k + 1) * sb, hi_of(k + 1), h->slab[1 - slot].p, h->h_slab[1 - slot])))
+            return rc;
+        h->pre_k = k + 1;
+    }
     return KW_OK;
 }
 

@@ -8,9 +8,17 @@ makes pandas' own ``np.argsort(keys, kind='quicksort')`` call (ties keep pandas'
 lays the records out in that order.  No cell is rendered on this route: every other file is refused, untouched,
 and stays with ``match_keywords._sort_native`` and pandas.
 
+A body of ``ingest.MAX_WINDOW`` bytes or more does not fit one parse.  It is read in windows through the ingest
+handle's two pinned slots (:func:`read_windows`), each window parsed and handed to ``kw_sort_window``, which
+gathers the text in a store in device memory; ``kw_sort_finish`` gives the whole file's keys and verdict, and
+``kw_sort_gather_slab`` the output slab by slab, written into a sibling temporary file that takes the target's
+place after the last slab.  Only a single record that no window holds (``'size'``) and a body that the device's
+free memory does not hold (``'memory'``) are refused for their size.
+
 ``LAST_STATS`` counts the files by route (``device``: rewritten here, ``unchanged``: found in order here,
 ``native`` and ``pandas``: the host routes, noted by ``match_keywords.sort_matched_csv``), the refusals by
-reason, the bytes the device route took and its summed device times.
+reason, the bytes the device route took, its summed device times, and the ``windows`` and ``slabs`` of the
+files that went in pieces.
 """
 from __future__ import annotations
 
@@ -30,9 +38,14 @@ INGEST_VERDICTS = ('OK', 'NUL', 'UTF8', 'QUOTE', 'CR', 'BLANK', 'FIELDS', 'ROWS'
 SORT_VERDICTS = ('OK', 'KEY', 'FORM', 'DTYPE')
 
 
+WINDOW_BYTES = 256 << 20           # a large file's body goes to the device in windows of this size ...
+SLAB_BYTES = 64 << 20              # ... and comes back in slabs of this one (a multiple of 1024)
+HEADROOM = 1 << 20                 # the bytes kept free before a window that is read ahead, for the last one's tail
+
+
 def _new_stats() -> dict:
     return {'device': 0, 'unchanged': 0, 'native': 0, 'pandas': 0, 'refused': {}, 'bytes': 0, 'gather_bytes': 0,
-            'prefetched': 0,
+            'prefetched': 0, 'windows': 0, 'slabs': 0,
             'ms': {'parse': 0.0, 'keys': 0.0, 'scan': 0.0, 'gather': 0.0, 'copies': 0.0},
             'wall_s': {'read': 0.0, 'device': 0.0, 'argsort': 0.0, 'write': 0.0}, 'last': None}
 
@@ -57,11 +70,95 @@ def sort_on_device() -> bool:
     return os.environ.get('KW_SORT_DEVICE', SORT_DEVICE_DEFAULT) != '0'
 
 
+class Refusal(Exception):
+    """A file the windowed route leaves to the host routes: ``reason`` as ``LAST_STATS['refused']`` counts it."""
+
+    def __init__(self, reason: str, keep_last: bool = False):
+        super().__init__(reason)
+        self.reason, self.keep_last = reason, keep_last
+
+
+class _Done:
+    """The future of a call that ran at once."""
+
+    def __init__(self, value):
+        self._value = value
+
+    def result(self):
+        return self._value
+
+
+def read_windows(nbody: int, window_bytes: int, fill, move, parse, submit=None,
+                 max_window: int = ingest.MAX_WINDOW) -> int:
+    """A body of ``nbody`` bytes through two staging slots, window by window; the windows that gave rows.
+
+    ``fill(slot, at, lo, n)``: the body's bytes [lo, lo + n) into the slot's bytes [at, at + n).
+    ``move(src, src_at, dst, dst_at, n)``: n bytes from one slot to the other.
+    ``parse(slot, at, n, final, start) -> (n_rows, consumed)``: the window that stands in the slot's bytes
+    [at, at + n) is the body's [start, start + n); ``final``: it ends the body.  ``n_rows == 0`` of a window that
+    is not final: it holds no complete record.
+    ``submit(fn, *args)`` runs ``fill`` on the reader thread and returns its future (None: at once).
+
+    Every window starts where the last one's consumed bytes end, so at a record start.  While a window is with
+    ``parse`` the body's next ``window_bytes`` are read ahead into the other slot, behind ``HEADROOM`` free bytes:
+    the unconsumed tail is moved in front of them and opens the next window.  A tail that is longer, and a window
+    without a complete record, read the next window again from its start, the latter at twice the size; a window
+    of ``max_window`` bytes that still holds no record raises ``Refusal('size')``."""
+    run = submit if submit is not None else (lambda fn, *a: _Done(fn(*a)))
+    head = min(window_bytes, HEADROOM)
+    pos, slot, at, n = 0, 0, head, min(window_bytes, nbody)
+    fill(slot, at, 0, n)
+    ahead = None               # (future, bytes) of the body's bytes after this window, on their way to the other slot
+    taken = 0
+
+    def settle():
+        nonlocal ahead
+        if ahead is not None:
+            ahead[0].result()
+        ahead = None
+
+    try:
+        while True:
+            end = pos + n
+            final = end == nbody
+            if not final and ahead is None:
+                m = min(window_bytes, nbody - end)
+                ahead = (run(fill, 1 - slot, head, end, m), m)
+            n_rows, consumed = parse(slot, at, n, final, pos)
+            if n_rows == 0 and not final:
+                if n >= max_window:
+                    raise Refusal('size')          # a single record that no window holds
+                settle()
+                slot, at, n = 1 - slot, 0, min(2 * n, max_window, nbody - pos)
+                fill(slot, at, pos, n)
+                continue
+            taken += n_rows > 0
+            pos += consumed
+            if final:
+                return taken
+            tail = end - pos
+            if ahead is not None and tail <= head:
+                m = ahead[1]
+                settle()
+                move(slot, at + consumed, 1 - slot, head - tail, tail)
+                slot, at, n = 1 - slot, head - tail, tail + m
+            else:
+                settle()
+                slot, at, n = 1 - slot, 0, min(max(window_bytes, tail), nbody - pos)
+                fill(slot, at, pos, n)
+    finally:
+        try:
+            settle()
+        except Exception:   # noqa: BLE001 - the reader is leaving
+            pass
+
+
 class _Job:
     """One file on its way to the device: the header's decisions, the staging slot its body is read into."""
 
     def __init__(self, path):
         self.path = path
+        self.windowed = False          # a body of large_from bytes or more: window by window (DeviceSorter._windowed)
         self.refusal: Optional[str] = None
         self.future = None
         self.dev = self.view = self.names = None
@@ -85,10 +182,20 @@ class _Job:
 class DeviceSorter:
     """One ``kw_sort`` handle and the ``DeviceIngest`` handles (keyed by the header's shape) of one device and
     host thread.  ``sort_file(path, next_path)`` sorts a file; with ``next_path`` the next file's body is read
-    into the other staging slot by a background thread while this one is on the device."""
+    into the other staging slot by a background thread while this one is on the device.
 
-    def __init__(self, device: int = 0):
+    A body of ``large_from`` bytes or more that does not fit one window of ``window_bytes`` goes to the device window
+    by window and comes back in slabs of ``slab_bytes`` (:meth:`_windowed`): pinned host memory stays at two windows
+    and two slabs whatever the file's size."""
+
+    def __init__(self, device: int = 0, large_from: int = ingest.MAX_WINDOW, window_bytes: int = WINDOW_BYTES,
+                 slab_bytes: int = SLAB_BYTES):
         from . import _native
+        if large_from < 0 or large_from > ingest.MAX_WINDOW or window_bytes < 1 or slab_bytes < 1024 or slab_bytes % 1024:
+            raise ValueError('large_from in [0, MAX_WINDOW], window_bytes >= 1, slab_bytes a positive multiple of 1024')
+        self.large_from = int(large_from)
+        self.window_bytes = min(int(window_bytes), ingest.MAX_WINDOW - 2 * HEADROOM)
+        self.slab_bytes = min(int(slab_bytes), 1 << 30)
         self._n = _native
         self.device = int(device)
         self.h = None
@@ -132,8 +239,6 @@ class DeviceSorter:
             job.refusal = 'header-columns'
         elif pos >= size:
             job.refusal = 'header-only'
-        elif size - pos >= ingest.MAX_WINDOW:
-            job.refusal = 'size'
         if job.refusal is None:
             line = egress._join(list(names))
             if line is None:
@@ -146,14 +251,18 @@ class DeviceSorter:
         dev = self._ingests.get(key)
         if dev is None:
             dev = self._ingests[key] = ingest.DeviceIngest(self.device, ncols, key[1])
-        job.slot = self._slot[key] = 1 - self._slot.get(key, 1)
         job.dev = dev
-        job.view = dev.stage(job.slot, job.nbody)
+        # (a body that one window holds takes the whole-body route whatever its size: large_from <= MAX_WINDOW and
+        # window_bytes < MAX_WINDOW, so that route never sees a body it cannot stage)
+        job.windowed = job.nbody >= self.large_from and job.nbody > self.window_bytes
+        if not job.windowed:
+            job.slot = self._slot[key] = 1 - self._slot.get(key, 1)
+            job.view = dev.stage(job.slot, job.nbody)
         return job
 
     def _start(self, path: str) -> _Job:
         job = self._prepare(path)
-        if job.refusal is None:
+        if job.refusal is None and not job.windowed:   # (a windowed file's reads take both slots: in its own turn)
             if self._pool is None:
                 from concurrent.futures import ThreadPoolExecutor
                 self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='kw-sort')
@@ -213,6 +322,11 @@ class DeviceSorter:
         try:
             if job.refusal is not None:
                 return self._refuse(job.refusal)
+            if job.windowed:
+                try:
+                    return self._windowed(job)
+                except Refusal as r:
+                    return self._refuse(r.reason, keep_last=r.keep_last)
             stats['wall_s']['read'] += job.future.result() if job.future is not None else job.read()
         finally:
             # the next file's body, into the other slot, while this one is on the device
@@ -261,6 +375,142 @@ class DeviceSorter:
         self._account(stats, ms, nbody, t0, t1, t2, t3, 'device')
         stats['gather_bytes'] += len(out)
         stats['wall_s']['write'] += time.perf_counter() - t3
+        return True
+
+    # ------------------------------------------------------------------ a file of several windows
+    def begin(self, time_col: int, expect_bytes: int, block_rows: int = egress.PANDAS_BLOCK_ROWS) -> None:
+        """kw_sort_begin; ``Refusal('memory')`` where the store does not fit."""
+        rc = self._n.lib().kw_sort_begin(self.h, int(time_col), int(block_rows), int(expect_bytes))
+        if rc == self._n.KW_EOVERFLOW:
+            raise Refusal('memory')
+        self._check(rc)
+
+    def window(self, dev: ingest.DeviceIngest, consumed: int) -> None:
+        """kw_sort_window over ``dev``'s last parse, which consumed ``consumed`` bytes."""
+        self._check(self._n.lib().kw_sort_window(self.h, dev.h, int(consumed), None))
+
+    def finish(self):
+        """kw_sort_finish: as :meth:`keys`, over all the windows' rows."""
+        keys_p, nr, body = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
+        sv, bad_row, bad_col, asc = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._n.lib().kw_sort_finish(self.h, ctypes.byref(keys_p), ctypes.byref(nr), ctypes.byref(body),
+                                                 ctypes.byref(sv), ctypes.byref(bad_row), ctypes.byref(bad_col),
+                                                 ctypes.byref(asc)))
+        keys = None
+        if sv.value == self._n.KW_SORT_OK:
+            keys = np.frombuffer((ctypes.c_int64 * nr.value).from_address(keys_p.value), dtype=np.int64)
+        return sv.value, int(bad_row.value), int(bad_col.value), keys, int(body.value), bool(asc.value)
+
+    def gather_begin(self, order, slab_bytes: int):
+        """kw_sort_gather_begin: ``(total bytes, slabs)`` of the body in ``order``."""
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        total, slabs = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._n.lib().kw_sort_gather_begin(self.h, self._n.ptr(order), len(order), int(slab_bytes),
+                                                       ctypes.byref(total), ctypes.byref(slabs)))
+        return int(total.value), int(slabs.value)
+
+    def gather_slab(self, k: int) -> np.ndarray:
+        """kw_sort_gather_slab: slab ``k`` as a uint8 view of a pinned slab of the handle (valid until the next one)."""
+        out_p, out_n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._n.lib().kw_sort_gather_slab(self.h, int(k), ctypes.byref(out_p), ctypes.byref(out_n)))
+        return np.frombuffer((ctypes.c_uint8 * out_n.value).from_address(out_p.value), dtype=np.uint8)
+
+    def _windowed(self, job: _Job) -> bool:
+        """:meth:`sort_file` for a body that goes to the device in windows; raises :class:`Refusal`."""
+        stats, n = LAST_STATS, self._n
+        dev, nbody, path = job.dev, job.nbody, job.path
+        t0 = time.perf_counter()
+        self.begin(job.names.index('time_unix'), nbody)
+        if self._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='kw-sort')
+        seen = {'rows': 0, 'last': 0, 'parse_ms': 0.0, 'read_s': 0.0}
+        for slot in (0, 1):   # (here, so that the reader thread finds both slots at their size and makes no device call)
+            dev.stage(slot, min(self.window_bytes, HEADROOM) + min(self.window_bytes, nbody))
+        with open(path, 'rb', buffering=0) as fh:
+
+            def fill(slot, at, lo, k):
+                t = time.perf_counter()
+                mv, got = memoryview(dev.stage(slot, at + k))[at:at + k], 0
+                while got < k:
+                    r = os.preadv(fh.fileno(), [mv[got:]], job.pos + lo + got)
+                    if not r:
+                        raise OSError(f'{path}: the file shrank while it was read')
+                    got += r
+                seen['read_s'] += time.perf_counter() - t
+
+            def move(src, src_at, dst, dst_at, k):
+                dev.stage(dst, dst_at + k)[dst_at:dst_at + k] = dev.stage(src, src_at + k)[src_at:src_at + k]
+
+            def parse(slot, at, k, final, _start):
+                view = dev.stage(slot, at + k)[at:at + k]
+                d_text = dev.upload(slot, at, k)
+                max_rows = int(np.count_nonzero(view == 0x0A)) + 1     # (while the upload runs)
+                verdict, _bad, n_rows, consumed = dev.parse(d_text, k, final, max_rows)
+                if verdict != n.KW_INGEST_OK:
+                    raise Refusal('ingest-' + INGEST_VERDICTS[verdict])
+                if final and consumed != k:
+                    raise Refusal('ingest-EMPTY')
+                seen['parse_ms'] += dev.last_ms()['all']
+                if n_rows:
+                    self.window(dev, consumed)
+                    seen['rows'] += n_rows
+                if final:
+                    seen['last'] = int(view[k - 1])
+                return n_rows, consumed
+
+            stats['windows'] += read_windows(nbody, self.window_bytes, fill, move, parse, self._pool.submit)
+        if seen['rows'] < 1:
+            raise Refusal('ingest-EMPTY')
+        sv, bad_row, bad_col, keys, body, asc = self.finish()
+        if sv != n.KW_SORT_OK:
+            stats['last'] = {'verdict': SORT_VERDICTS[sv], 'row': bad_row, 'col': bad_col}
+            raise Refusal('sort-' + SORT_VERDICTS[sv], keep_last=True)
+        t1 = time.perf_counter()
+        order = None
+        if not asc:
+            order = np.argsort(keys, kind='quicksort')       # pandas' own call: its order among equal keys
+            if (order == np.arange(len(keys))).all():
+                order = None
+        t2 = time.perf_counter()
+        raw_head, head = job.head
+        ms = {'all': seen['parse_ms']}
+        stats['wall_s']['read'] += seen['read_s']
+        # (the unchanged-file test of sort_file, with the bytes and the last byte the windows added up)
+        if order is None and raw_head == head and body == nbody and seen['last'] == 0x0A:
+            self._account(stats, ms, nbody, t0, t1, t2, t2, 'unchanged')
+            return True
+        if order is None:
+            order = np.arange(len(keys), dtype=np.int64)
+        total, slabs = self.gather_begin(order, self.slab_bytes)
+        # slab by slab into a sibling file that takes the target's place after the last one
+        import stat
+        import tempfile
+        mode = stat.S_IMODE(os.stat(path).st_mode)
+        fd, tmp = tempfile.mkstemp(prefix='.' + os.path.basename(path) + '.', suffix='.tmp',
+                                   dir=os.path.dirname(os.path.abspath(path)))
+        t_write = 0.0
+        try:
+            with os.fdopen(fd, 'wb') as out:
+                os.fchmod(out.fileno(), mode)
+                out.write(head)
+                for k in range(slabs):
+                    piece = self.gather_slab(k)
+                    t = time.perf_counter()
+                    out.write(piece)
+                    t_write += time.perf_counter() - t
+            os.replace(tmp, path)
+        except BaseException:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
+        t3 = time.perf_counter()
+        self._account(stats, ms, nbody, t0, t1, t2, t3 - t_write, 'device')
+        stats['slabs'] += slabs
+        stats['gather_bytes'] += total
+        stats['wall_s']['write'] += t_write
         return True
 
     def _account(self, stats, parse_ms, nbody, t0, t1, t2, t3, route):

@@ -23,9 +23,21 @@
  *                  bad_row: the block's first row, of the first such block; bad_col: its lowest such column.
  * A row that passes is written by pandas byte for byte as it stands in the file, with "\n" as its terminator.
  *
+ * A file of any size.  kw_ingest_parse takes less than 2^31 bytes, and kw_sort_gather lays out less than 2^31.
+ * A larger body -- or any body the caller wants staged in pieces -- is parsed in windows (final == 0, the
+ * unconsumed tail opens the next window): kw_sort_begin reserves a store in device memory, kw_sort_window appends
+ * each parsed window's text and spans to it and works its rows at their global row numbers (a block's witnesses
+ * may lie in another window than its numeric cells; the ascending test carries the last key over a window's
+ * edge, and equal keys there are not ascending), and kw_sort_finish gives the whole file's verdict: exactly what
+ * kw_sort_keys gives on the same body parsed as one text.  kw_sort_gather_begin then scans an order of any total
+ * size with 64-bit offsets, and kw_sort_gather_slab hands the output over one slab at a time through two pinned
+ * host slabs; a record, its '\n' and a lane's 16-byte store may straddle a slab's edge at any phase.  Two limits
+ * remain: a single record of 2^31 - 2^20 bytes or more (no window holds it), and a body larger than the device's
+ * free memory (kw_sort_begin: KW_EOVERFLOW).
+ *
  * Conventions as kwingest.h: 0 or a negative KW_E* code; kw_sort_last_error gives the message; one handle per
  * device and host thread.  The kw_ingest handle's parse, and the text it parsed, must stand from kw_sort_keys
- * until the last kw_sort_gather of that file.
+ * until the last kw_sort_gather of that file; after kw_sort_window the handle is free at once.
  */
 #ifndef KWSORT_H
 #define KWSORT_H
@@ -65,9 +77,45 @@ int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t block_rows
  * handle holding *out_bytes bytes, valid until the next kw_sort_gather. */
 int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const uint8_t **out, int64_t *out_bytes);
 
-/* Device times (ms) of the last kw_sort_keys and kw_sort_gather, up to 4 values: [0] keys (the rows' keys and
- * conditions), [1] scan (the order's range check, the records' lengths and their scan), [2] gather (the copy
- * kernel), [3] copies (the order to the device, the keys and the body to the host). */
+/* ---- a file of several windows -------------------------------------------------------------------------------
+ * Start a file whose body is parsed window by window: time_col and block_rows as kw_sort_keys; expect_bytes >= 1:
+ * the bytes of body text the windows will hand over at most.  Reserves the store for them (a store the handle
+ * already has is kept when it is large enough) and resets what the windows accumulate.  KW_EOVERFLOW, with
+ * nothing allocated: the store, a quarter of it again for what is kept per row, and 64 MiB do not fit in the
+ * device's free memory (hipMemGetInfo), or expect_bytes exceeds the tests' KW_TEST_SORT_STORE_MAX. */
+int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, int64_t expect_bytes);
+
+/* After an OK kw_ingest_parse of the file's next window (final or not; at least one row; every window's handle
+ * has the same ncols): bytes [0, consumed) of the parse's text -- consumed as the parse gave it -- go to the end
+ * of the store, the rows' spans with them, and the rows' keys, conditions and witnesses to their global rows.
+ * Returns after the device finished: the ingest handle may then take the next window.  KW_EOVERFLOW: more bytes
+ * than kw_sort_begin was told.  An error ends the file. */
+int kw_sort_window(kw_sort *h, kw_ingest *ig, int64_t consumed, void *stream);
+
+/* After the last window: the outputs of kw_sort_keys, over all the windows' rows as one text (*body_bytes: the
+ * sum over the windows).  With the verdict KW_SORT_OK the store stands for kw_sort_gather_begin, or for
+ * kw_sort_gather where the body stays under 2^31 bytes, until the next kw_sort_begin or kw_sort_keys. */
+int kw_sort_finish(kw_sort *h, const int64_t **keys, int64_t *n_rows, int64_t *body_bytes, int32_t *verdict,
+                   int64_t *bad_row, int32_t *bad_col, int32_t *ascending);
+
+/* ---- the output in slabs -------------------------------------------------------------------------------------
+ * After a taken kw_sort_keys or kw_sort_finish: kw_sort_gather's range check, lengths and scan for `order`
+ * (n entries), and nothing copied.  slab_bytes: a positive multiple of 1024, below 2^31.  *total_bytes: the
+ * body's bytes, of any size; *n_slabs: ceil(total / slab_bytes).  KW_EINVAL for an order entry outside
+ * [0, n_rows): no slab can then be fetched. */
+int kw_sort_gather_begin(kw_sort *h, const int64_t *order, int64_t n, int64_t slab_bytes, int64_t *total_bytes,
+                         int64_t *n_slabs);
+
+/* Bytes [k * slab_bytes, min((k + 1) * slab_bytes, total)) of that body, 0 <= k < n_slabs in any order: *out is
+ * one of two pinned host slabs of the handle, in turn, holding *out_bytes bytes, valid until the next
+ * kw_sort_gather_slab.  Before it returns the call starts slab k + 1 into the other slab: asked for next, it is
+ * laid out and copied while the caller writes slab k away. */
+int kw_sort_gather_slab(kw_sort *h, int64_t k, const uint8_t **out, int64_t *out_bytes);
+
+/* Device times (ms) of the last kw_sort_keys and kw_sort_gather, or summed over a file's windows and slabs, up to
+ * 4 values: [0] keys (the rows' keys and conditions), [1] scan (the order's range check, the records' lengths and
+ * their scan), [2] gather (the copy kernel), [3] copies (the text into the store, the order to the device, the
+ * keys and the body to the host). */
 int kw_sort_last_ms(kw_sort *h, float *ms, int32_t n);
 
 const char *kw_sort_last_error(kw_sort *h);
