@@ -6,6 +6,7 @@ Modules:
   match_keywords the drop-in replacement of the reference script
   dedup          CDX URL keep-first dedup on the GPU
   resume         the scraper's resume filter (links not yet scraped) on the GPU
+  links          the link list's refresh and split (experiental/drop.py, split.py) on the GPU
   dist           multi-GPU sharding + RCCL gather of hit records
   synth          seeded synthetic corpus (bench/test data)
 """

@@ -268,6 +268,69 @@ class GpuUrlDedup:
         self._check(_native.lib().kw_cdx_exclude_last_ms(self.h, _native.ptr(v), 3))
         return [float(x) for x in v]
 
+    # ---- the link list's refresh and split (include/kwdedup.h kw_cdx_run_exclude_unique, kw_cdx_csv_select_*; links.py)
+    def run_exclude_unique(self, n_exclude: int) -> Tuple[int, int, int, int]:
+        """run_exclude that also drops the repeats among the link rows
+        (``new[~new.url.isin(prev.url)].drop_duplicates('url')``): (link rows, those seen, those whose first holder
+        is an earlier link row, those kept)."""
+        st = self.torch.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_run_exclude_unique(self.h, int(n_exclude), ctypes.c_void_p(st.cuda_stream)))
+        c = np.zeros(3, dtype=np.int64)
+        self._check(_native.lib().kw_cdx_exclude_counts(self.h, _native.ptr(c)))
+        d = ctypes.c_int64()
+        self._check(_native.lib().kw_cdx_exclude_duplicates(self.h, ctypes.byref(d)))
+        return int(c[0]), int(c[1]), int(d.value), int(c[2])
+
+    def selected_ts(self) -> np.ndarray:
+        """The timestamps of the last run's surviving rows (cdx_run's kept rows, run_exclude's remaining rows,
+        run_exclude_unique's kept rows), in row order, on the host."""
+        t = self.torch
+        nk, nb = ctypes.c_int64(), ctypes.c_int64()
+        self._check(_native.lib().kw_dedup_kept_size(self.h, ctypes.byref(nk), ctypes.byref(nb)))
+        ts = t.empty(max(nk.value, 1), dtype=t.int64, device=t.device('cuda', self.device))
+        st = t.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_selected_ts(self.h, _native.ptr(ts), ctypes.c_void_p(st.cuda_stream)))
+        st.synchronize()
+        return ts[:nk.value].cpu().numpy()
+
+    def csv_select(self, order, seg=None) -> List[bytes]:
+        """The surviving rows ``order`` (indices among them: any subset, any order) rendered on the device as the
+        bytes of ``to_csv(index=False)`` over columns date_time, url; ``seg`` (ascending bounds into ``order``, from
+        0 to its length) cuts them into one file per pair of bounds, each with its own header.  A list of the
+        files' bytes (one file without ``seg``).  ``order`` and ``seg``: int64 numpy arrays or device tensors."""
+        t = self.torch
+        dev = t.device('cuda', self.device)
+
+        def on_device(a):
+            if isinstance(a, t.Tensor):
+                return a.to(device=dev, dtype=t.int64).contiguous().view(-1)
+            return t.from_numpy(np.ascontiguousarray(a, dtype=np.int64).reshape(-1)).to(dev)
+        d_order = on_device(order)
+        n_order = int(d_order.numel())
+        d_seg = on_device(np.array([0, n_order], dtype=np.int64) if seg is None else seg)
+        n_seg = int(d_seg.numel()) - 1
+        if n_seg < 0:
+            raise ValueError("csv_select: seg needs at least one bound")
+        d_size = t.zeros(max(n_seg, 1), dtype=t.int64, device=dev)
+        st = t.cuda.current_stream(self.device)
+        nb = ctypes.c_int64()
+        self._check(_native.lib().kw_cdx_csv_select_size(self.h, _native.ptr(d_order), n_order, _native.ptr(d_seg), n_seg,
+                                                         _native.ptr(d_size), ctypes.byref(nb),
+                                                         ctypes.c_void_p(st.cuda_stream)))
+        out = t.empty(nb.value + 16, dtype=t.uint8, device=dev)
+        self._check(_native.lib().kw_cdx_csv_select_copy(self.h, _native.ptr(out), ctypes.c_void_p(st.cuda_stream)))
+        raw = out[:nb.value].cpu().numpy().tobytes()
+        cut = np.concatenate([[0], np.cumsum(d_size[:n_seg].cpu().numpy())])
+        if int(cut[-1]) != nb.value:
+            raise RuntimeError(f"csv_select: the files' sizes sum to {int(cut[-1])}, the total is {nb.value}")
+        return [raw[cut[k]:cut[k + 1]] for k in range(n_seg)]
+
+    def select_last_ms(self) -> List[float]:
+        """Device times (ms) of the last csv_select: the size pass, the copy pass."""
+        v = np.zeros(2, dtype=np.float32)
+        self._check(_native.lib().kw_cdx_select_last_ms(self.h, _native.ptr(v), 2))
+        return [float(x) for x in v]
+
     def dedup_strings(self, urls: Sequence[str], normalize: bool = True) -> Tuple[np.ndarray, List[str]]:
         """Pack, upload, classify: (kept row indices, their normalised URLs)."""
         arena, off = pack_urls(urls)

@@ -24,6 +24,11 @@
 //   cx_linelen_kernel       lane = kept row: decimal digits of the timestamp, the URL's length, whether it holds
 //                           a ',' (then it is quoted).
 //
+//   cx_sel_*                the surviving rows rendered in a given order into several files (kw_cdx_csv_select_*; the
+//                           link list's refresh and split, experiental/drop.py and split.py): the order's indices and
+//                           the files' bounds checked, the lines' lengths gathered through the order, cx_scan_*, then
+//                           cx_fill_kernel with SelGen; described above the kernels.
+//
 //   cv_*                    quoted CSV, one column out (kw_csv_append, the scraper's resume filter:
 //                           constant_rate_scrapper.py:312-360; the rule is restated in tests/resume_rule.py): the
 //                           same tiles and masks with quote state carried across them; described above the kernels.
@@ -471,6 +476,114 @@ __global__ __launch_bounds__(BLOCK) void cx_linelen_kernel(int64_t n_kept, const
     if (blockIdx.x == 0 && threadIdx.x == 0) seglen[0] = HEADER_LEN;
 }
 
+// ---- the surviving rows rendered in a given order into several files (kw_cdx_csv_select_*)
+//
+// order[0, n_order) indexes the last run's surviving rows; seg[0 .. n_seg] bounds the files in it.  The output is a
+// list of m = n_order + n_seg lines: file s is its header line (line seg[s] + s) and then one line a selected row
+// (order position j of file s is line j + s + 1).  src[line] = -1 for a header, else the surviving row's index with
+// bit 62 set when its URL is quoted; len[line] its bytes, scanned in place by cx_scan_* into the lines' offsets.
+// The copy is cx_fill_kernel<SelGen>: a lane owns 16 bytes of the output, so the stores are full and coalesced
+// whatever the order; the gather is on the read side.
+constexpr int64_t SEL_QUOTED = (int64_t)1 << 62;
+
+struct SelErrs {
+    unsigned long long seg;     // the first s with a bad bound seg[s] (NONE)
+    unsigned long long order;   // the first j with order[j] outside [0, n_kept) (NONE)
+};
+
+// lane = bound s: seg[0] = 0, seg[n_seg] = n_order, ascending; file s's header line.  A bound is only ever used as
+// an index after it was found inside [0, n_order].
+__global__ __launch_bounds__(BLOCK) void cx_sel_seg_kernel(const int64_t *__restrict__ seg, int64_t n_seg, int64_t n_order,
+                                                           unsigned long long *__restrict__ len, int64_t *__restrict__ src,
+                                                           SelErrs *__restrict__ errs)
+{
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s <= n_seg; s += (int64_t)gridDim.x * BLOCK) {
+        const int64_t b = seg[s];
+        bool ok = b >= 0 && b <= n_order;
+        if (s == 0) ok = ok && b == 0;
+        if (s == n_seg) ok = ok && b == n_order;
+        if (s > 0) ok = ok && b >= seg[s - 1];
+        if (!ok) { atomicMin(&errs->seg, (unsigned long long)s); continue; }
+        if (s < n_seg) {
+            len[b + s] = HEADER_LEN;
+            src[b + s] = -1;
+        }
+    }
+}
+
+// lane = order position j: the index checked, the file found, the line's length (as cx_linelen_kernel)
+__global__ __launch_bounds__(BLOCK) void cx_sel_len_kernel(const int64_t *__restrict__ order, int64_t n_order,
+                                                           const int64_t *__restrict__ seg, int64_t n_seg, int64_t n_kept,
+                                                           const int64_t *__restrict__ ts, int64_t row_base,
+                                                           const int64_t *__restrict__ kept_row,
+                                                           const int64_t *__restrict__ kept_off,
+                                                           const uint8_t *__restrict__ kept_bytes,
+                                                           unsigned long long *__restrict__ len, int64_t *__restrict__ src,
+                                                           SelErrs *__restrict__ errs)
+{
+    constexpr uint64_t ONES = 0x0101010101010101ull;
+    for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < n_order; j += (int64_t)gridDim.x * BLOCK) {
+        const int64_t s = seg_find(seg, 0, n_seg, j);   // (in [0, n_seg) whatever seg holds: line < n_order + n_seg)
+        const int64_t line = j + s + 1;
+        const int64_t k = order[j];
+        if (k < 0 || k >= n_kept) {   // (never read as an address)
+            atomicMin(&errs->order, (unsigned long long)j);
+            len[line] = 0;
+            src[line] = -1;
+            continue;
+        }
+        const int64_t b = kept_off[k], e = kept_off[k + 1];
+        bool comma = false;
+        for (int64_t w = b & ~(int64_t)7; w < e && !comma; w += 8) {
+            const uint64_t v = *(const uint64_t *)(kept_bytes + w);
+            const int b0 = w < b ? (int)(b - w) : 0;
+            const int b1 = e - w >= 8 ? 8 : (int)(e - w);
+            const uint64_t in = ~((1ull << (8 * b0)) - 1ull) & (b1 == 8 ? ~0ull : (1ull << (8 * b1)) - 1ull);
+            comma = (eq8(v, 0x2Cull * ONES) & in) != 0;
+        }
+        len[line] = (unsigned long long)(dec_digits(ts[row_base + kept_row[k]]) + 1 + (e - b) + (comma ? 2 : 0) + 1);
+        src[line] = comma ? (k | SEL_QUOTED) : k;
+    }
+}
+
+// seg_bytes[s] = the bytes of file s, from the scanned line offsets (off[m] = the total)
+__global__ __launch_bounds__(BLOCK) void cx_sel_bytes_kernel(const int64_t *__restrict__ seg, int64_t n_seg,
+                                                             const int64_t *__restrict__ off,
+                                                             int64_t *__restrict__ seg_bytes)
+{
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < n_seg; s += (int64_t)gridDim.x * BLOCK)
+        seg_bytes[s] = off[seg[s + 1] + s + 1] - off[seg[s] + s];
+}
+
+// line l = a header (src[l] < 0) or surviving row src[l]: as CsvGen
+struct SelGen {
+    const int64_t *ts, *kept_row, *kept_off;
+    const uint8_t *kept_bytes;
+    const int64_t *src;
+    int64_t row_base;
+    __device__ __forceinline__ CsvGen::Ctx open(int64_t l) const
+    {
+        CsvGen::Ctx c{0, 0, nullptr, 0, 0};
+        const int64_t v = src[l];
+        if (v < 0) { c.nd = -1; return c; }
+        const int64_t k = v & (SEL_QUOTED - 1);
+        c.ts = ts[row_base + kept_row[k]];
+        c.nd = dec_digits(c.ts);
+        c.url = kept_bytes + kept_off[k];
+        c.ulen = kept_off[k + 1] - kept_off[k];
+        c.q = (v & SEL_QUOTED) ? 1 : 0;
+        return c;
+    }
+    __device__ __forceinline__ uint64_t byte(const CsvGen::Ctx &c, int64_t j) const { return CsvGen{}.byte(c, j); }
+};
+
+__global__ __launch_bounds__(BLOCK) void cx_sel_ts_kernel(int64_t n_kept, const int64_t *__restrict__ ts, int64_t row_base,
+                                                          const int64_t *__restrict__ kept_row, int64_t *__restrict__ out)
+{
+    for (int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x; k < n_kept; k += (int64_t)gridDim.x * BLOCK)
+        out[k] = ts[row_base + kept_row[k]];
+}
+
 // ---- quoted CSV, one column out (kw_csv_append; the rule: DESIGN.md §7, tests/resume_rule.py)
 //
 //   cv_quotes_kernel    a tile's '"' bytes counted (their exclusive scan over the tiles carries the quote parity
@@ -738,6 +851,14 @@ struct kw_cdx_store {
     bool csv_ready = false;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms[3] = {0.f, 0.f, 0.f};
+    // select render (kw_cdx_csv_select_*)
+    uint64_t sel_serial = 0;     // the kw_dedup_run of the last kw_cdx_run / _run_exclude / _run_exclude_unique over
+                                 //   this store (0: none since the store changed)
+    void *d_sel = nullptr;       // line offsets (m + 1), line sources (m), scan chunks, the error words
+    size_t sel_scratch = 0;
+    int64_t sel_lines = 0, sel_bytes = 0;
+    bool sel_ready = false;
+    float sel_ms[2] = {0.f, 0.f};
 };
 
 void kw_cdx_store_destroy(kw_cdx_store *s)
@@ -750,6 +871,7 @@ void kw_cdx_store_destroy(kw_cdx_store *s)
     if (s->d_tiles) (void)hipFree(s->d_tiles);
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_csv) (void)hipFree(s->d_csv);
+    if (s->d_sel) (void)hipFree(s->d_sel);
     for (auto &e : s->ev)
         if (e) (void)hipEventDestroy(e);
     delete s;
@@ -848,6 +970,8 @@ extern "C" int kw_cdx_begin(kw_dedup *h)
     s->n = s->n_bytes = 0;
     s->run_serial = 0;
     s->csv_ready = false;
+    s->sel_serial = 0;
+    s->sel_ready = false;
     s->ms[0] = s->ms[1] = s->ms[2] = 0.f;
     return KW_OK;
 }
@@ -965,6 +1089,8 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     s->n_bytes += total;
     s->run_serial = 0;
     s->csv_ready = false;
+    s->sel_serial = 0;
+    s->sel_ready = false;
     *n_rows = n_new;
     return KW_OK;
 }
@@ -1117,11 +1243,13 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     s->n_bytes += total;
     s->run_serial = 0;
     s->csv_ready = false;
+    s->sel_serial = 0;
+    s->sel_ready = false;
     *n_rows = n_new;
     return KW_OK;
 }
 
-extern "C" int kw_cdx_run_exclude(kw_dedup *h, int64_t n_exclude, void *stream)
+static int run_exclude(kw_dedup *h, int64_t n_exclude, bool unique, void *stream)
 {
     if (!h) return KW_EINVAL;
     DDCHK(h, hipSetDevice(h->device));
@@ -1133,11 +1261,26 @@ extern "C" int kw_cdx_run_exclude(kw_dedup *h, int64_t n_exclude, void *stream)
     if (rc) return rc;
     s->csv_ready = false;
     s->run_serial = 0;   // (the kept-rows buffers will hold the remaining rows: nothing for kw_cdx_csv_* to render)
+    s->sel_ready = false;
+    s->sel_serial = 0;
     h->no_compact = true;   // (the run's own kept rows would be thrown away: the pass compacts the link rows)
     rc = kw_dedup_run(h, s->arena, s->off, s->n, 0, s->code, stream);
     h->no_compact = false;
     if (rc) return rc;
-    return kw_dedup_exclude_pass(h, s->arena, n_exclude, s->code, (hipStream_t)stream);
+    rc = kw_dedup_exclude_pass(h, s->arena, n_exclude, s->code, unique, (hipStream_t)stream);
+    if (rc) return rc;
+    s->sel_serial = h->run_serial;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_run_exclude(kw_dedup *h, int64_t n_exclude, void *stream)
+{
+    return run_exclude(h, n_exclude, false, stream);
+}
+
+extern "C" int kw_cdx_run_exclude_unique(kw_dedup *h, int64_t n_exclude, void *stream)
+{
+    return run_exclude(h, n_exclude, true, stream);
 }
 
 extern "C" int kw_cdx_exclude_codes(kw_dedup *h, uint8_t *d_code, void *stream)
@@ -1192,9 +1335,12 @@ extern "C" int kw_cdx_run(kw_dedup *h, int32_t flags, void *stream)
     if (rc) return rc;
     s->csv_ready = false;
     s->run_serial = 0;
+    s->sel_ready = false;
+    s->sel_serial = 0;
     rc = kw_dedup_run(h, s->arena, s->off, s->n, flags, s->code, stream);
     if (rc) return rc;
     s->run_serial = h->run_serial;
+    s->sel_serial = h->run_serial;
     return KW_OK;
 }
 
@@ -1275,5 +1421,153 @@ extern "C" int kw_cdx_last_ms(kw_dedup *h, float *ms, int32_t k)
 {
     if (!h || !ms || k < 0) return KW_EINVAL;
     for (int i = 0; i < k && i < 3; ++i) ms[i] = h->cdx ? h->cdx->ms[i] : 0.f;
+    return KW_OK;
+}
+
+// ---- the surviving rows in a given order, into several files (kw_cdx_selected_ts, kw_cdx_csv_select_*)
+
+// the last run over this store and the store row of surviving row 0's row index: kw_cdx_run's kept rows carry store
+// rows, the exclude runs' remaining rows carry indices among the link rows
+static int select_state(kw_dedup *h, const char *who, kw_cdx_store **out, int64_t *row_base)
+{
+    kw_cdx_store *s = h->cdx;
+    if (!s || s->sel_serial == 0 || s->sel_serial != h->run_serial) {
+        h->err = std::string(who) + ": no kw_cdx_run, kw_cdx_run_exclude or kw_cdx_run_exclude_unique over this store";
+        return KW_ESTATE;
+    }
+    *out = s;
+    *row_base = (h->ex_serial != 0 && h->ex_serial == h->run_serial) ? s->n - h->ex_links : 0;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_selected_ts(kw_dedup *h, int64_t *d_ts, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = nullptr;
+    int64_t base = 0;
+    if (int rc = select_state(h, "kw_cdx_selected_ts", &s, &base)) return rc;
+    if (h->n_kept == 0) return KW_OK;
+    if (!d_ts) { h->err = "kw_cdx_selected_ts: bad arguments"; return KW_EINVAL; }
+    DDCHK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(cx_sel_ts_kernel, dim3(grid_for(h, h->n_kept)), dim3(BLOCK), 0, (hipStream_t)stream, h->n_kept,
+                       (const int64_t *)s->ts, base, (const int64_t *)h->kept_row, d_ts);
+    DDCHK(h, hipGetLastError());
+    return KW_OK;
+}
+
+// d_sel: off (m + 1 words), src (m words), the scan's chunks and grand total, the error words
+static void select_carve(kw_cdx_store *s, size_t m, unsigned long long **off, int64_t **src, unsigned long long **chunk,
+                         unsigned long long **grand, SelErrs **errs)
+{
+    uint8_t *p = (uint8_t *)s->d_sel;
+    *off = (unsigned long long *)p;
+    p += up256(8 * (m + 1));
+    *src = (int64_t *)p;
+    p += up256(8 * m);
+    *chunk = (unsigned long long *)p;
+    p += up256(8 * SCAN_CHUNKS);
+    *grand = (unsigned long long *)p;
+    *errs = (SelErrs *)(p + 64);
+}
+
+extern "C" int kw_cdx_csv_select_size(kw_dedup *h, const int64_t *d_order, int64_t n_order, const int64_t *d_seg,
+                                      int64_t n_seg, int64_t *d_seg_bytes, int64_t *n_bytes, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = nullptr;
+    int64_t base = 0;
+    if (int rc = select_state(h, "kw_cdx_csv_select_size", &s, &base)) return rc;
+    s->sel_ready = false;
+    if (!n_bytes || n_order < 0 || n_seg < 0 || (n_order > 0 && (!d_order || n_seg == 0)) ||
+        (n_seg > 0 && (!d_seg || !d_seg_bytes))) {
+        h->err = "kw_cdx_csv_select_size: bad arguments";
+        return KW_EINVAL;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    s->sel_ms[0] = s->sel_ms[1] = 0.f;
+    const int64_t m = n_order + n_seg;
+    s->sel_lines = m;
+    s->sel_bytes = 0;
+    if (m > 0) {
+        int rc = scratch_fit(h, &s->d_sel, &s->sel_scratch,
+                             up256(8 * ((size_t)m + 1)) + up256(8 * (size_t)m) + up256(8 * SCAN_CHUNKS) + 256);
+        if (rc) return rc;
+        unsigned long long *off, *chunk, *grand;
+        int64_t *src;
+        SelErrs *errs;
+        select_carve(s, (size_t)m, &off, &src, &chunk, &grand, &errs);
+        DDCHK(h, hipEventRecord(s->ev[3], st));
+        DDCHK(h, hipMemsetAsync(errs, 0xFF, sizeof(SelErrs), st));
+        hipLaunchKernelGGL(cx_sel_seg_kernel, dim3(grid_for(h, n_seg + 1)), dim3(BLOCK), 0, st, d_seg, n_seg, n_order, off,
+                           src, errs);
+        if (n_order > 0)
+            hipLaunchKernelGGL(cx_sel_len_kernel, dim3(grid_for(h, n_order)), dim3(BLOCK), 0, st, d_order, n_order, d_seg,
+                               n_seg, h->n_kept, (const int64_t *)s->ts, base, (const int64_t *)h->kept_row,
+                               (const int64_t *)h->kept_off, (const uint8_t *)h->kept_bytes, off, src, errs);
+        DDCHK(h, hipGetLastError());
+        SelErrs e;
+        DDCHK(h, hipMemcpyAsync(&e, errs, sizeof(e), hipMemcpyDeviceToHost, st));
+        DDCHK(h, hipStreamSynchronize(st));
+        if (e.seg != NONE) {
+            h->err = "kw_cdx_csv_select_size: d_seg[" + std::to_string(e.seg) + "] is not an ascending bound from 0 to n_order";
+            return KW_EINVAL;
+        }
+        if (e.order != NONE) {
+            int64_t v = 0;
+            DDCHK(h, hipMemcpy(&v, d_order + e.order, 8, hipMemcpyDeviceToHost));
+            h->err = "kw_cdx_csv_select_size: d_order[" + std::to_string(e.order) + "] = " + std::to_string(v) +
+                     " is outside the " + std::to_string(h->n_kept) + " surviving rows";
+            return KW_EINVAL;
+        }
+        scan_launch(off, m, chunk, grand, st);
+        DDCHK(h, hipGetLastError());
+        DDCHK(h, hipMemcpyAsync(off + m, grand, 8, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(cx_sel_bytes_kernel, dim3(grid_for(h, n_seg)), dim3(BLOCK), 0, st, d_seg, n_seg,
+                           (const int64_t *)off, d_seg_bytes);
+        DDCHK(h, hipGetLastError());
+        unsigned long long tot = 0;
+        DDCHK(h, hipMemcpyAsync(&tot, grand, 8, hipMemcpyDeviceToHost, st));
+        DDCHK(h, hipEventRecord(s->ev[4], st));
+        DDCHK(h, hipStreamSynchronize(st));
+        DDCHK(h, hipEventElapsedTime(&s->sel_ms[0], s->ev[3], s->ev[4]));
+        s->sel_bytes = (int64_t)tot;
+    }
+    s->sel_ready = true;
+    *n_bytes = s->sel_bytes;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_csv_select_copy(kw_dedup *h, uint8_t *d_out, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = nullptr;
+    int64_t base = 0;
+    if (int rc = select_state(h, "kw_cdx_csv_select_copy", &s, &base)) return rc;
+    if (!s->sel_ready) { h->err = "kw_cdx_csv_select_copy: no kw_cdx_csv_select_size since the last run"; return KW_ESTATE; }
+    if (s->sel_bytes == 0) return KW_OK;
+    if (!d_out || ((uintptr_t)d_out & 15) != 0) { h->err = "kw_cdx_csv_select_copy: d_out must be 16-byte aligned"; return KW_EINVAL; }
+    DDCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long *off, *chunk, *grand;
+    int64_t *src;
+    SelErrs *errs;
+    select_carve(s, (size_t)s->sel_lines, &off, &src, &chunk, &grand, &errs);
+    DDCHK(h, hipEventRecord(s->ev[3], st));
+    hipLaunchKernelGGL(cx_fill_kernel<SelGen>, dim3(grid_for(h, (s->sel_bytes + 31) / 16)), dim3(BLOCK), 0, st, d_out,
+                       (const int64_t *)off, s->sel_lines,
+                       SelGen{(const int64_t *)s->ts, (const int64_t *)h->kept_row, (const int64_t *)h->kept_off,
+                              (const uint8_t *)h->kept_bytes, (const int64_t *)src, base});
+    DDCHK(h, hipGetLastError());
+    DDCHK(h, hipEventRecord(s->ev[4], st));
+    DDCHK(h, hipStreamSynchronize(st));
+    DDCHK(h, hipEventElapsedTime(&s->sel_ms[1], s->ev[3], s->ev[4]));
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_select_last_ms(kw_dedup *h, float *ms, int32_t k)
+{
+    if (!h || !ms || k < 0) return KW_EINVAL;
+    for (int i = 0; i < k && i < 2; ++i) ms[i] = h->cdx ? h->cdx->sel_ms[i] : 0.f;
     return KW_OK;
 }

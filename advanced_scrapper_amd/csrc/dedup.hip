@@ -1506,13 +1506,16 @@ __global__ __launch_bounds__(BLOCK) void dd_materialize_kernel(const uint8_t *__
 // every URL that is not the holder's is always one of that pass's rows; the listed row itself need not be: it may
 // have been paired with a holder of its own URL that the other URL's earlier row displaced afterwards).
 // Without exclude rows (m == 0) nothing can be seen and nothing is hashed.  cnt[11]: rows listed, cnt[12]: rows seen.
+// unique (kw_cdx_run_exclude_unique): a row whose first holder is an earlier link row stays KW_URL_DUPLICATE, so
+// the rows left KEPT are new[~new.url.isin(prev.url)].drop_duplicates('url').
 __global__ __launch_bounds__(BLOCK) void dd_exclude_kernel(const uint8_t *__restrict__ arena, uint8_t *__restrict__ code,
-                                                           Scratch S, int64_t m, int64_t n)
+                                                           Scratch S, int64_t m, int64_t n, int unique)
 {
+    const uint8_t later = unique ? (uint8_t)KW_URL_DUPLICATE : (uint8_t)KW_URL_KEPT;
     uint32_t n_seen = 0;
     for (int64_t i = m + (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
         if (code[i] != KW_URL_DUPLICATE) continue;
-        if (m == 0) { code[i] = (uint8_t)KW_URL_KEPT; continue; }
+        if (m == 0) { code[i] = later; continue; }
         const RowGen gi = row_gen(S, arena, i);
         const uint64_t h = row_hash(S, gi);
         uint64_t slot = (h ^ (h >> 29)) & S.mask;
@@ -1526,7 +1529,7 @@ __global__ __launch_bounds__(BLOCK) void dd_exclude_kernel(const uint8_t *__rest
         const uint32_t r0 = (uint32_t)cur - 1u;
         if (r0 != (uint32_t)i && same_url(gi, row_gen(S, arena, r0))) {
             const bool seen = (int64_t)r0 < m;
-            code[i] = seen ? (uint8_t)KW_URL_SEEN : (uint8_t)KW_URL_KEPT;
+            code[i] = seen ? (uint8_t)KW_URL_SEEN : later;
             n_seen += seen;
         } else {
             code[i] = CODE_COLLIDE;
@@ -1894,12 +1897,13 @@ extern "C" int kw_dedup_kept_copy(kw_dedup *h, uint8_t *d_bytes, int64_t *d_off,
     return KW_OK;
 }
 
-int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, hipStream_t st)
+int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, bool unique, hipStream_t st)
 {
     const int64_t n = h->n;
     Scratch &S = h->S;
     h->ex_links = n - m;
     h->ex_seen = 0;
+    h->ex_dup = 0;
     h->n_kept = h->n_kept_bytes = 0;
     for (auto &e : h->ex_ev)
         if (!e) DDCHK(h, hipEventCreate(&e));
@@ -1907,7 +1911,8 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
     if (n > m) {
         // (without exclude rows every link row stays, the duplicates among them too: no holder is below m)
         const int grid = (int)std::min<int64_t>((n - m + BLOCK - 1) / BLOCK, (int64_t)h->cus * 8);
-        hipLaunchKernelGGL(dd_exclude_kernel, dim3(grid), dim3(BLOCK), 0, st, d_arena, d_code, S, m, n);
+        hipLaunchKernelGGL(dd_exclude_kernel, dim3(grid), dim3(BLOCK), 0, st, d_arena, d_code, S, m, n,
+                           unique ? 1 : 0);
         DDCHK(h, hipGetLastError());
         unsigned long long cnt[2];
         DDCHK(h, hipMemcpyAsync(cnt, S.cnt + 11, sizeof(cnt), hipMemcpyDeviceToHost, st));
@@ -1941,7 +1946,7 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
                     return KW_ESTATE;
                 }
                 const bool seen = (int64_t)it->second < m;
-                const uint8_t c = seen ? (uint8_t)KW_URL_SEEN : (uint8_t)KW_URL_KEPT;
+                const uint8_t c = seen ? (uint8_t)KW_URL_SEEN : unique ? (uint8_t)KW_URL_DUPLICATE : (uint8_t)KW_URL_KEPT;
                 h->ex_seen += seen;
                 DDCHK(h, hipMemcpy(d_code + rows[q], &c, 1, hipMemcpyHostToDevice));
             }
@@ -1958,6 +1963,7 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
     }
     DDCHK(h, hipEventRecord(h->ex_ev[2], st));
     DDCHK(h, hipStreamSynchronize(st));
+    h->ex_dup = h->ex_links - h->ex_seen - h->n_kept;   // (0 unless unique: every link row not seen stays)
     h->ex_serial = h->run_serial;
     return KW_OK;
 }
@@ -1975,7 +1981,15 @@ extern "C" int kw_cdx_exclude_counts(kw_dedup *h, int64_t *counts)
     if (int rc = exclude_state(h, "kw_cdx_exclude_counts")) return rc;
     counts[0] = h->ex_links;
     counts[1] = h->ex_seen;
-    counts[2] = h->ex_links - h->ex_seen;
+    counts[2] = h->ex_links - h->ex_seen - h->ex_dup;
+    return KW_OK;
+}
+
+extern "C" int kw_cdx_exclude_duplicates(kw_dedup *h, int64_t *n_duplicate)
+{
+    if (!h || !n_duplicate) return KW_EINVAL;
+    if (int rc = exclude_state(h, "kw_cdx_exclude_duplicates")) return rc;
+    *n_duplicate = h->ex_dup;
     return KW_OK;
 }
 

@@ -81,12 +81,13 @@ struct kw_dedup {
     bool no_compact = false;       // set around kw_cdx_run_exclude's kw_dedup_run: no kept rows wanted of it
     uint64_t ex_serial = 0;
     int64_t ex_links = 0, ex_seen = 0;
+    int64_t ex_dup = 0;            // kw_cdx_run_exclude_unique: link rows whose first holder is an earlier link row
     hipEvent_t ex_ev[3] = {nullptr, nullptr, nullptr};
 };
 
 // dedup.hip: the set-difference pass over the last kw_dedup_run's rows (a raw run over the same arena, offsets and
-// codes): the first m rows are the exclude rows
-int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, hipStream_t st);
+// codes): the first m rows are the exclude rows; unique: repeats among the link rows are dropped too
+int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, bool unique, hipStream_t st);
 
 #define DDCHK(h, x)                                                                    \
     do {                                                                               \

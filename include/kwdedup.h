@@ -215,6 +215,48 @@ int kw_cdx_remaining_copy(kw_dedup *h, uint8_t *d_bytes, int64_t *d_off, int64_t
  * remaining rows' compaction; k <= 3 values. */
 int kw_cdx_exclude_last_ms(kw_dedup *h, float *ms, int32_t k);
 
+/* ---- the link list's refresh and split (experiental/drop.py, experiental/split.py): the set difference that also
+ * drops repeats, the survivors' timestamps as sort keys, and a renderer that writes them in a given order into
+ * several files
+ *
+ *   d = new[~new.url.isin(prev.url)].drop_duplicates('url')
+ *
+ * kw_cdx_run_exclude_unique is kw_cdx_run_exclude (the same layout: the first n_exclude store rows are the exclude
+ * rows, the rest the link rows) except that a link row whose first holder f is an earlier link row is dropped too:
+ * f < n_exclude -> KW_URL_SEEN, f == the row itself -> KW_URL_KEPT, else KW_URL_DUPLICATE.  The kept-rows buffers
+ * then hold the KEPT link rows, dense and in row order; kw_cdx_exclude_codes, kw_cdx_remaining_* and
+ * kw_cdx_exclude_last_ms describe this run as they describe kw_cdx_run_exclude, and so does kw_cdx_exclude_counts
+ * (link rows, seen, remaining = KEPT).  kw_cdx_exclude_duplicates gives the DUPLICATE rows (0 after
+ * kw_cdx_run_exclude). */
+int kw_cdx_run_exclude_unique(kw_dedup *h, int64_t n_exclude, void *stream);
+int kw_cdx_exclude_duplicates(kw_dedup *h, int64_t *n_duplicate);
+
+/* The "surviving rows" of the last run over the store are kw_cdx_run's kept rows, kw_cdx_run_exclude's remaining
+ * rows or kw_cdx_run_exclude_unique's KEPT rows: n of them (kw_dedup_kept_size), numbered in row order.  The three
+ * functions below are valid after any of the three runs, until the store changes or another run starts; otherwise
+ * KW_ESTATE.
+ *
+ * kw_cdx_selected_ts: their timestamps into d_ts (caller-owned device memory, n values), enqueued on `stream`. */
+int kw_cdx_selected_ts(kw_dedup *h, int64_t *d_ts, void *stream);
+
+/* Surviving rows rendered in a given order into n_seg files that lie back to back.  d_order (device): n_order
+ * indices among the surviving rows, any subset in any order, repeats allowed.  d_seg (device): n_seg + 1 ascending
+ * bounds into d_order, d_seg[0] = 0 and d_seg[n_seg] = n_order; file s is "date_time,url\n" followed by the lines
+ * of d_order[d_seg[s], d_seg[s + 1]), each decimal(timestamp), ',', the URL (wrapped in '"' when it contains ','),
+ * '\n' as kw_cdx_csv_* render a row.  An empty file is the header alone.  n_seg >= 1 unless n_order = 0.
+ *
+ * kw_cdx_csv_select_size checks every index (0 <= i < n) and every bound on the device before anything is read
+ * through them: a bad one returns KW_EINVAL with the first offender named in kw_dedup_last_error.  It writes the
+ * files' sizes to d_seg_bytes (device, n_seg values), gives their sum in *n_bytes and returns when both are final.
+ * kw_cdx_csv_select_copy writes the bytes of that call to d_out (16-byte aligned, *n_bytes) and returns when they
+ * are written.  Offsets are 64-bit throughout. */
+int kw_cdx_csv_select_size(kw_dedup *h, const int64_t *d_order, int64_t n_order, const int64_t *d_seg, int64_t n_seg,
+                           int64_t *d_seg_bytes, int64_t *n_bytes, void *stream);
+int kw_cdx_csv_select_copy(kw_dedup *h, uint8_t *d_out, void *stream);
+
+/* Device times (ms) of the last kw_cdx_csv_select_size [0] and kw_cdx_csv_select_copy [1]; k <= 2 values. */
+int kw_cdx_select_last_ms(kw_dedup *h, float *ms, int32_t k);
+
 #ifdef __cplusplus
 }
 #endif
