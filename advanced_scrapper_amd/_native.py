@@ -65,7 +65,8 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_ingest_zone', 'kw_ingest_stamps', 'kw_ingest_stamps_device', 'kw_rows_emit_stamps_device',
            'kw_sort_create', 'kw_sort_destroy', 'kw_sort_last_error', 'kw_sort_last_ms', 'kw_sort_keys',
            'kw_sort_gather', 'kw_sort_begin', 'kw_sort_window', 'kw_sort_finish', 'kw_sort_gather_begin',
-           'kw_sort_gather_slab')
+           'kw_sort_gather_slab',
+           'kw_sort_index_begin', 'kw_sort_index_stage', 'kw_sort_index_window', 'kw_sort_index_finish')
 
 # KW_CDX_* verdicts of kw_cdx_append (include/kwdedup.h)
 (KW_CDX_OK, KW_CDX_QUOTE, KW_CDX_CR, KW_CDX_NUL, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL, KW_CDX_UTF8,
@@ -91,6 +92,7 @@ KW_EMIT_OK, KW_EMIT_NUL = 0, 1             # verdicts of kw_rows_emit (include/k
  KW_INGEST_ROWS) = range(8)
 # KW_SORT_* verdicts of kw_sort_keys (include/kwsort.h), in the order they are tested
 KW_SORT_OK, KW_SORT_KEY, KW_SORT_FORM, KW_SORT_DTYPE = range(4)
+KW_INDEX_OK, KW_INDEX_TERM = 0, 1          # verdicts of kw_sort_index_finish (include/kwsort.h)
 KW_N_STATS = 21
 # KW_RESCAN_* bits of stats[20] (include/kwmatch.h)
 KW_RESCAN_GENERIC_ITEMS, KW_RESCAN_RESULTS, KW_RESCAN_GENERIC_CPS = 1, 2, 4
@@ -227,9 +229,14 @@ def lib() -> ctypes.CDLL:
                                  ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.kw_sort_gather_begin.argtypes = [vp, vp, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.kw_sort_gather_slab.argtypes = [vp, i64, ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.kw_sort_index_begin.argtypes = [vp, vp, i64, i64, ctypes.POINTER(i64)]
+    L.kw_sort_index_stage.argtypes = [vp, i32, i64, ctypes.POINTER(vp)]
+    L.kw_sort_index_window.argtypes = [vp, i32, i64, vp]
+    L.kw_sort_index_finish.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64)]
     for f in ('kw_ingest_spans', 'kw_ingest_copy_spans', 'kw_sort_create', 'kw_sort_destroy', 'kw_sort_keys',
               'kw_sort_gather', 'kw_sort_last_ms', 'kw_sort_begin', 'kw_sort_window', 'kw_sort_finish',
-              'kw_sort_gather_begin', 'kw_sort_gather_slab'):
+              'kw_sort_gather_begin', 'kw_sort_gather_slab', 'kw_sort_index_begin', 'kw_sort_index_stage',
+              'kw_sort_index_window', 'kw_sort_index_finish'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_sort_last_error.argtypes = [vp]
     L.kw_sort_last_error.restype = ctypes.c_char_p

@@ -25,6 +25,16 @@
 // witnesses stay on the device from window to window, in buffers that keep their contents when they grow.
 // kw_sort_gather_slab runs ks_copy_kernel over one slab's byte range of the scanned offsets; every position in
 // the store and in the output is 64-bit.
+//
+// A file described by its write index (kw_sort_index_begin / kw_sort_index_window / kw_sort_index_finish): the
+// records' lengths come from the host, nothing is parsed, and the route ends in the state a taken kw_sort_finish
+// leaves, in front of the same gather.
+//   ks_span_kernel      lane = record: its length (the terminator included), scanned inside a tile of 256 into rs;
+//                       a length below 1 or above the body offends.
+//   ks_span_add_kernel  lane = record: the sum of the tiles before its own (ks_scan_kernel) onto rs, re = the place
+//                       of its terminator; a record that ends beyond the body offends.
+//   ks_term_kernel      lane = record: the store's byte at re is '\n', or the index does not describe the body.
+// The body arrives through two pinned slots of the handle, one asynchronous copy a window behind the last one.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -49,6 +59,7 @@ struct Dev {
     u64 body_bytes;                           // the rows' bytes + 1 each
     u64 total;                                // kw_sort_gather: the body's bytes
     int not_asc, bad_order;
+    u64 first_len, first_term;                // the index route: the first row of a bad length, of a missing '\n' (NONE)
 };
 
 __device__ __forceinline__ u64 wave_min(u64 x)
@@ -227,6 +238,76 @@ __global__ __launch_bounds__(BLOCK) void ks_add_kernel(u64 *__restrict__ doff, l
     for (long long j = t; j < n; j += step) doff[j] += tsum[j / BLOCK];
 }
 
+// ---- the index route: the records' spans from their lengths, not from a parse
+// A tile = BLOCK records: each one's length (its terminator included), scanned inside the tile into rs; the tile's
+// sum to tsum[tile].  A length below 1 or above the body's bytes offends and counts 0.
+__global__ __launch_bounds__(BLOCK) void ks_span_kernel(const long long *__restrict__ lens, long long n, long long body,
+                                                        long long *__restrict__ rs, u64 *__restrict__ tsum,
+                                                        Dev *__restrict__ D)
+{
+    __shared__ u64 ws[BLOCK / 64];
+    const long long ntiles = (n + BLOCK - 1) / BLOCK;
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {   // (block-uniform trip count)
+        const long long j = tile * BLOCK + threadIdx.x;
+        u64 len = 0, bad = NONE;
+        if (j < n) {
+            const long long l = lens[j];
+            if (l < 1 || l > body) bad = (u64)j; else len = (u64)l;
+        }
+        if (__any(bad != NONE)) {   // (rare: one atomic a wave)
+            bad = wave_min(bad);
+            if ((threadIdx.x & 63) == 0) atomicMin(&D->first_len, bad);
+        }
+        u64 total;
+        const u64 before = block_scan(len, ws, &total);
+        if (j < n) rs[j] = (long long)before;
+        if (threadIdx.x == 0) tsum[tile] = total;
+    }
+}
+
+// rs[j] += the sum of the tiles before j's: the bytes before record j; re[j] = the place of its last byte, the
+// terminator.  A record that ends beyond the body offends: up to the first such row no sum has wrapped (every
+// length counted lies in [1, body]), so the first offender is exact and the rows before it lie inside the store.
+__global__ __launch_bounds__(BLOCK) void ks_span_add_kernel(const long long *__restrict__ lens, long long n,
+                                                            long long body, long long *__restrict__ rs,
+                                                            long long *__restrict__ re, const u64 *__restrict__ tsum,
+                                                            Dev *__restrict__ D)
+{
+    const long long rounds = (n + BLOCK - 1) / BLOCK;   // (every lane of a wave makes the same trips)
+    for (long long q = blockIdx.x; q < rounds; q += gridDim.x) {
+        const long long j = q * BLOCK + threadIdx.x;
+        u64 bad = NONE;
+        if (j < n) {
+            const long long l = lens[j];
+            const u64 s = (u64)rs[j] + tsum[q];
+            rs[j] = (long long)s;
+            re[j] = (long long)(s + (u64)l - 1ull);
+            if (l >= 1 && l <= body && s + (u64)l > (u64)body) bad = (u64)j;
+        }
+        if (__any(bad != NONE)) {
+            bad = wave_min(bad);
+            if ((threadIdx.x & 63) == 0) atomicMin(&D->first_len, bad);
+        }
+    }
+}
+
+// lane = record: the store's byte at the record's last place is its '\n', or the index does not describe the body
+__global__ __launch_bounds__(BLOCK) void ks_term_kernel(const uint8_t *__restrict__ store,
+                                                        const long long *__restrict__ re, long long n,
+                                                        Dev *__restrict__ D)
+{
+    const long long rounds = (n + BLOCK - 1) / BLOCK;   // (every lane of a wave makes the same trips)
+    for (long long q = blockIdx.x; q < rounds; q += gridDim.x) {
+        const long long j = q * BLOCK + threadIdx.x;
+        u64 bad = NONE;
+        if (j < n && store[re[j]] != 0x0A) bad = (u64)j;
+        if (__any(bad != NONE)) {   // (rare: one atomic a wave)
+            bad = wave_min(bad);
+            if ((threadIdx.x & 63) == 0) atomicMin(&D->first_term, bad);
+        }
+    }
+}
+
 typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));   // 16 bytes at any address
 
 // A lane's 16 bytes from out position x0 < total, its record among [lo, l2] (doff[lo] <= x0, the record of the
@@ -381,6 +462,13 @@ struct kw_sort {
     ks::Buf slab[2];
     void *h_slab[2] = {nullptr, nullptr};
     size_t h_slab_cap[2] = {0, 0};
+    // the index route (kw_sort_index_begin .. kw_sort_index_finish): two pinned staging slots, each one's copy to the
+    // store between its two events while `busy`; the records' lengths stand in `keys` until the spans are made
+    bool iopen = false;
+    void *h_stage[2] = {nullptr, nullptr};
+    size_t h_stage_cap[2] = {0, 0};
+    bool busy[2] = {false, false};
+    hipEvent_t wev[2][2] = {};
 };
 
 #define KSCHK(h, x)                                                                    \
@@ -488,6 +576,9 @@ extern "C" int kw_sort_create(int32_t device, kw_sort **out)
               hipHostMalloc((void **)&h->H, sizeof(Dev), hipHostMallocDefault) == hipSuccess;
     for (auto &e : h->ev)
         if (ok) ok = hipEventCreate(&e) == hipSuccess;
+    for (auto &s : h->wev)
+        for (auto &e : s)
+            if (ok) ok = hipEventCreate(&e) == hipSuccess;
     if (!ok) {
         kw_sort_destroy(h);
         return KW_EHIP;
@@ -510,8 +601,13 @@ extern "C" int kw_sort_destroy(kw_sort *h)
     if (h->H) (void)hipHostFree(h->H);
     if (h->h_keys) (void)hipHostFree(h->h_keys);
     if (h->h_out) (void)hipHostFree(h->h_out);
+    for (void *p : h->h_stage)
+        if (p) (void)hipHostFree(p);
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto &s : h->wev)
+        for (auto &e : s)
+            if (e) (void)hipEventDestroy(e);
     delete h;
     return KW_OK;
 }
@@ -523,7 +619,7 @@ static int reset_state(kw_sort *h, hipStream_t st)
 {
     Dev init;
     memset(&init, 0, sizeof(init));
-    init.first_key = init.first_form = init.first_dtype = NONE;
+    init.first_key = init.first_form = init.first_dtype = init.first_len = init.first_term = NONE;
     *h->H = init;   // (pinned: the copy below reads it in stream order; the last call's copy back has finished)
     KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
     return KW_OK;
@@ -572,7 +668,7 @@ extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t
                             int32_t *ascending, void *stream)
 {
     if (!h) return KW_EINVAL;
-    h->have = h->scanned = h->open = false;
+    h->have = h->scanned = h->open = h->iopen = false;
     if (!ig || !keys || !n_rows || !body_bytes || !verdict || !bad_row || !bad_col || !ascending || block_rows < 1) {
         h->err = "kw_sort_keys: bad arguments";
         return KW_EINVAL;
@@ -632,17 +728,12 @@ extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t
 }
 
 // ------------------------------------------------------------------ a file of several windows
-extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, int64_t expect_bytes)
+// The store of a file's body: expect_bytes and a lane's read past a record's end.  A store the handle has is kept
+// when it is large enough.  KW_EOVERFLOW, with nothing allocated: see kw_sort_begin (kwsort.h).
+static int reserve_store(kw_sort *h, int64_t expect_bytes, const char *who)
 {
-    if (!h) return KW_EINVAL;
-    h->have = h->scanned = h->open = false;
-    if (time_col < 0 || block_rows < 1 || expect_bytes < 1) {
-        h->err = "kw_sort_begin: bad arguments";
-        return KW_EINVAL;
-    }
-    KSCHK(h, hipSetDevice(h->device));
     if (expect_bytes > store_cap()) {
-        h->err = "kw_sort_begin: a store of " + std::to_string(expect_bytes) + " bytes is over the cap";
+        h->err = std::string(who) + ": a store of " + std::to_string(expect_bytes) + " bytes is over the cap";
         return KW_EOVERFLOW;
     }
     const size_t want = (size_t)expect_bytes + 64;   // (a lane's 16-byte load may read past a record's end)
@@ -654,7 +745,7 @@ extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, i
         KSCHK(h, hipMemGetInfo(&free_b, &total_b));
         const size_t need = want + want / 4 + ((size_t)64 << 20);
         if (need > free_b + h->store.cap) {
-            h->err = "kw_sort_begin: a store of " + std::to_string(expect_bytes) + " bytes does not fit in the " +
+            h->err = std::string(who) + ": a store of " + std::to_string(expect_bytes) + " bytes does not fit in the " +
                      std::to_string(free_b) + " free bytes of the device";
             return KW_EOVERFLOW;
         }
@@ -664,18 +755,31 @@ extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, i
         if (hipMalloc(&h->store.p, want) != hipSuccess) {
             (void)hipGetLastError();
             h->store.p = nullptr;
-            h->err = "kw_sort_begin: no device memory for a store of " + std::to_string(expect_bytes) + " bytes";
+            h->err = std::string(who) + ": no device memory for a store of " + std::to_string(expect_bytes) + " bytes";
             return KW_EOVERFLOW;
         }
         h->store.cap = want;
     }
+    return KW_OK;
+}
+
+extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, int64_t expect_bytes)
+{
+    if (!h) return KW_EINVAL;
+    h->have = h->scanned = h->open = h->iopen = false;
+    if (time_col < 0 || block_rows < 1 || expect_bytes < 1) {
+        h->err = "kw_sort_begin: bad arguments";
+        return KW_EINVAL;
+    }
+    KSCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = reserve_store(h, expect_bytes, "kw_sort_begin"))) return rc;
     h->time_col = time_col;
     h->block_rows = block_rows;
     h->expect = expect_bytes;
     h->used = h->rows = 0;
     h->ncols = 0;
     h->ms[0] = h->ms[1] = h->ms[2] = h->ms[3] = h->ms_keys_copy = 0;
-    int rc;
     if ((rc = reset_state(h, nullptr))) return rc;
     KSCHK(h, hipStreamSynchronize(nullptr));
     h->open = true;
@@ -796,6 +900,167 @@ extern "C" int kw_sort_finish(kw_sort *h, const int64_t **keys, int64_t *n_rows,
         h->re = (const int64_t *)h->sre.p;
         h->n_rows = n;
     }
+    return KW_OK;
+}
+
+// ------------------------------------------------------------------ a file described by its write index
+// the slot's copy to the store has finished: its time onto ms[3] (copies)
+static int settle_slot(kw_sort *h, int slot)
+{
+    if (!h->busy[slot]) return KW_OK;
+    h->busy[slot] = false;
+    KSCHK(h, hipEventSynchronize(h->wev[slot][1]));
+    float a = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->wev[slot][0], h->wev[slot][1]));
+    h->ms[3] += a;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_index_begin(kw_sort *h, const int64_t *lens, int64_t n_rows, int64_t body_bytes, int64_t *bad_row)
+{
+    if (!h) return KW_EINVAL;
+    h->have = h->scanned = h->open = h->iopen = false;
+    if (!lens || !bad_row || n_rows < 1 || body_bytes < 1) {
+        h->err = "kw_sort_index_begin: bad arguments";
+        return KW_EINVAL;
+    }
+    *bad_row = -1;
+    KSCHK(h, hipSetDevice(h->device));
+    int rc;
+    // (a slot whose copy into the last file's store is still under way: the store may be replaced below)
+    if ((rc = settle_slot(h, 0)) || (rc = settle_slot(h, 1))) return rc;
+    if ((rc = reserve_store(h, body_bytes, "kw_sort_index_begin"))) return rc;
+    const long long ntiles = (n_rows + BLOCK - 1) / BLOCK;
+    if ((rc = ensure(h, h->keys, (size_t)n_rows * 8)) || (rc = ensure(h, h->srs, (size_t)n_rows * 8)) ||
+        (rc = ensure(h, h->sre, (size_t)n_rows * 8)) || (rc = ensure(h, h->tsum, (size_t)ntiles * 8)))
+        return rc;
+    h->ms[0] = h->ms[1] = h->ms[2] = h->ms[3] = h->ms_keys_copy = 0;
+    hipStream_t st = nullptr;
+    const int gcap = grid_cap();
+    const long long *d_lens = (const long long *)h->keys.p;
+    KSCHK(h, hipEventRecord(h->ev[0], st));
+    if ((rc = reset_state(h, st))) return rc;
+    KSCHK(h, hipMemcpyAsync(h->keys.p, lens, (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
+    KSCHK(h, hipEventRecord(h->ev[1], st));
+    hipLaunchKernelGGL(ks_span_kernel, grid_for(n_rows, gcap), dim3(BLOCK), 0, st, d_lens, (long long)n_rows,
+                       (long long)body_bytes, (long long *)h->srs.p, (u64 *)h->tsum.p, h->D);
+    hipLaunchKernelGGL(ks_scan_kernel, dim3(1), dim3(BLOCK), 0, st, (u64 *)h->tsum.p, ntiles, &h->D->total);
+    hipLaunchKernelGGL(ks_span_add_kernel, grid_for(n_rows, gcap), dim3(BLOCK), 0, st, d_lens, (long long)n_rows,
+                       (long long)body_bytes, (long long *)h->srs.p, (long long *)h->sre.p, (const u64 *)h->tsum.p,
+                       h->D);
+    KSCHK(h, hipEventRecord(h->ev[2], st));
+    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    KSCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[1]));
+    KSCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[1], h->ev[2]));
+    const Dev &R = *h->H;
+    if (R.first_len != NONE || R.total != (u64)body_bytes) {
+        // (with no offender every length was counted and every record ends inside the body: the sum is short)
+        *bad_row = R.first_len != NONE ? (int64_t)R.first_len : n_rows;
+        h->err = "kw_sort_index_begin: row " + std::to_string(*bad_row) +
+                 (R.first_len == NONE       ? ": the lengths end before the body's " + std::to_string(body_bytes) + " bytes"
+                  : lens[*bad_row] < 1      ? ": a length below 1"
+                                            : ": the record ends beyond the body's " + std::to_string(body_bytes) + " bytes");
+        return KW_EINVAL;
+    }
+    h->expect = body_bytes;
+    h->used = 0;
+    h->rows = n_rows;
+    h->stream = st;
+    h->iopen = true;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_index_stage(kw_sort *h, int32_t slot, int64_t n_bytes, uint8_t **host)
+{
+    if (!h) return KW_EINVAL;
+    if (!host || slot < 0 || slot > 1 || n_bytes < 1) {
+        h->err = "kw_sort_index_stage: bad arguments";
+        return KW_EINVAL;
+    }
+    *host = nullptr;
+    KSCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = settle_slot(h, slot)) || (rc = ensure_pinned(h, &h->h_stage[slot], &h->h_stage_cap[slot], (size_t)n_bytes)))
+        return rc;
+    *host = (uint8_t *)h->h_stage[slot];
+    return KW_OK;
+}
+
+extern "C" int kw_sort_index_window(kw_sort *h, int32_t slot, int64_t n_bytes, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->iopen) {
+        h->err = "kw_sort_index_window: no kw_sort_index_begin";
+        return KW_ESTATE;
+    }
+    h->iopen = false;   // (an error below ends the file)
+    if (slot < 0 || slot > 1 || n_bytes < 1 || (size_t)n_bytes > h->h_stage_cap[slot] || !h->h_stage[slot]) {
+        h->err = "kw_sort_index_window: no such slot, or more bytes than it was staged for";
+        return KW_EINVAL;
+    }
+    if (n_bytes > h->expect - h->used) {
+        h->err = "kw_sort_index_window: the store holds " + std::to_string(h->used) + " of " +
+                 std::to_string(h->expect) + " bytes, the window has " + std::to_string(n_bytes);
+        return KW_EOVERFLOW;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    KSCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = settle_slot(h, slot))) return rc;
+    KSCHK(h, hipEventRecord(h->wev[slot][0], st));
+    KSCHK(h, hipMemcpyAsync((uint8_t *)h->store.p + h->used, h->h_stage[slot], (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    KSCHK(h, hipEventRecord(h->wev[slot][1], st));
+    h->busy[slot] = true;
+    h->used += n_bytes;
+    h->stream = st;
+    h->iopen = true;
+    return KW_OK;
+}
+
+extern "C" int kw_sort_index_finish(kw_sort *h, int32_t *verdict, int64_t *bad_row)
+{
+    if (!h) return KW_EINVAL;
+    if (!h->iopen || h->used != h->expect) {
+        h->err = !h->iopen ? std::string("kw_sort_index_finish: no kw_sort_index_begin")
+                           : "kw_sort_index_finish: the windows gave " + std::to_string(h->used) + " of the body's " +
+                                 std::to_string(h->expect) + " bytes";
+        h->iopen = false;
+        return KW_ESTATE;
+    }
+    h->iopen = false;
+    if (!verdict || !bad_row) {
+        h->err = "kw_sort_index_finish: bad arguments";
+        return KW_EINVAL;
+    }
+    *verdict = KW_INDEX_OK;
+    *bad_row = -1;
+    hipStream_t st = h->stream;
+    KSCHK(h, hipSetDevice(h->device));
+    KSCHK(h, hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(ks_term_kernel, grid_for(h->rows, grid_cap()), dim3(BLOCK), 0, st, (const uint8_t *)h->store.p,
+                       (const long long *)h->sre.p, h->rows, h->D);
+    KSCHK(h, hipEventRecord(h->ev[1], st));
+    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KSCHK(h, hipStreamSynchronize(st));
+    KSCHK(h, hipGetLastError());
+    int rc;
+    if ((rc = settle_slot(h, 0)) || (rc = settle_slot(h, 1))) return rc;
+    float a = 0;
+    KSCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    h->ms[0] += a;
+    h->ms_keys_copy = h->ms[3];
+    if (h->H->first_term != NONE) {
+        *verdict = KW_INDEX_TERM;
+        *bad_row = (int64_t)h->H->first_term;
+        return KW_OK;
+    }
+    h->have = true;
+    h->text = (const uint8_t *)h->store.p;
+    h->rs = (const int64_t *)h->srs.p;
+    h->re = (const int64_t *)h->sre.p;
+    h->n_rows = h->rows;
     return KW_OK;
 }
 

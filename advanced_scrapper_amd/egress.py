@@ -201,6 +201,9 @@ class RunFiles:
     cell holds a lone '\\r'), the sorted file is the written records in ``np.argsort(time_unix,
     kind='quicksort')`` order -- the records already in that order (ascending, no ties) mean no rewrite at
     all.  Other files (pre-existing ones, those a row went to by another path) take sort_matched_csv.
+    A file that has to be rewritten goes to the device with the index's lengths and that order
+    (sortfiles.DeviceSorter.sort_indexed: no parse, the sort's gather); ``KW_FINISH_DEVICE=0``, ``--gpus N``, a
+    process without a device or the library, and a file that route refuses keep the host branch of :meth:`finish`.
 
     Under ``--gpus N`` every rank appends its share of each chunk in rank order: each append is keyed
     ``(chunk's first row, rank)``, the ranks' indexes of a file meet at the rank that sorts it
@@ -211,6 +214,9 @@ class RunFiles:
         self.pre = set(os.listdir(out_dir)) if os.path.isdir(out_dir) else set()
         self.files = {}          # name -> [[(key, stamps, lengths, flags), ...], header bytes]
         self.other = set()       # names written by another path
+        self.device = None       # the HIP device of the rewrite's device route (None: 0)
+        self._next = {}          # plan(): a name -> the name finish() is called with after it
+        self._ahead = {}         # decisions made ahead of a name's own turn
 
     def owned(self, name: str) -> bool:
         return name not in self.pre and name not in self.other
@@ -241,8 +247,15 @@ class RunFiles:
                 f = self.files[n] = [[], header]
             f[0].extend(entries)
 
-    def finish(self, name: str) -> bool:
-        """Sort one indexed file as the reference's sort_matched_csv does; False = not decidable here."""
+    def plan(self, names) -> None:
+        """The names :meth:`finish` is called with next, in order: while one file is on the device the next one
+        that needs a rewrite is read ahead (the idea of sortfiles.plan)."""
+        names = list(names)
+        self._next = dict(zip(names, names[1:]))
+
+    def _decide(self, name: str):
+        """What :meth:`finish` does with ``name``, from the index alone: ``False`` (not decidable here), ``True``
+        (the records stand in order: no rewrite, no read) or ``(path, header, lens, order)`` of a rewrite."""
         if not self.owned(name) or name not in self.files:
             return False
         entries, header = self.files[name]
@@ -265,15 +278,52 @@ class RunFiles:
         if n > 1 and not (np.diff(stamps) > 0).all():
             order = np.argsort(stamps, kind='quicksort')
             if not (order == np.arange(n)).all():
-                with open(path, 'rb') as fh:
-                    data = fh.read()
-                ends = len(header) + np.cumsum(lens)
-                starts = ends - lens
-                mv = memoryview(data)
-                body = b''.join([mv[s:e] for s, e in zip(starts[order].tolist(), ends[order].tolist())])
-                with open(path, 'wb') as fh:
-                    fh.write(data[:len(header)])
-                    fh.write(body)
+                return path, header, lens, order
+        return True
+
+    def _decided(self, name: str):
+        got = self._ahead.pop(name, None)
+        return self._decide(name) if got is None else got
+
+    def _rewrite_on_device(self, name: str, path: str, header: bytes, lens, order) -> bool:
+        """The rewrite on the device (sortfiles.DeviceSorter.sort_indexed); ``False``: the host branch takes it --
+        the route is switched off (``KW_FINISH_DEVICE=0``), this thread keeps to the host (--gpus N), there is no
+        device or no library, or the route refused the file, untouched."""
+        from . import sortfiles
+        if not sortfiles.finish_on_device() or getattr(sortfiles.HOST_ONLY, 'on', False):
+            return False
+        sorter = sortfiles.sorter(self.device)
+        if sorter is None:
+            return False
+        # the next file that needs a rewrite (decided now, kept for its own turn): its first window is read ahead
+        nxt, ahead = self._next.get(name), None
+        while nxt is not None:
+            d = self._ahead[nxt] = self._decided(nxt)
+            if isinstance(d, tuple):
+                ahead = (d[0], len(d[1]), int(d[2].sum()))
+                break
+            nxt = self._next.get(nxt)
+        return sorter.sort_indexed(path, len(header), lens, order, ahead)
+
+    def finish(self, name: str) -> bool:
+        """Sort one indexed file as the reference's sort_matched_csv does; False = not decidable here."""
+        d = self._decided(name)
+        if not isinstance(d, tuple):
+            return d
+        path, header, lens, order = d
+        if self._rewrite_on_device(name, path, header, lens, order):
+            return True
+        with open(path, 'rb') as fh:
+            data = fh.read()
+        ends = len(header) + np.cumsum(lens)
+        starts = ends - lens
+        mv = memoryview(data)
+        body = b''.join([mv[s:e] for s, e in zip(starts[order].tolist(), ends[order].tolist())])
+        with open(path, 'wb') as fh:
+            fh.write(data[:len(header)])
+            fh.write(body)
+        from . import sortfiles
+        sortfiles.LAST_STATS['index_host'] += 1
         return True
 
 

@@ -639,7 +639,7 @@ def _sort_host(file_path):
 
 
 # run()'s sharded form (--gpus N) keeps every file on the host routes: set on the thread that runs that loop only
-_SORT_HOST_ONLY = threading.local()
+_SORT_HOST_ONLY = sortfiles.HOST_ONLY
 
 
 def sort_matched_csv(file_path):
@@ -813,13 +813,18 @@ def run(args, rank: int, world: int, device, backend, matcher=None):
         print("All matched CSV files have been processed.")
         sortfiles.reset_stats()
         rest = []
-        for name in os.listdir(out_dir):
+        names = os.listdir(out_dir)
+        _RUN.device = device
+        _RUN.plan(names)                       # (the device route reads the next file it rewrites ahead)
+        t0 = time.perf_counter()
+        for name in names:
             # the files this run created are sorted from their write index (no re-read when already in
             # time order); the others take the reference's re-read, sort and rewrite
             if _RUN.finish(name):
                 print(f"Sorted and saved: {out_dir}/{name}")
             else:
                 rest.append(f"{out_dir}/{name}")
+        sortfiles.LAST_STATS['finish_s'] = time.perf_counter() - t0
         # one sorter for all of them: it knows the files to come and reads the next one while this one is on
         # the device
         t0 = time.perf_counter()

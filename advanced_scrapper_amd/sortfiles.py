@@ -19,12 +19,19 @@ free memory does not hold (``'memory'``) are refused for their size.
 ``native`` and ``pandas``: the host routes, noted by ``match_keywords.sort_matched_csv``), the refusals by
 reason, the bytes the device route took, its summed device times, and the ``windows`` and ``slabs`` of the
 files that went in pieces.
+
+``DeviceSorter.sort_indexed`` is the way in for the files a run wrote itself (egress.RunFiles.finish): their
+records' lengths are known from the write index and the order is decided on the host, so the body goes to the
+store unparsed (``kw_sort_index_begin`` / ``_window`` / ``_finish``) and the same gather lays it out.
+``LAST_STATS`` counts those files under ``indexed`` (``index_host``: rewritten by the host branch instead) and
+adds their bytes, windows, slabs and times to the entries above.
 """
 from __future__ import annotations
 
 import atexit
 import ctypes
 import os
+import threading
 import time
 from typing import Dict, Optional
 
@@ -33,6 +40,7 @@ import numpy as np
 from . import egress, ingest
 
 SORT_DEVICE_DEFAULT = '1'
+FINISH_DEVICE_DEFAULT = '1'
 _HEAD_PROBE = 1 << 16              # the header line lies within the file's first bytes, or the file is refused
 INGEST_VERDICTS = ('OK', 'NUL', 'UTF8', 'QUOTE', 'CR', 'BLANK', 'FIELDS', 'ROWS')
 SORT_VERDICTS = ('OK', 'KEY', 'FORM', 'DTYPE')
@@ -44,7 +52,8 @@ HEADROOM = 1 << 20                 # the bytes kept free before a window that is
 
 
 def _new_stats() -> dict:
-    return {'device': 0, 'unchanged': 0, 'native': 0, 'pandas': 0, 'refused': {}, 'bytes': 0, 'gather_bytes': 0,
+    return {'device': 0, 'unchanged': 0, 'native': 0, 'pandas': 0, 'indexed': 0, 'index_host': 0, 'refused': {}, 'bytes': 0,
+            'gather_bytes': 0,
             'prefetched': 0, 'windows': 0, 'slabs': 0,
             'ms': {'parse': 0.0, 'keys': 0.0, 'scan': 0.0, 'gather': 0.0, 'copies': 0.0},
             'wall_s': {'read': 0.0, 'device': 0.0, 'argsort': 0.0, 'write': 0.0}, 'last': None}
@@ -68,6 +77,16 @@ def sort_on_device() -> bool:
     """``KW_SORT_DEVICE=0`` keeps every file on the host routes; ``KW_SORT_DEVICE=1`` asks for the device route
     (profiles/e2e_sort.json holds the measurement behind the default)."""
     return os.environ.get('KW_SORT_DEVICE', SORT_DEVICE_DEFAULT) != '0'
+
+
+def finish_on_device() -> bool:
+    """``KW_FINISH_DEVICE=0`` keeps the rewrite of a run's own files (egress.RunFiles.finish) on the host;
+    profiles/e2e_finish.json holds the measurement behind the default."""
+    return os.environ.get('KW_FINISH_DEVICE', FINISH_DEVICE_DEFAULT) != '0'
+
+
+# set (``.on = True``) on a thread whose files stay on the host routes: run()'s sharded form (--gpus N)
+HOST_ONLY = threading.local()
 
 
 class Refusal(Exception):
@@ -202,6 +221,7 @@ class DeviceSorter:
         self._ingests: Dict[tuple, ingest.DeviceIngest] = {}
         self._slot: Dict[tuple, int] = {}
         self._ahead: Optional[_Job] = None
+        self._index_ahead = None       # (path, header bytes, body bytes, slot, bytes read, future): sort_indexed's next file
         self._pool = None
         h = ctypes.c_void_p()
         rc = _native.lib().kw_sort_create(self.device, ctypes.byref(h))
@@ -482,10 +502,20 @@ class DeviceSorter:
             return True
         if order is None:
             order = np.arange(len(keys), dtype=np.int64)
-        total, slabs = self.gather_begin(order, self.slab_bytes)
-        # slab by slab into a sibling file that takes the target's place after the last one
+        total, slabs, t_write = self._write_slabs(path, head, order)
+        t3 = time.perf_counter()
+        self._account(stats, ms, nbody, t0, t1, t2, t3 - t_write, 'device')
+        stats['slabs'] += slabs
+        stats['gather_bytes'] += total
+        stats['wall_s']['write'] += t_write
+        return True
+
+    def _write_slabs(self, path: str, head: bytes, order):
+        """``head`` and the body in ``order``, slab by slab, into a sibling file that carries the target's mode and
+        takes its place after the last slab (removed on any failure): ``(body bytes, slabs, seconds writing)``."""
         import stat
         import tempfile
+        total, slabs = self.gather_begin(order, self.slab_bytes)
         mode = stat.S_IMODE(os.stat(path).st_mode)
         fd, tmp = tempfile.mkstemp(prefix='.' + os.path.basename(path) + '.', suffix='.tmp',
                                    dir=os.path.dirname(os.path.abspath(path)))
@@ -506,11 +536,148 @@ class DeviceSorter:
             except OSError:
                 pass
             raise
+        return total, slabs, t_write
+
+    # ------------------------------------------------------------------ a file described by its write index
+    def index_begin(self, lens, body_bytes: int) -> None:
+        """kw_sort_index_begin; ``Refusal('memory')`` where the store does not fit."""
+        lens = np.ascontiguousarray(lens, dtype=np.int64)
+        bad = ctypes.c_int64()
+        rc = self._n.lib().kw_sort_index_begin(self.h, self._n.ptr(lens), len(lens), int(body_bytes), ctypes.byref(bad))
+        if rc == self._n.KW_EOVERFLOW:
+            raise Refusal('memory')
+        self._check(rc)
+
+    def index_stage(self, slot: int, n_bytes: int) -> np.ndarray:
+        """kw_sort_index_stage: the slot's first ``n_bytes`` as a uint8 view, free to be filled."""
+        p = ctypes.c_void_p()
+        self._check(self._n.lib().kw_sort_index_stage(self.h, int(slot), int(n_bytes), ctypes.byref(p)))
+        return np.frombuffer((ctypes.c_uint8 * int(n_bytes)).from_address(p.value), dtype=np.uint8)
+
+    def index_window(self, slot: int, n_bytes: int) -> None:
+        self._check(self._n.lib().kw_sort_index_window(self.h, int(slot), int(n_bytes), None))
+
+    def index_finish(self):
+        """kw_sort_index_finish: ``(verdict, bad_row)``."""
+        v, bad = ctypes.c_int32(), ctypes.c_int64()
+        self._check(self._n.lib().kw_sort_index_finish(self.h, ctypes.byref(v), ctypes.byref(bad)))
+        return int(v.value), int(bad.value)
+
+    @staticmethod
+    def _fill(path: str, at: int, view: np.ndarray) -> float:
+        """The file's bytes from ``at`` into ``view`` (runs on the reader thread: no device call); the seconds."""
+        t0 = time.perf_counter()
+        mv, got = memoryview(view), 0
+        with open(path, 'rb', buffering=0) as fh:
+            while got < len(mv):
+                r = os.preadv(fh.fileno(), [mv[got:]], at + got)
+                if not r:
+                    raise OSError(f'{path}: the file shrank while it was read')
+                got += r
+        return time.perf_counter() - t0
+
+    def _drop_index_ahead(self):
+        job, self._index_ahead = self._index_ahead, None
+        if job is not None:
+            try:
+                job[-1].result()
+            except Exception:   # noqa: BLE001 - that file is read again when its turn comes
+                pass
+
+    def sort_indexed(self, path: str, header_len: int, lens, order, next_file=None) -> bool:
+        """Rewrite ``path`` -- ``header_len`` bytes of header, then records of ``lens`` bytes each, the terminator
+        included -- with its records in ``order``, the header as the file holds it.  The caller has decided that
+        this is the sorted file (egress.RunFiles.finish): nothing is parsed.  The body is read through the sort
+        handle's two pinned slots, one filled by the reader thread while the other is uploaded.  A body below
+        ``large_from`` that one window holds is gathered whole and written in place, the file opened for writing
+        only when the whole result is on the host; any other body comes back in slabs, into a sibling temporary
+        file that takes the target's place after the last one.  ``next_file``: ``(path, header_len, body bytes)``
+        of the file that comes next, whose first window is read while this one is on the device.
+
+        ``False`` (the file untouched): refused -- ``'memory'`` (the store does not fit the device) or
+        ``'index-TERM'`` (a record of the index does not end with a line end in the file).  A ``KW_E*`` error
+        raises ``KwError``, the file untouched."""
+        stats, n = LAST_STATS, self._n
+        lens = np.ascontiguousarray(lens, dtype=np.int64)
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        nbody = int(lens.sum())
+        if self._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='kw-sort')
+        W = self.window_bytes
+        t0 = time.perf_counter()
+        ahead = self._index_ahead
+        if ahead is not None and ahead[:3] == (path, header_len, nbody):
+            self._index_ahead = None
+            stats['prefetched'] += 1
+            slot, k, fut = ahead[3:]
+        else:
+            self._drop_index_ahead()
+            slot, k = 0, min(W, nbody)
+            fut = None
+        read_s, windows = 0.0, 0
+        try:
+            try:
+                self.index_begin(lens, nbody)
+            except Refusal as r:
+                return self._refuse(r.reason)
+            with open(path, 'rb') as fh:
+                head = fh.read(header_len)
+            if fut is None:
+                fut = self._pool.submit(self._fill, path, header_len, self.index_stage(slot, k))
+            pos = 0
+            while True:
+                read_s += fut.result()
+                fut = None
+                self.index_window(slot, k)       # (asynchronous: the next read runs beside it)
+                windows += 1
+                pos += k
+                if pos == nbody:
+                    break
+                slot, k = 1 - slot, min(W, nbody - pos)
+                fut = self._pool.submit(self._fill, path, header_len + pos, self.index_stage(slot, k))
+            # the next file's first window, into the slot this file's last window left free
+            if next_file is not None:
+                try:
+                    npath, nhead, nbytes = next_file
+                    m = min(W, int(nbytes))
+                    view = self.index_stage(1 - slot, m)
+                    self._index_ahead = (npath, nhead, int(nbytes), 1 - slot, m,
+                                         self._pool.submit(self._fill, npath, nhead, view))
+                except OSError:   # (that file's own turn reports it)
+                    self._index_ahead = None
+            verdict, _bad = self.index_finish()
+        finally:
+            if fut is not None:   # (an error left a read under way)
+                try:
+                    fut.result()
+                except Exception:   # noqa: BLE001 - the route is leaving
+                    pass
+        stats['wall_s']['read'] += read_s
+        if verdict != n.KW_INDEX_OK:
+            return self._refuse('index-TERM')
+        slabs = 0
+        if nbody < self.large_from and nbody <= W:
+            out = self.gather(order)
+            t2 = time.perf_counter()
+            # (the whole body is on the host: only now is the file opened for writing)
+            with open(path, 'wb') as fh:
+                fh.write(head)
+                fh.write(out)
+            total, t_write = len(out), time.perf_counter() - t2
+        else:
+            total, slabs, t_write = self._write_slabs(path, head, order)
         t3 = time.perf_counter()
-        self._account(stats, ms, nbody, t0, t1, t2, t3 - t_write, 'device')
+        stats['indexed'] += 1
+        stats['bytes'] += nbody
+        stats['windows'] += windows
         stats['slabs'] += slabs
         stats['gather_bytes'] += total
+        for name, v in self.last_ms().items():
+            stats['ms'][name] += v
+        stats['wall_s']['device'] += (t3 - t0) - read_s - t_write
         stats['wall_s']['write'] += t_write
+        stats['last'] = {'verdict': 'OK', 'route': 'indexed'}
         return True
 
     def _account(self, stats, parse_ms, nbody, t0, t1, t2, t3, route):
@@ -533,6 +700,7 @@ class DeviceSorter:
 
     def close(self):
         self._drop_ahead()
+        self._drop_index_ahead()
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None

@@ -98,6 +98,43 @@ int kw_sort_window(kw_sort *h, kw_ingest *ig, int64_t consumed, void *stream);
 int kw_sort_finish(kw_sort *h, const int64_t **keys, int64_t *n_rows, int64_t *body_bytes, int32_t *verdict,
                    int64_t *bad_row, int32_t *bad_col, int32_t *ascending);
 
+/* ---- a file described by its write index ---------------------------------------------------------------------
+ * A run that wrote a file itself holds every record's length (egress.RunFiles) and has decided on the host that
+ * the sorted file is a permutation of the written records: such a body needs no parse and no take rule, only the
+ * records' places.  This route ends in the state a taken kw_sort_finish leaves -- the body in the store, the
+ * records' spans, n_rows -- so kw_sort_gather, kw_sort_gather_begin and kw_sort_gather_slab follow it unchanged.
+ * It needs no kw_ingest handle: the body comes through two pinned staging slots of the sort handle.
+ *
+ * kw_sort_index_begin: lens[i] >= 1 is record i's bytes in the body, its terminator included (a host array of
+ * n_rows >= 1 entries); body_bytes >= 1 their sum.  Reserves the store by kw_sort_begin's rule (KW_EOVERFLOW as
+ * there, nothing allocated), uploads lens and computes on the device, from their 64-bit exclusive scan, the spans
+ * rs[i] = the bytes before record i and re[i] = rs[i] + lens[i] - 1, the place of the terminator (which the copy
+ * kernel writes itself).  KW_EINVAL, with *bad_row and the message naming the row: the first row whose length is
+ * below 1 or which ends beyond body_bytes; n_rows when the lengths end before body_bytes.  Returns after the
+ * device finished. */
+#define KW_INDEX_OK 0
+#define KW_INDEX_TERM 1
+int kw_sort_index_begin(kw_sort *h, const int64_t *lens, int64_t n_rows, int64_t body_bytes, int64_t *bad_row);
+
+/* *host: staging slot `slot` (0 or 1), pinned, of n_bytes at least (a slot that grows does not keep its
+ * contents).  Waits for the slot's last kw_sort_index_window copy first: the caller may fill the slot when the
+ * call returns, from any thread.  Valid until the next call for that slot with a larger size, or the destroy. */
+int kw_sort_index_stage(kw_sort *h, int32_t slot, int64_t n_bytes, uint8_t **host);
+
+/* The slot's first n_bytes go to the store, behind the bytes the windows before gave.  A window ends anywhere, in
+ * the middle of a record too: nothing is parsed.  The copy is asynchronous on `stream`: the other slot may be
+ * filled meanwhile, and kw_sort_index_stage for this slot waits for it.  KW_EOVERFLOW: more bytes than
+ * body_bytes.  An error ends the file. */
+int kw_sort_index_window(kw_sort *h, int32_t slot, int64_t n_bytes, void *stream);
+
+/* After the last window.  KW_ESTATE: the windows gave another number of bytes than body_bytes.  Else, one lane a
+ * record, the store's byte at re[i] must be '\n': *verdict is KW_INDEX_OK, and the handle stands as after a taken
+ * kw_sort_finish; or KW_INDEX_TERM with *bad_row the first record that does not end so -- the index does not
+ * describe the file, a refusal and no error, after which no gather is possible (KW_ESTATE).  Returns after the
+ * device finished.  kw_sort_last_ms: the spans and this check under [0] keys, lens and the windows under [3]
+ * copies. */
+int kw_sort_index_finish(kw_sort *h, int32_t *verdict, int64_t *bad_row);
+
 /* ---- the output in slabs -------------------------------------------------------------------------------------
  * After a taken kw_sort_keys or kw_sort_finish: kw_sort_gather's range check, lengths and scan for `order`
  * (n entries), and nothing copied.  slab_bytes: a positive multiple of 1024, below 2^31.  *total_bytes: the

@@ -51,6 +51,15 @@ run, the configurations in turn (one warm-up each, then the median and range of 
 and, with ``--parent-tree DIR``, that tree.  OUT.json gets the medians and ranges, the wall time of the final sort
 loop on each route, the ``kw_sort_last_ms`` sums, the parse and gather rates, the gather kernel's share of the HBM
 peak, the route counts, and which route the standing rule makes the default.
+
+``--finish-ab OUT.json`` compares the routes by which a first ``main()`` finishes the files it wrote itself
+(egress.RunFiles.finish) when the articles' dates do not follow the articles: N articles written newest first, and
+the same N with ``date_perm`` dates.  A fresh child per run, the configurations in turn (one warm-up each, then the
+median and range of 5): this tree (the rewrite on the device from the write index), this tree with
+``KW_FINISH_DEVICE=0`` (the host branch) and, with ``--parent-tree DIR``, that tree.  OUT.json gets the whole run's
+wall time and the wall time inside ``RunFiles.finish``, the files by route, the ``kw_sort_last_ms`` sums, the
+process's peak resident size, and which route the standing rule makes the default; then the ascending corpus on this
+tree and the parent, where the finish loop must make no device call.
 """
 import argparse
 import contextlib
@@ -410,6 +419,47 @@ print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span
 '''
 
 
+FINISH_CHILD = r'''
+import contextlib, hashlib, io, json, os, resource, shutil, sys, tempfile, time
+tree, info_dir, csv_path, chunksize = sys.argv[1:5]
+sys.path.insert(0, tree)
+os.environ.setdefault('TZ', 'UTC')
+time.tzset()
+from advanced_scrapper_amd import egress, match_keywords as mk
+span = {'finish_calls': 0, 'finish_s': 0.0}
+inner = egress.RunFiles.finish
+def timed_finish(self, name):
+    t = time.perf_counter()
+    out = inner(self, name)
+    span['finish_s'] += time.perf_counter() - t
+    span['finish_calls'] += 1
+    return out
+egress.RunFiles.finish = timed_finish
+work = tempfile.mkdtemp(prefix='e2e_finish_')
+os.chdir(work)
+t0 = time.perf_counter()
+with contextlib.redirect_stdout(io.StringIO()) as log:
+    rc = mk.main(['--info-dir', info_dir, '--articles', csv_path, '--chunksize', chunksize, '--device', '0'])
+total = time.perf_counter() - t0
+assert rc == 0 and 'Error processing' not in log.getvalue()
+span['maxrss_kib'] = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss
+st = sys.modules['advanced_scrapper_amd.sortfiles'].LAST_STATS
+span['stats'] = {k: st[k] for k in ('device', 'unchanged', 'native', 'pandas', 'indexed', 'index_host', 'refused', 'bytes',
+                                    'gather_bytes', 'prefetched', 'windows', 'slabs', 'ms', 'wall_s') if k in st}
+out = os.path.join(work, 'yahoo_ticker_matched_articles')
+span['files'] = len(os.listdir(out))
+span['out_bytes'] = sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out))
+h = hashlib.sha256()
+for fn in sorted(os.listdir(out)):
+    h.update(fn.encode())
+    with open(os.path.join(out, fn), 'rb') as fh:
+        h.update(fh.read())
+os.chdir(tree)
+shutil.rmtree(work, ignore_errors=True)
+print('E2E_ROWS ' + json.dumps({'seconds': total, 'sha256': h.hexdigest(), 'span': span}))
+'''
+
+
 def rows_config(tree, env_extra, info_dir, csv_path, chunksize, runs, child=ROWS_CHILD, span_runs=()):
     """main() in a fresh child per run on ``tree``: one warm-up, then ``runs`` timed runs."""
     import statistics
@@ -733,8 +783,78 @@ def sort_ab(args):
     assert res['same_bytes'], 'the configurations wrote different bytes'
 
 
+def finish_ab(args):
+    import math
+    import statistics
+    import bench
+    from advanced_scrapper_amd import synth
+    from advanced_scrapper_amd.kb import compile_kb
+    work = tempfile.mkdtemp(prefix='e2e_')
+    info_dir = os.path.join(work, 'ticker')
+    processed = bench.load_kb(info_dir)
+    names, kinds = synth.injectable_names(compile_kb(processed))
+    corpus = synth.generate(args.docs, names, kinds, seed=20250905, doc_base=0)
+    mult = 3_000_017
+    while math.gcd(mult, args.docs) != 1:
+        mult += 2
+    csvs = {k: os.path.join(work, f'articles_{k}.csv') for k in ('newest_first', 'date_perm', 'ascending')}
+    frame = synth.to_dataframe(corpus)
+    frame.to_csv(csvs['ascending'], index=False)
+    frame.iloc[::-1].to_csv(csvs['newest_first'], index=False)
+    del frame
+    synth.to_dataframe(corpus, span_docs=args.docs, date_perm=(mult, 123_457 % args.docs)).to_csv(csvs['date_perm'],
+                                                                                                 index=False)
+    del corpus
+    parent = os.path.abspath(args.parent_tree) if args.parent_tree else None
+    res = {'docs': args.docs, 'chunksize': args.chunksize, 'runs_per_config': args.runs,
+           'date_perm': [mult, 123_457 % args.docs], 'csv_bytes': {k: os.path.getsize(v) for k, v in csvs.items()},
+           'timed': 'a first match_keywords.main() into an empty directory, wall time in a fresh child per run; 1 warm-up '
+                    '+ the median of the runs, the configurations in turn in one call; finish_s: the wall time inside '
+                    'egress.RunFiles.finish summed over the files (per timed run in finish_s_runs); cells.stats: '
+                    'sortfiles.LAST_STATS of the median run (indexed: files rewritten on the device from the write '
+                    'index, index_host: by the host branch; ms: kw_sort_last_ms summed over the files); maxrss_kib: '
+                    'the process\'s peak resident size'}
+
+    def config(tree, env, csv_path):
+        out = rows_config(tree, env, info_dir, csv_path, args.chunksize, args.runs, FINISH_CHILD, ('finish_s',))
+        out['finish_median_s'] = statistics.median(out['finish_s_runs'])
+        out['finish_range_s'] = [min(out['finish_s_runs']), max(out['finish_s_runs'])]
+        print('finish-ab', os.path.basename(csv_path), os.path.relpath(tree, REPO), env, round(out['median_s'], 3),
+              round(out['finish_median_s'], 3), file=sys.stderr, flush=True)
+        return out
+
+    try:
+        for k in ('newest_first', 'date_perm'):
+            r = res[k] = {}
+            r['device'] = config(REPO, {'KW_FINISH_DEVICE': '1'}, csvs[k])
+            r['host'] = config(REPO, {'KW_FINISH_DEVICE': '0'}, csvs[k])
+            if parent:
+                r['parent'] = config(parent, {}, csvs[k])
+            r['same_bytes'] = len({v['sha256'] for v in r.values()}) == 1
+            r['device_faster'] = r['device']['finish_median_s'] < r['host']['finish_median_s']
+        a = res['ascending'] = {}
+        a['device'] = config(REPO, {'KW_FINISH_DEVICE': '1'}, csvs['ascending'])
+        if parent:
+            a['parent'] = config(parent, {}, csvs['ascending'])
+            a['inside_parent_spread'] = a['parent']['min_s'] <= a['device']['median_s'] <= a['parent']['max_s']
+        a['same_bytes'] = len({v['sha256'] for v in a.values() if isinstance(v, dict)}) == 1
+        a['device_calls'] = a['device']['cells']['stats']['indexed']
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    res['device_faster_on_both'] = res['newest_first']['device_faster'] and res['date_perm']['device_faster']
+    res['default'] = 'device' if res['device_faster_on_both'] else 'host (the device route behind KW_FINISH_DEVICE=1)'
+    with open(args.finish_ab, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res), flush=True)
+    assert res['newest_first']['same_bytes'] and res['date_perm']['same_bytes'] and res['ascending']['same_bytes'], \
+        'the configurations wrote different bytes'
+    assert res['ascending']['device_calls'] == 0, 'the ascending corpus made a device call in the finish loop'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--finish-ab', metavar='OUT.json', help='compare the routes that finish a run\'s own files (see the module doc)')
     ap.add_argument('--sort-ab', metavar='OUT.json', help='compare the final sort\'s routes on a re-run (see the module doc)')
     ap.add_argument('--ingest-ab', metavar='OUT.json', help='compare the article ingest\'s routes (see the module doc)')
     ap.add_argument('--tz-ab', metavar='OUT.json', help='compare the time_unix routes in a zone that is not UTC (see the module doc)')
@@ -767,6 +887,9 @@ def main():
     if args.sort_ab:
         args.sort_ab = os.path.abspath(args.sort_ab)
         return sort_ab(args)
+    if args.finish_ab:
+        args.finish_ab = os.path.abspath(args.finish_ab)
+        return finish_ab(args)
     import bench
     from advanced_scrapper_amd import ingest, match_keywords as mk, synth
     from advanced_scrapper_amd.kb import compile_kb
