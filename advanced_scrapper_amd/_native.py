@@ -39,7 +39,8 @@ HIT_DTYPE = np.dtype([('doc', '<u4'), ('pattern', '<u4'), ('pos', '<u4'), ('fiel
 
 # every symbol include/kwmatch.h, include/kwdedup.h, include/kwrows.h, include/kwingest.h and include/kwsort.h declare
 EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_last_kernel_ms',
-           'kw_last_kernel_times', 'kw_doc_routes', 'kw_scan_counts', 'kw_last_error', 'kw_destroy',
+           'kw_last_kernel_times', 'kw_doc_routes', 'kw_scan_counts', 'kw_filter_variant', 'kw_last_error',
+           'kw_destroy',
            'kw_scan_host', 'kw_hits_host', 'kw_device_count', 'kw_device_init',
            'kw_comm_unique_id', 'kw_comm_init', 'kw_allgather_counts', 'kw_allgather_hits',
            'kw_allgather_hits_planned', 'kw_exchange_plan', 'kw_exchange_caps_ok', 'kw_comm_last_error',
@@ -259,6 +260,9 @@ def lib() -> ctypes.CDLL:
     L.kw_last_kernel_times.restype = ctypes.c_int
     L.kw_doc_routes.argtypes = [vp, vp, i64]
     L.kw_doc_routes.restype = ctypes.c_int
+    if hasattr(L, 'kw_filter_variant'):   # (as kw_scan_counts below)
+        L.kw_filter_variant.argtypes = [vp, vp]
+        L.kw_filter_variant.restype = ctypes.c_int
     if hasattr(L, 'kw_scan_counts'):   # (a tuning variant built from an earlier tree, for an A/B, has none)
         L.kw_scan_counts.argtypes = [vp, vp, i64, vp, i32]
         L.kw_scan_counts.restype = ctypes.c_int

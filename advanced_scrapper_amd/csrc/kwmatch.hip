@@ -1945,6 +1945,13 @@ extern "C" int kw_doc_routes(kw_handle *h, uint8_t *routes, int64_t n)
     return KW_OK;
 }
 
+extern "C" int kw_filter_variant(kw_handle *h, int32_t *variant)
+{
+    if (!h || !variant) return KW_EINVAL;
+    *variant = fk_gate_variant(h->FT.has_short, h->FT.gate);
+    return KW_OK;
+}
+
 extern "C" int kw_scan_counts(kw_handle *h, uint32_t *doc_items, int64_t n, int64_t *tasks, int32_t n_tasks)
 {
     if (!h || (n > 0 && !doc_items) || (n_tasks > 0 && !tasks)) return KW_EINVAL;

@@ -242,6 +242,17 @@ __device__ __forceinline__ int64_t fk_next_group(uint32_t *ctr, bool dyn, int64_
     return (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
 
+// which fk_stage1<SH> the filter runs for a KB's pair box (kw_filter_kernel's dispatch; kw_filter_variant reports
+// it): 0 no boxed short anchor, 2 one box for both bytes, 3 two boxes below 0x80, 1 two boxes, one reaching
+// bytes >= 0x80
+__host__ __device__ __forceinline__ int fk_gate_variant(int has_short, const uint32_t *gate)
+{
+    if (!has_short) return 0;
+    if (gate[0] == gate[3] && gate[1] == gate[4] && gate[2] == gate[5]) return 2;
+    if (gate[2] == 0u && gate[5] == 0u) return 3;
+    return 1;
+}
+
 // host + device hashes of the LDS tables
 // stage 1: the 4-gram b0..b3 at a position as k4 = b0 | b1 << 8 | b2 << 16 | b3 << 24; h = (b0..b2) * M1 +
 // (b1..b3) * M2 (a v_mul_u32_u24 and a v_mad_u32_u24; the one-multiply form h = (k4 mod 2^24) * M1 + k4 was

@@ -471,16 +471,16 @@ __global__ __launch_bounds__(FS_BLOCK, FS_MINW) void kw_filter_kernel(FastTables
     const int64_t n_groups = (n_docs + FG_DOCS - 1) / FG_DOCS;
     const int64_t K = S.chunk_groups;
     const int64_t n_chunks = (n_groups + K - 1) / K;
-    const bool gate_one = FT.gate[0] == FT.gate[3] && FT.gate[1] == FT.gate[4] && FT.gate[2] == FT.gate[5];
+    const int sh = fk_gate_variant(FT.has_short, FT.gate);   // (wave-uniform: kernel arguments)
     for (int64_t c = S.dyn ? fk_next_group(S.gnext, true, 0, 0) : wave; c < n_chunks;
          c = fk_next_group(S.gnext, S.dyn, c, n_waves)) {
         uint32_t ccur = 0;
         const int64_t g_lo = c * K, g_hi = g_lo + K < n_groups ? g_lo + K : n_groups;
-        if (!FT.has_short)
+        if (sh == 0)
             fk_filter_groups<0>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
-        else if (gate_one)
+        else if (sh == 2)
             fk_filter_groups<2>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
-        else if (FT.gate[2] == 0u && FT.gate[5] == 0u)
+        else if (sh == 3)
             fk_filter_groups<3>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
         else
             fk_filter_groups<1>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);

@@ -180,6 +180,12 @@ class GpuMatcher:
         _native.check(_native.lib().kw_scan_counts(self.h, _native.ptr(out), int(n_docs), None, 0), self.h)
         return out[:n_docs]
 
+    def filter_variant(self) -> int:
+        """The stage-1 gate the filter kernel runs for this KB (kw_filter_variant: fk_stage1<0..3>)."""
+        v = ctypes.c_int32(-1)
+        _native.check(_native.lib().kw_filter_variant(self.h, ctypes.byref(v)), self.h)
+        return int(v.value)
+
     TASK_KEYS = ('verify', 'edge', 'short', 'regex', 'regex_early')
 
     def task_counts(self) -> Dict[str, int]:

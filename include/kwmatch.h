@@ -220,6 +220,12 @@ int kw_doc_routes(kw_handle *h, uint8_t *routes, int64_t n);
  * the epilogue queued (the ones that run beside the verify and short-field kernels). */
 int kw_scan_counts(kw_handle *h, uint32_t *doc_items, int64_t n, int64_t *tasks, int32_t n_tasks);
 
+/* Which stage-1 gate of the filter kernel the compiled KB selects (fk_stage1<SH>, csrc/kwmatch_split.hpp), from
+ * the pair box of its 2-3 byte uppercase names: 0 no such name, 1 two boxes of which one reaches bytes >= 0x80,
+ * 2 one box for both bytes, 3 two boxes below 0x80.  The value the kernel's own dispatch computes
+ * (fk_gate_variant); valid after kw_compile.  For tests. */
+int kw_filter_variant(kw_handle *h, int32_t *variant);
+
 /* Host-buffer forms of kw_scan / kw_hits_copy for callers with no device allocator of their own (the
  * drop-in driver's single-GPU path runs without torch).  kw_scan_host copies the host arena
  * (arena_bytes bytes) and the 2*n_docs+1 offsets into library-owned device buffers (grown on demand, kept
