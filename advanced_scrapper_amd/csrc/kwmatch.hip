@@ -231,6 +231,7 @@ struct FastBuild {
     int has_short = 0;
     int has_t3 = 0;
     uint32_t gate[6] = {0, 0, 0, 0, 0, 0};   // stage-1 pair box (FastTables::gate)
+    uint32_t gatex[4] = {0, 0, 0, 0};        // ... and its extra values (FastTables::gatex)
     std::vector<uint64_t> ht_key, as_head, sig, bsig;
     std::vector<uint32_t> ht_begin, ht_cnt, kl, as_len, as_use_begin, as_use_cnt, use_pat, use_info0, use_info1,
         rxk, boff;
@@ -343,6 +344,141 @@ size_t rarest4(const QStats &Q, const uint8_t *s, size_t lo, size_t hi, size_t m
     for (size_t a = lo; a + 4 <= hi && a <= max_start; ++a) {
         uint32_t c = Q.count(s + a);
         if (c < bc) { bc = c; best = a; }
+    }
+    return best;
+}
+
+// ---- the filter's stage-1 pair box, chosen by selectivity
+// A 2-3 byte anchor (an uppercase name's whole bytes) passes stage 1 through the pair box: its first byte in one
+// range, its second in another (fk_stage1, kwmatch_split.hpp).  Without a background sample the box is the
+// bounding box of those anchors.  With one, kw_compile prices candidate gates on the sample and takes the
+// cheapest.  The price of a gate, in VALU instructions per 1 KiB tile of text:
+//
+//     cost = GATE_VALU[variant] + S2_VALU_PER_SURVIVOR * 1024 * (share of the sample's positions that pass)
+//
+// * GATE_VALU: the gate's instructions in fk_stage1<variant>, counted in the gfx950 assembly of a kernel that
+//   runs stage 1 alone, less fk_stage1<0>'s (profiles/r10_ab_notes.txt): 3: 46, 4: 58, 5: 61, 6: 73; 2 with its
+//   range below 0x80: 34, which is 3's count less the first byte's own 8 additions and 4 v_bitop3_b32 (1 is
+//   never a candidate: the choice is made only when every boxed byte is below 0x80).
+// * S2_VALU_PER_SURVIVOR = 1.86: stage 2 costs the filter 0.2 ms of a 1M-document scan for 60.3M stage-1
+//   survivors (profiles/r06_ab_notes.txt), 3.32 ps a survivor; the filter is bound by VALU issue, 4 us a scan per
+//   instruction and tile over the scan's 2.24M tiles, 1.79 ps: 3.32 / 1.79.
+// * the share: the sample's byte pairs inside the candidate (bytes >= 0x80 by their low seven bits, as the
+//   kernel's SWAR test sees them), plus, for every 3-byte anchor left outside, which goes to the 4-gram table as
+//   the 256 4-grams that start with it, its own occurrences and the table's 256 more bits of 2^FK_S1_BITS.
+//
+// Candidates: per byte, the range of the anchors' values with up to GATE_TRIM distinct values cut from either
+// end, alone or with one of the cut values as the "one more value" of fk_stage1<4..6>; every pair of those, and
+// for two plain ranges also their common hull (fk_stage1<2>: one flag word per text word).  A candidate must
+// hold every 2-byte anchor (65 536 4-grams would extend one) and may leave out as many 3-byte anchors as
+// FK_S1_EXT_MAX still takes.  The bounding box is the first candidate and wins ties, so a sample changes the
+// gate only where it pays.
+struct ShortAnchor { uint8_t b0, b1, b2, len; };
+struct PairGate {
+    int lo[2] = {255, 255}, hi[2] = {0, 0}, x[2] = {-1, -1};   // per byte: the range, one more value (-1: none)
+    bool in(int r, int v) const { return (v >= lo[r] && v <= hi[r]) || v == x[r]; }
+    bool holds(const ShortAnchor &e) const { return in(0, e.b0) && in(1, e.b1); }
+};
+#ifndef GATE_HULL
+#define GATE_HULL 1   // 0: no common-hull candidates (a tuning build: profiles/r10_ab_notes.txt)
+#endif
+constexpr int GATE_TRIM = 3;
+#ifndef GATE_S2_COST
+#define GATE_S2_COST 1.86
+#endif
+constexpr double S2_VALU_PER_SURVIVOR = GATE_S2_COST;
+constexpr double GATE_VALU[7] = {0, 0, 34, 46, 58, 61, 73};
+
+PairGate choose_gate(const QStats &Q, const std::vector<ShortAnchor> &boxed, uint32_t s1_ext)
+{
+    PairGate bb;
+    bool ascii = true;
+    for (const ShortAnchor &e : boxed) {
+        bb.lo[0] = std::min<int>(bb.lo[0], e.b0);
+        bb.hi[0] = std::max<int>(bb.hi[0], e.b0);
+        bb.lo[1] = std::min<int>(bb.lo[1], e.b1);
+        bb.hi[1] = std::max<int>(bb.hi[1], e.b1);
+        ascii = ascii && e.b0 < 0x80 && e.b1 < 0x80;
+    }
+    if (!Q.have || boxed.empty() || !ascii) return bb;
+    // the sample's pairs (low seven bits) as a summed-area table, and the outside candidates' own 3-grams
+    std::vector<uint64_t> sat(129 * 129, 0);
+    std::unordered_map<uint32_t, uint64_t> c3;
+    for (const ShortAnchor &e : boxed)
+        if (e.len == 3) c3[(uint32_t)e.b0 | ((uint32_t)e.b1 << 8) | ((uint32_t)e.b2 << 16)] = 0;
+    for (const auto &kv : Q.c4) {
+        sat[((kv.first & 0x7Fu) + 1) * 129 + ((kv.first >> 8) & 0x7Fu) + 1] += kv.second;
+        auto it = c3.find(kv.first & 0xFFFFFFu);
+        if (it != c3.end()) it->second += kv.second;
+    }
+    for (int a = 1; a <= 128; ++a)
+        for (int b = 1; b <= 128; ++b)
+            sat[a * 129 + b] += sat[(a - 1) * 129 + b] + sat[a * 129 + b - 1] - sat[(a - 1) * 129 + b - 1];
+    auto rect = [&](int a0, int a1, int b0, int b1) -> uint64_t {   // first byte in [a0, a1], second in [b0, b1]
+        return sat[(a1 + 1) * 129 + b1 + 1] - sat[a0 * 129 + b1 + 1] - sat[(a1 + 1) * 129 + b0] + sat[a0 * 129 + b0];
+    };
+    const double positions = (double)std::max<int64_t>(Q.len - 3, 1);
+    auto price = [&](const PairGate &g, double &cost) -> bool {
+        uint64_t pass = rect(g.lo[0], g.hi[0], g.lo[1], g.hi[1]);
+        if (g.x[0] >= 0) pass += rect(g.x[0], g.x[0], g.lo[1], g.hi[1]);
+        if (g.x[1] >= 0) pass += rect(g.lo[0], g.hi[0], g.x[1], g.x[1]);
+        if (g.x[0] >= 0 && g.x[1] >= 0) pass += rect(g.x[0], g.x[0], g.x[1], g.x[1]);
+        uint32_t n_out = 0;
+        for (const ShortAnchor &e : boxed) {
+            if (g.holds(e)) continue;
+            if (e.len != 3) return false;
+            ++n_out;
+            pass += c3[(uint32_t)e.b0 | ((uint32_t)e.b1 << 8) | ((uint32_t)e.b2 << 16)];
+        }
+        if ((uint64_t)s1_ext + 256ull * n_out > FK_S1_EXT_MAX) return false;
+        const int variant = g.x[0] >= 0 ? (g.x[1] >= 0 ? 6 : 4) : g.x[1] >= 0 ? 5
+                            : (g.lo[0] == g.lo[1] && g.hi[0] == g.hi[1]) ? 2 : 3;
+        const double share = (double)pass / positions + n_out * 256.0 / (double)(1u << FK_S1_BITS);
+        cost = GATE_VALU[variant] + S2_VALU_PER_SURVIVOR * 1024.0 * share;
+        return true;
+    };
+    struct Shape { int lo, hi, x; };
+    std::vector<Shape> shapes[2];
+    for (int r = 0; r < 2; ++r) {
+        std::vector<int> vals;
+        for (const ShortAnchor &e : boxed) vals.push_back(r ? e.b1 : e.b0);
+        std::sort(vals.begin(), vals.end());
+        vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+        const int n = (int)vals.size();
+        for (int i = 0; i <= GATE_TRIM && i < n; ++i)
+            for (int j = 0; j <= GATE_TRIM && i + j < n; ++j) {
+                shapes[r].push_back({vals[i], vals[n - 1 - j], -1});
+                for (int k = 0; k < i; ++k) shapes[r].push_back({vals[i], vals[n - 1 - j], vals[k]});
+                for (int k = n - j; k < n; ++k) shapes[r].push_back({vals[i], vals[n - 1 - j], vals[k]});
+            }
+    }
+    PairGate best = bb;
+    double best_cost = 0;
+    price(bb, best_cost);   // (always true: it holds every anchor)
+    const double bb_cost = best_cost;
+    auto offer = [&](const PairGate &g) {
+        double c;
+        if (price(g, c) && c < best_cost) { best = g; best_cost = c; }
+    };
+    for (const Shape &s0 : shapes[0])
+        for (const Shape &s1 : shapes[1]) {
+            PairGate g;
+            g.lo[0] = s0.lo; g.hi[0] = s0.hi; g.x[0] = s0.x;
+            g.lo[1] = s1.lo; g.hi[1] = s1.hi; g.x[1] = s1.x;
+            offer(g);
+            if (GATE_HULL && s0.x < 0 && s1.x < 0) {
+                g.lo[0] = g.lo[1] = std::min(s0.lo, s1.lo);
+                g.hi[0] = g.hi[1] = std::max(s0.hi, s1.hi);
+                offer(g);
+            }
+        }
+    if (kw_env("KW_DEBUG_GATE")) {   // (developer aid) the choice and its price beside the bounding box's
+        uint32_t n_out = 0;
+        for (const ShortAnchor &e : boxed) n_out += best.holds(e) ? 0u : 1u;
+        fprintf(stderr, "kw gate: %zu boxed anchors; bounding box [%02x-%02x] x [%02x-%02x] costs %.1f VALU a tile; chosen "
+                "[%02x-%02x]+%02x x [%02x-%02x]+%02x costs %.1f, %u anchors to the 4-gram table\n", boxed.size(), bb.lo[0],
+                bb.hi[0], bb.lo[1], bb.hi[1], bb_cost, best.lo[0], best.hi[0], best.x[0] & 0xFF, best.lo[1], best.hi[1],
+                best.x[1] & 0xFF, best_cost, n_out);
     }
     return best;
 }
@@ -646,7 +782,15 @@ int build_fast(FastBuild &B, const QStats &Q, int n_pat, const uint8_t *pat_byte
     B.b2.assign(FK_B2_WORDS, 0);
     std::unordered_map<uint64_t, std::vector<uint32_t>> keys;
     uint32_t s1_ext = 0;                         // 4-grams the fuzzy 3-byte anchors added to the stage-1 table
-    uint32_t box[4] = {255u, 0u, 255u, 0u};      // first byte lo / hi, second byte lo / hi of the boxed anchors
+    std::vector<ShortAnchor> boxed;              // the other 2-3 byte anchors: the pair box's (choose_gate)
+    auto extend3 = [&](const uint8_t *p) {       // the 256 4-grams that start with a 3-byte anchor
+        for (uint32_t x = 0; x < 256; ++x) {
+            const uint32_t k4 = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | (x << 24);
+            const uint32_t h1 = fk_s1_hash(k4);
+            B.s1[fk_s1_word(h1)] |= 1u << (h1 & 31);
+        }
+        s1_ext += 256;
+    };
     for (uint32_t a = 0; a < na; ++a) {
         const std::string &st = astr[a];
         const uint8_t *p = (const uint8_t *)st.data();
@@ -665,18 +809,9 @@ int build_fast(FastBuild &B, const QStats &Q, int n_pat, const uint8_t *pat_byte
             bool upper_only = true;
             for (const auto &u : auses[a]) upper_only = upper_only && (u.i0 & 0xFFu) == FU_UPPER;
             if (st.size() == 3 && !upper_only && s1_ext < FK_S1_EXT_MAX) {
-                for (uint32_t x = 0; x < 256; ++x) {
-                    const uint32_t k4 = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | (x << 24);
-                    const uint32_t h1 = fk_s1_hash(k4);
-                    B.s1[fk_s1_word(h1)] |= 1u << (h1 & 31);
-                }
-                s1_ext += 256;
+                extend3(p);
             } else {
-                box[0] = std::min<uint32_t>(box[0], p[0]);
-                box[1] = std::max<uint32_t>(box[1], p[0]);
-                box[2] = std::min<uint32_t>(box[2], p[1]);
-                box[3] = std::max<uint32_t>(box[3], p[1]);
-                B.has_short = 1;
+                boxed.push_back({p[0], p[1], (uint8_t)(st.size() == 3 ? p[2] : 0), (uint8_t)st.size()});
             }
             if (st.size() == 3) {
                 const uint32_t k3 = k2 | ((uint32_t)p[2] << 16);
@@ -694,7 +829,23 @@ int build_fast(FastBuild &B, const QStats &Q, int n_pat, const uint8_t *pat_byte
     }
     // the box as SWAR range constants per byte: bytes < 0x80 in [lo, hi] by two additions, bytes >= 0x80 all
     // in (one flag) when the range reaches them
+    // (choose_gate: the bounding box of the boxed anchors' first two bytes, or with a background sample the
+    // cheapest of its candidates; the 3-byte anchors it leaves outside go to the 4-gram extension)
+    const PairGate G = choose_gate(Q, boxed, s1_ext);
+    uint32_t n_in = 0;
+    for (const ShortAnchor &e : boxed) {
+        if (G.holds(e)) { ++n_in; continue; }
+        const uint8_t p3[3] = {e.b0, e.b1, e.b2};
+        extend3(p3);
+    }
+    B.has_short = n_in ? 1 : 0;
     if (B.has_short) {
+        const uint32_t box[4] = {(uint32_t)G.lo[0], (uint32_t)G.hi[0], (uint32_t)G.lo[1], (uint32_t)G.hi[1]};
+        for (int r = 0; r < 2; ++r)
+            if (G.x[r] >= 0) {
+                B.gatex[2 * r] = (0x80u - (uint32_t)G.x[r]) * 0x01010101u;
+                B.gatex[2 * r + 1] = (0x7Fu - (uint32_t)G.x[r]) * 0x01010101u;
+            }
         for (int r = 0; r < 2; ++r) {
             const uint32_t lo = box[2 * r], hi = box[2 * r + 1];
             const uint32_t alo = std::min(lo, 0x80u), ahi = std::min(hi, 0x7Fu);
@@ -1236,6 +1387,7 @@ extern "C" int kw_compile(const uint8_t *pat_bytes, const int64_t *pat_off, cons
     F.has_t3 = FB.has_t3;
     F.has_short = FB.has_short;
     for (int r = 0; r < 6; ++r) F.gate[r] = FB.gate[r];
+    for (int r = 0; r < 4; ++r) F.gatex[r] = FB.gatex[r];
     F.ht_key = (const uint64_t *)(B + f_htk);
     F.ht_begin = (const uint32_t *)(B + f_htb);
     F.ht_cnt = (const uint32_t *)(B + f_htc);
@@ -1948,7 +2100,7 @@ extern "C" int kw_doc_routes(kw_handle *h, uint8_t *routes, int64_t n)
 extern "C" int kw_filter_variant(kw_handle *h, int32_t *variant)
 {
     if (!h || !variant) return KW_EINVAL;
-    *variant = fk_gate_variant(h->FT.has_short, h->FT.gate);
+    *variant = fk_gate_variant(h->FT.has_short, h->FT.gate, h->FT.gatex);
     return KW_OK;
 }
 

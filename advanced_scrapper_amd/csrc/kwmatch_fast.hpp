@@ -111,6 +111,8 @@ struct FastTables {
     const uint32_t *edge_suf;   // FK_EDGE_WORDS
     int has_short;              // any 2- or 3-byte anchor in the stage-1 pair box
     uint32_t gate[6];           // the pair box: first byte {A, B, N}, second byte {A, B, N} (fk_in_box)
+    uint32_t gatex[4];          // one more value beside the box's range: first byte {A, B}, second byte {A, B} (A = 0:
+                                // none; kw_compile's gate choice with a background sample, fk_stage1<4..6>)
     int has_t3;                 // any 3-byte anchor
     const uint64_t *ht_key;     // (len << 32) | key bytes; ~0 = empty
     const uint32_t *ht_begin;
@@ -244,10 +246,11 @@ __device__ __forceinline__ int64_t fk_next_group(uint32_t *ctr, bool dyn, int64_
 
 // which fk_stage1<SH> the filter runs for a KB's pair box (kw_filter_kernel's dispatch; kw_filter_variant reports
 // it): 0 no boxed short anchor, 2 one box for both bytes, 3 two boxes below 0x80, 1 two boxes, one reaching
-// bytes >= 0x80
-__host__ __device__ __forceinline__ int fk_gate_variant(int has_short, const uint32_t *gate)
+// bytes >= 0x80; 4 / 5 / 6 two boxes below 0x80 and one more value for the first byte / the second / both
+__host__ __device__ __forceinline__ int fk_gate_variant(int has_short, const uint32_t *gate, const uint32_t *gatex)
 {
     if (!has_short) return 0;
+    if (gatex[0] != 0u || gatex[2] != 0u) return gatex[0] == 0u ? 5 : gatex[2] == 0u ? 4 : 6;
     if (gate[0] == gate[3] && gate[1] == gate[4] && gate[2] == gate[5]) return 2;
     if (gate[2] == 0u && gate[5] == 0u) return 3;
     return 1;

@@ -36,7 +36,8 @@ namespace kw {
 #ifndef FS_EQ_TRIGGER
 #define FS_EQ_TRIGGER 32   // queued entries that start a stage-2 round: a round then takes ~2 tiles of survivors
                            // while their bytes are still in L2 (64: filter reads 4.03 GB a launch, 48: 3.59, 32: 3.08
-                           // for 1.103 / 1.111 / 1.112 ms; 24: 1.145 ms, 16: 1.238 ms)
+                           // for 1.103 / 1.111 / 1.112 ms; 24: 1.145 ms, 16: 1.238 ms; again with round 10's
+                           // 45.5M survivors a scan: 32: 0.930, 24: 0.967, 16: 1.026 ms, r10_ab_notes.txt)
 #endif
 #ifndef FS_AHEAD
 #define FS_AHEAD 3       // 1 KiB tiles each filter wave keeps in flight
@@ -123,17 +124,33 @@ __device__ __forceinline__ uint32_t fk_transpose16(uint32_t v)
     return t;
 }
 
+// (b << C) | h as one v_lshl_or_b32
+template <uint32_t C>
+__device__ __forceinline__ uint32_t fk_lshl_or(uint32_t b, uint32_t h)
+{
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(b), "n"(C), "v"(h));
+    return r;
+}
+
+// a & ~b, (a & ~b) | c and a & b & c as one v_bitop3_b32 each (the truth table over a = 0xF0, b = 0xCC, c = 0xAA;
+// spelled out: the compiler's own choice for the pair box's flags changed with the code around them)
+__device__ __forceinline__ uint32_t fk_andn(uint32_t a, uint32_t b) { return __builtin_amdgcn_bitop3_b32(a, b, b, 0x30); }
+__device__ __forceinline__ uint32_t fk_andn_or(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xBA); }
+__device__ __forceinline__ uint32_t fk_and3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x80); }
+
 // the pair box's byte flags of a word: bit 7 of byte i set iff byte i is in the box's range {A, B, N}
 __device__ __forceinline__ uint32_t fk_in_box(uint32_t x, uint32_t A, uint32_t B, uint32_t N)
 {
     const uint32_t t = x & 0x7F7F7F7Fu;
-    return (((t + A) & ~(t + B) & ~x) | (x & N)) & 0x80808080u;
+    return (__builtin_amdgcn_bitop3_b32(t + A, t + B, x, 0x10) | (x & N)) & 0x80808080u;   // (0x10: a & ~b & ~c)
 }
 
 // Stage 1 of one lane's 16 bytes W[0..3] (+ W[4]): `hit` = positions where an anchor of >= 4 bytes may start
 // (its first four bytes' bit in the 4-gram table; also the fuzzy 3-byte anchors' 4-grams), `gate` = positions
 // whose first two bytes lie in the pair box of the other 2-3 byte anchors (SWAR, no lookup; SH = 2: one box
-// for both bytes, the byte flags of each word computed once; SH = 3: two ranges below 0x80); transposed bit order (fk_tbit).  Per position:
+// for both bytes, the byte flags of each word computed once; SH = 3: two ranges below 0x80; SH = 4, 5, 6: those
+// with one more value for the first byte, the second, both); transposed bit order (fk_tbit).  Per position:
 // one v_mad_u32_u24 (fk_s1_hash), the address, the lookup, v_bfe_u32 and v_lshl_or_b32.
 template <int SH>
 __device__ __forceinline__ void fk_stage1(const FastTables &FT, const FilterLds &L, const uint32_t (&W)[5],
@@ -161,37 +178,61 @@ __device__ __forceinline__ void fk_stage1(const FastTables &FT, const FilterLds 
             const uint32_t pr = f0[q] & __builtin_amdgcn_alignbyte(f1[q + 1], f1[q], 1);   // byte i: b[i], b[i+1]
             g |= pr >> (7 - q);
         }
-    } else if (SH == 3) {
+    } else if (SH >= 3) {
         // both ranges below 0x80 (no N term): a byte >= 0x80 may be flagged too (a superset; the exact pair
-        // table decides in stage 2), so each flag is two additions and one v_bitop3_b32
+        // table decides in stage 2), so each flag is two additions and one v_bitop3_b32.  SH = 4 / 5 / 6: the
+        // first / second / both bytes' range takes one more value (FT.gatex, a range of one: kw_compile's
+        // choice for a 2-byte name that would stretch the box), or-ed into the byte's flag by two more additions
+        // and one v_bitop3_b32 per word
+        constexpr bool X0 = SH == 4 || SH == 6, X1 = SH == 5 || SH == 6;
         uint32_t t[5], f1[5];
 #pragma unroll
         for (int q = 0; q < 5; ++q) t[q] = W[q] & 0x7F7F7F7Fu;
 #pragma unroll
-        for (int q = 0; q < 5; ++q) f1[q] = (t[q] + FT.gate[3]) & ~(t[q] + FT.gate[4]);
+        for (int q = 0; q < 5; ++q) {
+            f1[q] = fk_andn(t[q] + FT.gate[3], t[q] + FT.gate[4]);
+            if (X1) f1[q] = fk_andn_or(t[q] + FT.gatex[2], t[q] + FT.gatex[3], f1[q]);
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const uint32_t f0 = (t[q] + FT.gate[0]) & ~(t[q] + FT.gate[1]);
-            const uint32_t pr = f0 & __builtin_amdgcn_alignbyte(f1[q + 1], f1[q], 1) & 0x80808080u;
+            uint32_t f0 = fk_andn(t[q] + FT.gate[0], t[q] + FT.gate[1]);
+            if (X0) f0 = fk_andn_or(t[q] + FT.gatex[0], t[q] + FT.gatex[1], f0);
+            const uint32_t pr = fk_and3(f0, __builtin_amdgcn_alignbyte(f1[q + 1], f1[q], 1), 0x80808080u);
             g |= pr >> (7 - q);
         }
     } else if (SH == 2) {
         uint32_t f[5];
+        if (FT.gate[2] == 0u) {   // (wave-uniform) the range below 0x80: the flags as SH = 3 computes them, once
 #pragma unroll
-        for (int q = 0; q < 5; ++q) f[q] = fk_in_box(W[q], FT.gate[0], FT.gate[1], FT.gate[2]);
+            for (int q = 0; q < 5; ++q) {
+                const uint32_t t = W[q] & 0x7F7F7F7Fu;
+                f[q] = fk_andn(t + FT.gate[0], t + FT.gate[1]);
+            }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t pr = f[q] & __builtin_amdgcn_alignbyte(f[q + 1], f[q], 1);
-            g |= pr >> (7 - q);
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t pr = fk_and3(f[q], __builtin_amdgcn_alignbyte(f[q + 1], f[q], 1), 0x80808080u);
+                g |= pr >> (7 - q);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) f[q] = fk_in_box(W[q], FT.gate[0], FT.gate[1], FT.gate[2]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t pr = f[q] & __builtin_amdgcn_alignbyte(f[q + 1], f[q], 1);
+                g |= pr >> (7 - q);
+            }
         }
     }
-    uint32_t h = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const uint32_t b = __builtin_amdgcn_ubfe(sw[j], hh[j], 1);
-        h |= b << fk_tbit(j);
-    }
-    hit = h;
+    // the 16 lookup bits to their places: v_bfe_u32, then one v_lshl_or_b32 each (as inline asm: left to itself
+    // the compiler shifts each bit on its own and joins them by v_or3_b32, half an instruction more a position);
+    // two chains of eight, so that no instruction waits for the one before it
+    uint32_t h0 = __builtin_amdgcn_ubfe(sw[0], hh[0], 1), h1 = __builtin_amdgcn_ubfe(sw[1], hh[1], 1) << fk_tbit(1);
+#define FK_PLACE(h, j) h = fk_lshl_or<fk_tbit(j)>(__builtin_amdgcn_ubfe(sw[j], hh[j], 1), h)
+    FK_PLACE(h0, 2);  FK_PLACE(h1, 3);  FK_PLACE(h0, 4);  FK_PLACE(h1, 5);  FK_PLACE(h0, 6);  FK_PLACE(h1, 7);
+    FK_PLACE(h0, 8);  FK_PLACE(h1, 9);  FK_PLACE(h0, 10); FK_PLACE(h1, 11); FK_PLACE(h0, 12); FK_PLACE(h1, 13);
+    FK_PLACE(h0, 14); FK_PLACE(h1, 15);
+#undef FK_PLACE
+    hit = h0 | h1;
     gate = g;
 }
 
@@ -471,7 +512,7 @@ __global__ __launch_bounds__(FS_BLOCK, FS_MINW) void kw_filter_kernel(FastTables
     const int64_t n_groups = (n_docs + FG_DOCS - 1) / FG_DOCS;
     const int64_t K = S.chunk_groups;
     const int64_t n_chunks = (n_groups + K - 1) / K;
-    const int sh = fk_gate_variant(FT.has_short, FT.gate);   // (wave-uniform: kernel arguments)
+    const int sh = fk_gate_variant(FT.has_short, FT.gate, FT.gatex);   // (wave-uniform: kernel arguments)
     for (int64_t c = S.dyn ? fk_next_group(S.gnext, true, 0, 0) : wave; c < n_chunks;
          c = fk_next_group(S.gnext, S.dyn, c, n_waves)) {
         uint32_t ccur = 0;
@@ -482,6 +523,12 @@ __global__ __launch_bounds__(FS_BLOCK, FS_MINW) void kw_filter_kernel(FastTables
             fk_filter_groups<2>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
         else if (sh == 3)
             fk_filter_groups<3>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
+        else if (sh == 4)
+            fk_filter_groups<4>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
+        else if (sh == 5)
+            fk_filter_groups<5>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
+        else if (sh == 6)
+            fk_filter_groups<6>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
         else
             fk_filter_groups<1>(FT, L, arena, off, n_docs, S, c, g_lo, g_hi, wib, ncand, ncand2, ccur);
         if (lane == 0) {

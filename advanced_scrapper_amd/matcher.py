@@ -181,7 +181,8 @@ class GpuMatcher:
         return out[:n_docs]
 
     def filter_variant(self) -> int:
-        """The stage-1 gate the filter kernel runs for this KB (kw_filter_variant: fk_stage1<0..3>)."""
+        """The stage-1 gate the filter kernel runs for this KB (kw_filter_variant: fk_stage1<0..6>; 4-6 only
+        when a background sample made kw_compile choose a box with one more value beside a range)."""
         v = ctypes.c_int32(-1)
         _native.check(_native.lib().kw_filter_variant(self.h, ctypes.byref(v)), self.h)
         return int(v.value)

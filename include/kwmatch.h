@@ -222,7 +222,8 @@ int kw_scan_counts(kw_handle *h, uint32_t *doc_items, int64_t n, int64_t *tasks,
 
 /* Which stage-1 gate of the filter kernel the compiled KB selects (fk_stage1<SH>, csrc/kwmatch_split.hpp), from
  * the pair box of its 2-3 byte uppercase names: 0 no such name, 1 two boxes of which one reaches bytes >= 0x80,
- * 2 one box for both bytes, 3 two boxes below 0x80.  The value the kernel's own dispatch computes
+ * 2 one box for both bytes, 3 two boxes below 0x80, 4 / 5 / 6 two boxes below 0x80 and one more value for the
+ * first byte / the second / both (chosen only with a background sample).  The value the kernel's own dispatch computes
  * (fk_gate_variant); valid after kw_compile.  For tests. */
 int kw_filter_variant(kw_handle *h, int32_t *variant);
 
