@@ -54,6 +54,7 @@ EXPORTS = ('kw_compile', 'kw_scan', 'kw_hits', 'kw_hits_copy', 'kw_stats', 'kw_l
            'kw_cdx_remaining_size', 'kw_cdx_remaining_copy', 'kw_cdx_exclude_last_ms',
            'kw_cdx_run_exclude_unique', 'kw_cdx_exclude_duplicates', 'kw_cdx_selected_ts', 'kw_cdx_csv_select_size',
            'kw_cdx_csv_select_copy', 'kw_cdx_select_last_ms',
+           'kw_csv_stream_begin', 'kw_csv_stream_window', 'kw_csv_stream_end', 'kw_cdx_exclude_distinct_seen',
            'kw_rows_create', 'kw_rows_run', 'kw_rows_copy', 'kw_rows_last_ms', 'kw_rows_last_error',
            'kw_rows_destroy',
            'kw_rows_cells', 'kw_rows_emit', 'kw_rows_emit_result', 'kw_rows_copy_index', 'kw_rows_emit_last_ms',
@@ -169,6 +170,13 @@ def lib() -> ctypes.CDLL:
     L.kw_cdx_select_last_ms.argtypes = [vp, vp, i32]
     for f in ('kw_cdx_run_exclude_unique', 'kw_cdx_exclude_duplicates', 'kw_cdx_selected_ts', 'kw_cdx_csv_select_size',
               'kw_cdx_csv_select_copy', 'kw_cdx_select_last_ms'):
+        getattr(L, f).restype = ctypes.c_int
+    L.kw_csv_stream_begin.argtypes = [vp, ctypes.c_char_p, i32, i32]
+    L.kw_csv_stream_window.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32),
+                                       ctypes.POINTER(i64), vp]
+    L.kw_csv_stream_end.argtypes = [vp, i32, ctypes.POINTER(i64)]
+    L.kw_cdx_exclude_distinct_seen.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
+    for f in ('kw_csv_stream_begin', 'kw_csv_stream_window', 'kw_csv_stream_end', 'kw_cdx_exclude_distinct_seen'):
         getattr(L, f).restype = ctypes.c_int
     L.kw_rows_create.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(vp)]
     L.kw_rows_run.argtypes = [vp, vp, i64, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),

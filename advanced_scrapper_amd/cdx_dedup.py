@@ -225,6 +225,228 @@ class GpuUrlDedup:
                                                 ctypes.byref(bad), ctypes.c_void_p(st.cuda_stream)))
         return int(verdict.value), int(bad.value), int(rows.value)
 
+    # ---- files of any size: fixed file ranges through two pinned slots, a reader thread one window ahead, two
+    # device texts used in turn (include/kwdedup.h kw_csv_stream_*; DESIGN.md §7, "Windowed CSV append")
+    def _stream_buffers(self, window_bytes: int, max_record_bytes: int):
+        """Two pinned host slots of a window and two device texts of a tail plus a window, kept for the next file
+        of the same geometry."""
+        t = self.torch
+        W, cap = int(window_bytes), (int(window_bytes) + int(max_record_bytes) + ARENA_PAD + 15) & ~15
+        have = getattr(self, '_stream_bufs', None)
+        if have is None or have[0][0].numel() != W or have[1][0].numel() != cap:
+            self._stream_bufs = have = None   # (the old ones go first)
+            dev = t.device('cuda', self.device)
+            slots = [t.empty(W, dtype=t.uint8, pin_memory=True) for _ in range(2)]
+            texts = [t.empty(cap, dtype=t.uint8, device=dev) for _ in range(2)]
+            have = self._stream_bufs = (slots, texts)
+        return have
+
+    def _stream_mark(self):
+        """An event after the work enqueued so far (its ``synchronize`` waits for it)."""
+        t = self.torch
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return ev
+
+    def _stream_ptr(self) -> ctypes.c_void_p:
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _stream_sync(self) -> None:
+        self.torch.cuda.current_stream(self.device).synchronize()
+
+    def _stream_file(self, path: str, window_bytes: int, max_record_bytes: int, take, find_cut: bool = False):
+        """The file's ranges [k * window_bytes, (k + 1) * window_bytes) to the device one after the other.  Device
+        text k is the unconsumed tail of text k - 1 (copied device-to-device to offset 0, so every text starts
+        16-byte aligned) and range k behind it (an async copy from a pinned slot on the current stream); the reader
+        thread fills the other slot with range k + 1 meanwhile.  ``take(d_text, n, final, cut) -> consumed`` (a
+        negative value stops the stream) is given the text, its bytes, whether it ends the file and, with
+        ``find_cut``, the position after the last '\\n' of the text (found on the reader thread).  Returns (stats,
+        stopped): stopped is None, the value ``take`` stopped with, or 'record' when a tail outgrew
+        ``max_record_bytes``."""
+        import concurrent.futures
+        import time
+        W, R = int(window_bytes), int(max_record_bytes)
+        if W < 1 or R < 0:
+            raise ValueError('window_bytes >= 1, max_record_bytes >= 0')
+        slots, texts = self._stream_buffers(W, R)
+        views = [s.numpy() for s in slots]
+        size = os.path.getsize(path)
+        n_win = max(1, -(-size // W))
+        stats = {'windows': 0, 'file_bytes': size, 'read_s': 0.0, 'wait_s': 0.0, 'tail_max': 0, 'consumed': [],
+                 'pinned_bytes': 2 * int(slots[0].numel()), 'device_text_bytes': 2 * int(texts[0].numel())}
+        fd = os.open(path, os.O_RDONLY)
+
+        def read(k: int):
+            t0 = time.perf_counter()
+            m = min(W, size - k * W)
+            mv, got = memoryview(views[k & 1]), 0
+            while got < m:
+                g = os.preadv(fd, [mv[got:m]], k * W + got)
+                if not g:
+                    raise OSError(f'{path}: the file shrank while it was read')
+                got += g
+            last_nl = -1
+            if find_cut:   # (backwards in pieces: the last line end lies near the end)
+                hi = m
+                while hi > 0 and last_nl < 0:
+                    lo = max(0, hi - (1 << 16))
+                    hit = np.flatnonzero(views[k & 1][lo:hi] == 0x0A)
+                    if len(hit):
+                        last_nl = lo + int(hit[-1])
+                    hi = lo
+            return m, last_nl, time.perf_counter() - t0
+
+        pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+        stopped = None
+        copied = [None, None]   # the event after each slot's last copy to the device
+        try:
+            ahead = pool.submit(read, 0)
+            tail = 0
+            for k in range(n_win):
+                t0 = time.perf_counter()
+                m, last_nl, dt = ahead.result()
+                stats['wait_s'] += time.perf_counter() - t0
+                stats['read_s'] += dt
+                # (slot (k + 1) & 1 held range k - 1: its copy has ended before the reader writes there again)
+                if copied[(k + 1) & 1] is not None:
+                    copied[(k + 1) & 1].synchronize()
+                ahead = pool.submit(read, k + 1) if k + 1 < n_win else None
+                cur, n = texts[k & 1], tail + m
+                if m:
+                    cur[tail:n].copy_(slots[k & 1][:m], non_blocking=True)
+                    copied[k & 1] = self._stream_mark()
+                final = k == n_win - 1
+                cut = n if final else (tail + last_nl + 1 if last_nl >= 0 else 0)
+                consumed = take(cur, n, final, cut)
+                stats['windows'] += 1
+                if consumed < 0:
+                    stopped = consumed
+                    break
+                tail = n - consumed
+                stats['consumed'].append(consumed)
+                stats['tail_max'] = max(stats['tail_max'], tail)
+                if final:
+                    break
+                if tail > R:
+                    stopped = 'record'
+                    break
+                if tail:
+                    texts[(k + 1) & 1][:tail].copy_(cur[consumed:n], non_blocking=True)
+        finally:
+            pool.shutdown(wait=True)   # (the reader has left before anything is raised)
+            os.close(fd)
+        self._stream_sync()   # (the slots and texts are free for the next file)
+        return stats, stopped
+
+    def csv_stream_begin(self, header: str, url_col: int) -> None:
+        """kw_csv_stream_begin: open the windowed form of ``csv_append`` over the store as it stands."""
+        self._check(_native.lib().kw_csv_stream_begin(self.h, header.encode('utf-8'), int(url_col),
+                                                      header.count(',') + 1))
+
+    def csv_stream_window(self, data, final: bool) -> Tuple[int, int, int, int]:
+        """kw_csv_stream_window over one window's bytes (as ``csv_append`` takes a text): (verdict, the first
+        offender's position in the file or -1, rows appended, consumed)."""
+        d_text, n = self.cdx_text_device(data)
+        consumed, rows, verdict, bad = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+        st = self.torch.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_csv_stream_window(self.h, _native.ptr(d_text), n, 1 if final else 0,
+                                                       ctypes.byref(consumed), ctypes.byref(rows), ctypes.byref(verdict),
+                                                       ctypes.byref(bad), ctypes.c_void_p(st.cuda_stream)))
+        return int(verdict.value), int(bad.value), int(rows.value), int(consumed.value)
+
+    def csv_stream_end(self, commit: bool) -> Tuple[int, int]:
+        """kw_csv_stream_end: (KW_CSV_OK, or KW_CSV_ROWS when a committed stream appended no row; the rows that
+        stay appended)."""
+        total = ctypes.c_int64()
+        rc = _native.lib().kw_csv_stream_end(self.h, 1 if commit else 0, ctypes.byref(total))
+        if rc == _native.KW_CSV_ROWS:
+            return rc, 0
+        self._check(rc)
+        return _native.KW_CSV_OK, int(total.value)
+
+    def csv_append_file(self, path: str, header: str, url_col: int, window_bytes: int, max_record_bytes: int):
+        """``csv_append`` over a file of any size, window by window: (verdict KW_CSV_* or None, rows appended, stats).
+        Device memory for text is two windows plus two tails whatever the file's size.  A record that no text of
+        ``window_bytes + max_record_bytes`` holds (or a stray quote that swallows the rest) ends the stream with
+        nothing appended, verdict None and ``stats['refusal'] == 'record'``: more conservative than the one-piece
+        call, never wrong.  ``stats['bad_pos']``: the first offender's position in the file (-1).  A KW_E* error
+        or an exception of the reader is raised after the reader thread has been joined; nothing stays appended."""
+        L = _native.lib()
+        st = self._stream_ptr()
+        self._check(L.kw_csv_stream_begin(self.h, header.encode('utf-8'), int(url_col), header.count(',') + 1))
+        state = {'verdict': _native.KW_CSV_OK, 'bad': -1}
+
+        def take(d_text, n, final, _cut):
+            consumed, rows, verdict, bad = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+            self._check(L.kw_csv_stream_window(self.h, _native.ptr(d_text), n, 1 if final else 0, ctypes.byref(consumed),
+                                               ctypes.byref(rows), ctypes.byref(verdict), ctypes.byref(bad),
+                                               st))
+            if verdict.value != _native.KW_CSV_OK:
+                state['verdict'], state['bad'] = int(verdict.value), int(bad.value)
+                return -1
+            return int(consumed.value)
+
+        try:
+            stats, stopped = self._stream_file(path, window_bytes, max_record_bytes, take)
+        except BaseException:
+            L.kw_csv_stream_end(self.h, 0, None)
+            raise
+        total = ctypes.c_int64()
+        rc = L.kw_csv_stream_end(self.h, 1 if stopped is None else 0, ctypes.byref(total))
+        stats['refusal'], stats['bad_pos'] = None, state['bad']
+        if stopped == 'record':
+            stats['refusal'] = 'record'
+            return None, 0, stats
+        if stopped is not None:
+            return state['verdict'], 0, stats
+        if rc == _native.KW_CSV_ROWS:   # (no record after the header: the one-piece call's verdict, at the file's end)
+            stats['bad_pos'] = stats['file_bytes']
+            return _native.KW_CSV_ROWS, 0, stats
+        self._check(rc)
+        return _native.KW_CSV_OK, int(total.value), stats
+
+    def cdx_append_file(self, path: str, dialect, window_bytes: int, max_record_bytes: int):
+        """``cdx_append`` over a file of any size in a dialect without quotes (the part CSVs): every window is cut on
+        the host at its last '\\n', the rest is carried in front of the next, and the header line is skipped once.
+        (verdict KW_CDX_* or None, rows appended, stats); a line that no text holds: verdict None and
+        ``stats['refusal'] == 'record'``.  Unlike the CSV stream a refused window leaves the earlier windows' rows
+        in the store: the caller starts over with ``cdx_begin``."""
+        L = _native.lib()
+        st = self._stream_ptr()
+        base = list(CDX_DIALECTS[dialect])
+        state = {'verdict': _native.KW_CDX_OK, 'rows': 0, 'first': True}
+
+        def take(d_text, n, final, cut):
+            if cut == 0 and not (final and state['first']):
+                return 0
+            dia = _native.CdxDialect(*(base[:3] + [base[3] if state['first'] else 0] + base[4:]))
+            rows, verdict, bad = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+            self._check(L.kw_cdx_append(self.h, _native.ptr(d_text), cut, ctypes.byref(dia), ctypes.byref(rows),
+                                        ctypes.byref(verdict), ctypes.byref(bad), st))
+            if verdict.value != _native.KW_CDX_OK:
+                state['verdict'] = int(verdict.value)
+                return -1
+            state['first'] = False
+            state['rows'] += int(rows.value)
+            return cut
+
+        stats, stopped = self._stream_file(path, window_bytes, max_record_bytes, take, find_cut=True)
+        stats['refusal'] = 'record' if stopped == 'record' else None
+        if stopped == 'record':
+            return None, 0, stats
+        if stopped is not None:
+            return state['verdict'], 0, stats
+        return _native.KW_CDX_OK, state['rows'], stats
+
+    def exclude_distinct_seen(self) -> Tuple[int, int]:
+        """After run_exclude: (the distinct URLs among the link rows that were seen, the distinct URLs of the exclude
+        rows), the unique-URL counts of experiental/new_links.py."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        st = self.torch.cuda.current_stream(self.device)
+        self._check(_native.lib().kw_cdx_exclude_distinct_seen(self.h, ctypes.byref(a), ctypes.byref(b),
+                                                               ctypes.c_void_p(st.cuda_stream)))
+        return int(a.value), int(b.value)
+
     def run_exclude(self, n_exclude: int) -> Tuple[int, int, int]:
         """The set difference over the store, whose first `n_exclude` rows are the exclude rows and the rest the
         link rows: (link rows, those whose string is among the exclude rows, those remaining)."""

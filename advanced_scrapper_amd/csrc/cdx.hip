@@ -1,5 +1,5 @@
 // libkwmatch: CDX listings and quoted CSV files parsed into the dedup's row store and the kept rows rendered as CSV,
-// on the device (include/kwdedup.h, kw_cdx_* and kw_csv_append).
+// on the device (include/kwdedup.h, kw_cdx_*, kw_csv_append and its windowed form kw_csv_stream_*).
 //
 // Reference: yahoo_links_selenium.py:59 (read_csv of a listing), :82 / :176 (to_csv), :164-167 (read_csv of the
 // part CSVs); the rule under which a text is taken at all is restated in tests/cdx_rule.py.
@@ -42,6 +42,7 @@
 #include <string>
 
 #include "kwdedup_handle.hpp"
+#include "kwenv.hpp"
 
 namespace cx {
 
@@ -598,6 +599,8 @@ __global__ __launch_bounds__(BLOCK) void cx_sel_ts_kernel(int64_t n_kept, const 
 //                       count at the end of the record before it; the two that bound the column give the cell.
 //   cv_rows_kernel      lane = record: the field count from the two delimiter counts, the cell without its outer
 //                       quotes, ':' looked for and '"' / '\n' / '\r' refused 8 bytes a step.
+//   cv_last_end_kernel  a window of a stream (kw_csv_stream_window): the position after the last '\n' outside quotes,
+//                       from the same masks and carried parity; every pass after it runs over the bytes before it.
 //   then cx_scan_*, cx_off_kernel and cx_fill_kernel<ArenaGen> as kw_cdx_append.
 enum { CV_COUNT = 0, CV_ENDS = 1, CV_CELLS = 2 };
 
@@ -685,6 +688,7 @@ struct CsvArgs {
     int64_t *rec_start, *end_pos, *end_dcnt, *cell_start, *cell_end;
     int64_t cap;                                    // entries of the per-record arrays
     int url_col;
+    int r0;                                         // the first record that is a row: 1 when record 0 is the header
 };
 
 template <int MODE>
@@ -771,8 +775,9 @@ __global__ __launch_bounds__(BLOCK) void cv_tile_kernel(CsvArgs A)
                     } else {
                         A.rec_start[r] = p + k;
                     }
-                } else if (r >= 1) {
-                    const int64_t f = cd + __popc(DL & below) - A.end_dcnt[r - 1];   // the delimiter ends field f
+                } else if (r >= A.r0) {
+                    // the delimiter ends field f
+                    const int64_t f = cd + __popc(DL & below) - (r > 0 ? A.end_dcnt[r - 1] : 0);
                     if (f == A.url_col - 1) A.cell_start[r] = p + k + 1;
                     if (f == A.url_col) A.cell_end[r] = p + k;
                 }
@@ -781,17 +786,55 @@ __global__ __launch_bounds__(BLOCK) void cv_tile_kernel(CsvArgs A)
     }
 }
 
-// Record r >= 1 (record 0 is the header): [rec_start[r], its end); the records past n_ends end with the text.
-// The cell's position and length go to cell_start[r] / cell_end[r] (their own lane's entries).
-__global__ __launch_bounds__(BLOCK) void cv_rows_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t n_rec,
-                                                        int64_t n_ends, int64_t n_delims, int n_fields, int url_col,
+// The windowed form (kw_csv_stream_window): the position after the last '\n' outside quotes, as a maximum over the
+// lanes (0: none).  tile_q holds the tiles' scanned '"' counts, so the parity is cv_tile_kernel's.
+__global__ __launch_bounds__(BLOCK) void cv_last_end_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t ntiles,
+                                                            const unsigned long long *__restrict__ tile_q,
+                                                            unsigned long long *__restrict__ last)
+{
+    __shared__ unsigned long long ws[BLOCK / 64];
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t p = tile * TILE + (int64_t)threadIdx.x * 16;
+        uint32_t valid = 0, q = 0, nl = 0;
+        if (p < n) {
+            const uint4 v = *(const uint4 *)(text + p);
+            valid = n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u;
+            q = mask16(v, 0x22u) & valid;
+            nl = mask16(v, 0x0Au) & valid;
+        }
+        unsigned long long total;
+        const unsigned long long qb = block_scan((unsigned long long)__popc(q), ws, &total);
+        const uint32_t inpar = (uint32_t)((tile_q[tile] + qb) & 1ull);
+        uint32_t incl = q;
+        incl ^= incl << 1;
+        incl ^= incl << 2;
+        incl ^= incl << 4;
+        incl ^= incl << 8;
+        const uint32_t sb = ((incl << 1) ^ (inpar ? 0xFFFFu : 0u)) & valid;
+        const uint32_t ends = nl & ~sb;
+        unsigned long long e = ends ? (unsigned long long)p + (unsigned long long)(32 - __builtin_clz(ends)) : 0ull;
+        if (__any(e != 0ull)) {
+            for (int d = 32; d >= 1; d >>= 1) {
+                const unsigned long long y = __shfl_xor(e, d, 64);
+                e = y > e ? y : e;
+            }
+            if ((threadIdx.x & 63) == 0) atomicMax(last, e);
+        }
+    }
+}
+
+// Record r >= r0 (r0 = 1: record 0 is the header): [rec_start[r], its end); the records past n_ends end with the
+// text.  The cell's position and length go to cell_start[r] / cell_end[r] (their own lane's entries).
+__global__ __launch_bounds__(BLOCK) void cv_rows_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t r0,
+                                                        int64_t n_rec, int64_t n_ends, int64_t n_delims, int n_fields,
+                                                        int url_col,
                                                         const int64_t *__restrict__ rec_start,
                                                         const int64_t *__restrict__ end_pos,
                                                         const int64_t *__restrict__ end_dcnt, int64_t *cell_start,
                                                         int64_t *cell_end, CsvErrs *__restrict__ errs)
 {
     constexpr uint64_t ONES = 0x0101010101010101ull;
-    for (int64_t r = 1 + (int64_t)blockIdx.x * BLOCK + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * BLOCK) {
+    for (int64_t r = r0 + (int64_t)blockIdx.x * BLOCK + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * BLOCK) {
         const int64_t s = rec_start[r];
         int64_t e = n, dc = n_delims;
         if (r < n_ends) {
@@ -799,7 +842,7 @@ __global__ __launch_bounds__(BLOCK) void cv_rows_kernel(const uint8_t *__restric
             dc = end_dcnt[r];
             if (e > s && text[e - 1] == 0x0Du) --e;   // "\r\n"
         }
-        if (dc - end_dcnt[r - 1] + 1 != (int64_t)n_fields) {
+        if (dc - (r > 0 ? end_dcnt[r - 1] : 0) + 1 != (int64_t)n_fields) {
             atomicMin(&errs->fields, (unsigned long long)s);
             continue;
         }
@@ -859,6 +902,12 @@ struct kw_cdx_store {
     int64_t sel_lines = 0, sel_bytes = 0;
     bool sel_ready = false;
     float sel_ms[2] = {0.f, 0.f};
+    // the windowed CSV append (kw_csv_stream_*): the header arguments, the rows and bytes kw_csv_stream_begin noted,
+    // the file position of the next window's first byte
+    bool stream_open = false, stream_first = false, stream_final = false, stream_bad = false;
+    std::string stream_header;
+    int32_t stream_col = 0, stream_fields = 0;
+    int64_t stream_n0 = 0, stream_bytes0 = 0, stream_pos = 0;
 };
 
 void kw_cdx_store_destroy(kw_cdx_store *s)
@@ -968,6 +1017,7 @@ extern "C" int kw_cdx_begin(kw_dedup *h)
     int rc = store_get(h, &s);
     if (rc) return rc;
     s->n = s->n_bytes = 0;
+    s->stream_open = false;
     s->run_serial = 0;
     s->csv_ready = false;
     s->sel_serial = 0;
@@ -1095,16 +1145,9 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     return KW_OK;
 }
 
-extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const char *header_line,
-                             int32_t url_col, int32_t n_fields, int64_t *n_rows, int32_t *verdict, int64_t *bad_pos,
-                             void *stream)
+// a header line kw_csv_append can be given: no '"' or line break, n_fields names, the column among them
+static bool csv_header_ok(const char *header_line, int32_t url_col, int32_t n_fields)
 {
-    if (!h) return KW_EINVAL;
-    if (!header_line || !n_rows || !verdict || !bad_pos || n_bytes < 0 || (n_bytes > 0 && !d_text)) {
-        h->err = "kw_csv_append: bad arguments";
-        return KW_EINVAL;
-    }
-    if (((uintptr_t)d_text & 15) != 0) { h->err = "kw_csv_append: the text must be 16-byte aligned"; return KW_EINVAL; }
     const size_t hl = strlen(header_line);
     int commas = 0;
     bool plain = hl >= 1 && hl <= 255;
@@ -1113,22 +1156,46 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
         commas += c == ',';
         plain = c != '"' && c != '\n' && c != '\r';
     }
-    if (!plain || n_fields != commas + 1 || url_col < 0 || url_col >= n_fields) {
-        h->err = "kw_csv_append: unsupported header line or column";
-        return KW_EINVAL;
+    return plain && n_fields == commas + 1 && url_col >= 0 && url_col < n_fields;
+}
+
+// The cap on the tile kernels' launch grids: the device's, or the tests' KW_TEST_CSV_GRID in [1, 2048] (read per call
+// through kw_env: the kernels' loops then make several trips on a text of a few tiles).
+static int csv_grid_cap(const kw_dedup *h)
+{
+    if (const char *e = kw_env("KW_TEST_CSV_GRID")) {
+        char *end = nullptr;
+        const long g = strtol(e, &end, 10);
+        if (end != e && *end == '\0' && g >= 1 && g <= 2048) return (int)g;
     }
-    DDCHK(h, hipSetDevice(h->device));
-    kw_cdx_store *s = nullptr;
-    int rc = store_get(h, &s);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
+    return h->cus * 16;
+}
+
+// How csv_parse reads a text: the whole file (kw_csv_append), or one window of a stream (kw_csv_stream_window).
+struct CsvMode {
+    bool window;   // a window: only the bytes before *consumed are judged, a window without rows is not refused
+    bool first;    // the text starts with the header line (record 0)
+    bool final;    // the text's end is the file's end
+};
+
+// kw_csv_append's parse over d_text[0, n_win).  A window (M.window) first finds *consumed, the position after the last
+// '\n' outside quotes (n_win when final), and then runs every pass over [0, *consumed) alone; positions are the text's.
+static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_t n_win, const char *header_line,
+                     int32_t url_col, int32_t n_fields, CsvMode M, int64_t *consumed, int64_t *n_rows,
+                     int32_t *verdict, int64_t *bad_pos, hipStream_t st)
+{
+    int rc;
+    const size_t hl = strlen(header_line);
     *n_rows = 0;
     *verdict = KW_CSV_OK;
     *bad_pos = -1;
+    *consumed = 0;
     auto refuse = [&](int32_t v, int64_t pos) { *verdict = v; *bad_pos = pos; return KW_OK; };
-    if (n_bytes == 0) return refuse(KW_CSV_HEADER, 0);
+    if (n_win == 0) return (M.first && M.final) ? refuse(KW_CSV_HEADER, 0) : KW_OK;
+    if (M.window && M.first && !M.final && n_win < (int64_t)hl + 1) return KW_OK;   // (not yet the header line)
     // ---- '"' bytes per tile, the byte conditions
-    const int64_t ntiles = (n_bytes + TILE - 1) / TILE;
+    int64_t n_bytes = n_win;
+    int64_t ntiles = (n_bytes + TILE - 1) / TILE;
     const size_t tw = up256(8 * (size_t)ntiles);
     rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, 3 * tw + up256(8 * SCAN_CHUNKS) + 256);
     if (rc) return rc;
@@ -1137,28 +1204,44 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     unsigned long long *tile_d = (unsigned long long *)((uint8_t *)s->d_tiles + 2 * tw);
     unsigned long long *chunk = (unsigned long long *)((uint8_t *)s->d_tiles + 3 * tw);
     // small: the totals [0] '"' bytes, [1] record ends, [2] delimiters, [3] record starts, then CsvErrs; [12] a
-    // scan's total
+    // scan's total; [13] a window's consumed bytes
     unsigned long long *small = chunk + up256(8 * SCAN_CHUNKS) / 8;
     CsvErrs *errs = (CsvErrs *)(small + 4);
     DDCHK(h, hipMemsetAsync(small, 0, 32, st));
     DDCHK(h, hipMemsetAsync(small + 4, 0xFF, sizeof(CsvErrs), st));
+    DDCHK(h, hipMemsetAsync(small + 13, 0, 8, st));
     DDCHK(h, hipEventRecord(s->ev[0], st));
-    const int tgrid = (int)std::min<int64_t>(ntiles, (int64_t)h->cus * 16);
+    const int gcap = csv_grid_cap(h);
+    int tgrid = (int)std::min<int64_t>(ntiles, (int64_t)gcap);
     hipLaunchKernelGGL(cv_quotes_kernel, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_q, errs);
     scan_launch(tile_q, ntiles, chunk, small, st);
+    if (M.window && !M.final)
+        hipLaunchKernelGGL(cv_last_end_kernel, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles,
+                           (const unsigned long long *)tile_q, small + 13);
     DDCHK(h, hipGetLastError());
-    unsigned long long hs[10];
+    unsigned long long hs[14];
     uint8_t head[260] = {0};
-    const size_t hn = (size_t)std::min<int64_t>(n_bytes, (int64_t)hl + 2);
     DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipMemcpyAsync(head, d_text, hn, hipMemcpyDeviceToHost, st));
+    DDCHK(h, hipMemcpyAsync(head, d_text, (size_t)std::min<int64_t>(n_bytes, (int64_t)hl + 2), hipMemcpyDeviceToHost, st));
     DDCHK(h, hipStreamSynchronize(st));
-    if (hs[4] != NONE) return refuse(KW_CSV_NUL, (int64_t)hs[4]);
-    if (hs[5] != NONE) return refuse(KW_CSV_UTF8, (int64_t)hs[5]);
-    if (!(hn > hl && memcmp(head, header_line, hl) == 0 &&
-          (head[hl] == '\n' || (head[hl] == '\r' && hn > hl + 1 && head[hl + 1] == '\n'))))
+    if (M.window && !M.final) {
+        // only the records that end inside the window are judged: every pass below runs over [0, consumed)
+        if (hs[13] > (unsigned long long)n_win) { h->err = "kw_csv_stream_window: a record end past the window"; return KW_ESTATE; }
+        n_bytes = (int64_t)hs[13];
+        if (n_bytes == 0) return KW_OK;   // (no record ends here: the caller comes back with more bytes)
+        ntiles = (n_bytes + TILE - 1) / TILE;
+        tgrid = (int)std::min<int64_t>(ntiles, (int64_t)gcap);
+    }
+    const size_t hn = (size_t)std::min<int64_t>(n_bytes, (int64_t)hl + 2);
+    if (hs[4] != NONE && (int64_t)hs[4] < n_bytes) return refuse(KW_CSV_NUL, (int64_t)hs[4]);
+    if (hs[5] != NONE && (int64_t)hs[5] < n_bytes) return refuse(KW_CSV_UTF8, (int64_t)hs[5]);
+    if (M.first && !(hn > hl && memcmp(head, header_line, hl) == 0 &&
+                     (head[hl] == '\n' || (head[hl] == '\r' && hn > hl + 1 && head[hl + 1] == '\n'))))
         return refuse(KW_CSV_HEADER, 0);
-    const bool ends_quoted = (hs[0] & 1ull) != 0;
+    // (a window that is not final ends after a '\n' outside quotes)
+    const bool ends_quoted = (!M.window || M.final) && (hs[0] & 1ull) != 0;
+    const int64_t r0 = M.first ? 1 : 0;
+    *consumed = n_bytes;
     // ---- record ends, delimiters and record starts per tile; the quote discipline, the '\r' rule
     CsvArgs A{};
     A.text = d_text;
@@ -1170,6 +1253,7 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     A.n_starts = small + 3;
     A.errs = errs;
     A.url_col = url_col;
+    A.r0 = (int)r0;
     hipLaunchKernelGGL(cv_tile_kernel<CV_COUNT>, dim3(tgrid), dim3(BLOCK), 0, st, A);
     scan_launch(tile_e, ntiles, chunk, small + 1, st);
     scan_launch(tile_d, ntiles, chunk, small + 2, st);
@@ -1179,11 +1263,12 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     if (hs[6] != NONE || ends_quoted) return refuse(KW_CSV_QUOTE, hs[6] != NONE ? (int64_t)hs[6] : n_bytes);
     if (hs[7] != NONE) return refuse(KW_CSV_CR, (int64_t)hs[7]);
     const int64_t n_ends = (int64_t)hs[1], n_delims = (int64_t)hs[2], n_rec = (int64_t)hs[3];
-    if (n_rec < 1 || n_ends > n_rec || n_ends < n_rec - 1) {   // (the header is a record; the last may end with the text)
+    if (n_rec < r0 || n_ends > n_rec || n_ends < n_rec - 1) {   // (the header is a record; the last may end with the text)
         h->err = "kw_csv_append: record starts and ends do not pair up";
         return KW_ESTATE;
     }
-    const int64_t n_new = n_rec - 1;
+    const int64_t n_new = n_rec - r0;
+    if (n_new == 0 && M.window) return KW_OK;   // (blank lines, or the header alone: kw_csv_stream_end tests the total)
     if (n_new == 0 || s->n + n_new >= ((int64_t)1 << 32)) return refuse(KW_CSV_ROWS, n_bytes);
     // ---- the records located, their cells checked
     const size_t rw = up256(8 * ((size_t)n_rec + 1));
@@ -1198,9 +1283,9 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     DDCHK(h, hipMemsetAsync(s->d_rows, 0, 5 * rw, st));   // (an entry nobody wrote is an empty cell at 0, not a wild one)
     hipLaunchKernelGGL(cv_tile_kernel<CV_ENDS>, dim3(tgrid), dim3(BLOCK), 0, st, A);
     hipLaunchKernelGGL(cv_tile_kernel<CV_CELLS>, dim3(tgrid), dim3(BLOCK), 0, st, A);
-    hipLaunchKernelGGL(cv_rows_kernel, dim3(grid_for(h, n_new)), dim3(BLOCK), 0, st, d_text, n_bytes, n_rec, n_ends,
-                       n_delims, (int)n_fields, (int)url_col, (const int64_t *)A.rec_start, (const int64_t *)A.end_pos,
-                       (const int64_t *)A.end_dcnt, A.cell_start, A.cell_end, errs);
+    hipLaunchKernelGGL(cv_rows_kernel, dim3(std::min(grid_for(h, n_new), gcap)), dim3(BLOCK), 0, st, d_text, n_bytes, r0,
+                       n_rec, n_ends, n_delims, (int)n_fields, (int)url_col, (const int64_t *)A.rec_start,
+                       (const int64_t *)A.end_pos, (const int64_t *)A.end_dcnt, A.cell_start, A.cell_end, errs);
     DDCHK(h, hipGetLastError());
     DDCHK(h, hipEventRecord(s->ev[1], st));
     DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -1216,8 +1301,8 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
         if (rc) return rc;
         s->rows_cap = cap / 8;
     }
-    const int64_t *url_pos = A.cell_start + 1;
-    unsigned long long *url_len = (unsigned long long *)(A.cell_end + 1);
+    const int64_t *url_pos = A.cell_start + r0;
+    unsigned long long *url_len = (unsigned long long *)(A.cell_end + r0);
     unsigned long long *grand = small + 12;
     DDCHK(h, hipMemsetAsync(s->ts + s->n, 0, 8 * (size_t)n_new, st));
     scan_launch(url_len, n_new, chunk, grand, st);
@@ -1246,6 +1331,116 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     s->sel_serial = 0;
     s->sel_ready = false;
     *n_rows = n_new;
+    return KW_OK;
+}
+
+extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const char *header_line,
+                             int32_t url_col, int32_t n_fields, int64_t *n_rows, int32_t *verdict, int64_t *bad_pos,
+                             void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (!header_line || !n_rows || !verdict || !bad_pos || n_bytes < 0 || (n_bytes > 0 && !d_text)) {
+        h->err = "kw_csv_append: bad arguments";
+        return KW_EINVAL;
+    }
+    if (((uintptr_t)d_text & 15) != 0) { h->err = "kw_csv_append: the text must be 16-byte aligned"; return KW_EINVAL; }
+    if (!csv_header_ok(header_line, url_col, n_fields)) {
+        h->err = "kw_csv_append: unsupported header line or column";
+        return KW_EINVAL;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    if (s->stream_open) { h->err = "kw_csv_append: a kw_csv_stream is open"; return KW_ESTATE; }
+    int64_t consumed = 0;
+    return csv_parse(h, s, d_text, n_bytes, header_line, url_col, n_fields, CsvMode{false, true, true}, &consumed, n_rows,
+                     verdict, bad_pos, (hipStream_t)stream);
+}
+
+// ---- the windowed form: kw_csv_stream_begin / _window / _end (the contract: include/kwdedup.h)
+static void store_changed(kw_cdx_store *s)
+{
+    s->run_serial = 0;
+    s->csv_ready = false;
+    s->sel_serial = 0;
+    s->sel_ready = false;
+}
+
+extern "C" int kw_csv_stream_begin(kw_dedup *h, const char *header_line, int32_t url_col, int32_t n_fields)
+{
+    if (!h) return KW_EINVAL;
+    if (!header_line || !csv_header_ok(header_line, url_col, n_fields)) {
+        h->err = "kw_csv_stream_begin: unsupported header line or column";
+        return KW_EINVAL;
+    }
+    kw_cdx_store *s = nullptr;
+    int rc = store_get(h, &s);
+    if (rc) return rc;
+    if (s->stream_open) { h->err = "kw_csv_stream_begin: a stream is open"; return KW_ESTATE; }
+    s->stream_open = true;
+    s->stream_first = true;
+    s->stream_final = s->stream_bad = false;
+    s->stream_header = header_line;
+    s->stream_col = url_col;
+    s->stream_fields = n_fields;
+    s->stream_n0 = s->n;
+    s->stream_bytes0 = s->n_bytes;
+    s->stream_pos = 0;
+    return KW_OK;
+}
+
+extern "C" int kw_csv_stream_window(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, int32_t final, int64_t *consumed,
+                                    int64_t *n_rows, int32_t *verdict, int64_t *bad_pos, void *stream)
+{
+    if (!h) return KW_EINVAL;
+    if (!consumed || !n_rows || !verdict || !bad_pos || n_bytes < 0 || (n_bytes > 0 && !d_text)) {
+        h->err = "kw_csv_stream_window: bad arguments";
+        return KW_EINVAL;
+    }
+    if (((uintptr_t)d_text & 15) != 0) { h->err = "kw_csv_stream_window: the text must be 16-byte aligned"; return KW_EINVAL; }
+    kw_cdx_store *s = h->cdx;
+    if (!s || !s->stream_open || s->stream_final || s->stream_bad) {
+        h->err = "kw_csv_stream_window: no open stream, or one that has had its final or a refused window";
+        return KW_ESTATE;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    const int rc = csv_parse(h, s, d_text, n_bytes, s->stream_header.c_str(), s->stream_col, s->stream_fields,
+                             CsvMode{true, s->stream_first, final != 0}, consumed, n_rows, verdict, bad_pos,
+                             (hipStream_t)stream);
+    if (rc != KW_OK || *verdict != KW_CSV_OK) {
+        s->stream_bad = true;   // (kw_csv_stream_end puts the store back)
+        *consumed = 0;
+        if (rc == KW_OK) *bad_pos += s->stream_pos;
+        return rc;
+    }
+    if (*consumed > 0) s->stream_first = false;
+    s->stream_pos += *consumed;
+    s->stream_final = final != 0;
+    return KW_OK;
+}
+
+extern "C" int kw_csv_stream_end(kw_dedup *h, int32_t commit, int64_t *n_rows_total)
+{
+    if (!h) return KW_EINVAL;
+    kw_cdx_store *s = h->cdx;
+    if (!s || !s->stream_open) { h->err = "kw_csv_stream_end: no open stream"; return KW_ESTATE; }
+    s->stream_open = false;
+    if (n_rows_total) *n_rows_total = 0;
+    const int64_t added = s->n - s->stream_n0;
+    const bool keep = commit != 0 && !s->stream_bad && s->stream_final && added > 0;
+    if (!keep) {
+        // off[stream_n0] still holds stream_bytes0: the rows noted by kw_csv_stream_begin are the store again
+        s->n = s->stream_n0;
+        s->n_bytes = s->stream_bytes0;
+        store_changed(s);
+        if (commit != 0 && !s->stream_bad && !s->stream_final) {
+            h->err = "kw_csv_stream_end: commit before the final window";
+            return KW_ESTATE;
+        }
+        return (commit != 0 && !s->stream_bad) ? KW_CSV_ROWS : KW_OK;
+    }
+    if (n_rows_total) *n_rows_total = added;
     return KW_OK;
 }
 
@@ -1281,6 +1476,23 @@ extern "C" int kw_cdx_run_exclude(kw_dedup *h, int64_t n_exclude, void *stream)
 extern "C" int kw_cdx_run_exclude_unique(kw_dedup *h, int64_t n_exclude, void *stream)
 {
     return run_exclude(h, n_exclude, true, stream);
+}
+
+extern "C" int kw_cdx_exclude_distinct_seen(kw_dedup *h, int64_t *n_distinct_seen, int64_t *n_exclude_kept, void *stream)
+{
+    if (!h || !n_distinct_seen || !n_exclude_kept) return KW_EINVAL;
+    kw_cdx_store *s = h->cdx;
+    if (!s || h->ex_serial == 0 || h->ex_serial != h->run_serial || s->sel_serial != h->run_serial) {
+        h->err = "kw_cdx_exclude_distinct_seen: the last run was not kw_cdx_run_exclude";
+        return KW_ESTATE;
+    }
+    DDCHK(h, hipSetDevice(h->device));
+    int64_t out[2] = {0, 0};
+    const int rc = kw_dedup_distinct_seen(h, s->arena, s->n - h->ex_links, s->code, out, (hipStream_t)stream);
+    if (rc) return rc;
+    *n_distinct_seen = out[0];
+    *n_exclude_kept = out[1];
+    return KW_OK;
 }
 
 extern "C" int kw_cdx_exclude_codes(kw_dedup *h, uint8_t *d_code, void *stream)

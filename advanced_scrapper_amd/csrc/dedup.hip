@@ -42,6 +42,10 @@
 //                        run over exclude rows followed by link rows, a duplicate
 //                        link row is dropped iff its tag's first row in the table
 //                        holds its bytes and is an exclude row.
+//   dd_seen_marks_kernel the distinct URLs among the link rows that were seen
+//                        (kw_cdx_exclude_distinct_seen): every such row marks
+//                        its first holder's bit; dd_count_kept_kernel counts
+//                        the exclude rows the run kept.
 //
 // All byte/integer work: the roofline is HBM bandwidth; the table's random
 // atomics bound the insert.
@@ -1541,6 +1545,55 @@ __global__ __launch_bounds__(BLOCK) void dd_exclude_kernel(const uint8_t *__rest
     if ((threadIdx.x & 63) == 0 && n_seen) atomicAdd(&S.cnt[12], (unsigned long long)n_seen);
 }
 
+// ---- the distinct URLs among the SEEN link rows (kw_cdx_exclude_distinct_seen): after the set-difference pass a
+// link row coded KW_URL_SEEN (lane = row) finds its first holder among the exclude rows as dd_exclude_kernel did and
+// sets that row's bit in marks (m bits, zeroed); a bit that was clear counts one URL (out[0]).  The holder's index
+// is checked before it is used.  A row whose tag's holder has other bytes is listed for the host (out[1] rows listed,
+// in `listed`, cap entries), which knows its first holder from the run's exact pass.
+__global__ __launch_bounds__(BLOCK) void dd_seen_marks_kernel(const uint8_t *__restrict__ arena,
+                                                              const uint8_t *__restrict__ code, Scratch S, int64_t m,
+                                                              int64_t n, uint32_t *__restrict__ marks,
+                                                              unsigned long long *__restrict__ out,
+                                                              uint32_t *__restrict__ listed, uint32_t cap)
+{
+    uint32_t fresh = 0;
+    for (int64_t i = m + (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        if (code[i] != KW_URL_SEEN) continue;
+        const RowGen gi = row_gen(S, arena, i);
+        const uint64_t h = row_hash(S, gi);
+        uint64_t slot = (h ^ (h >> 29)) & S.mask;
+        unsigned long long cur = 0;
+        const uint32_t want = (uint32_t)((h >> 40) << 8) | S.epoch;
+        bool found = false;
+        for (uint64_t step = 0; step <= S.mask; ++step) {   // (the row's own insert found or left its tag on this path)
+            cur = S.table[slot];
+            if ((uint32_t)(cur >> 32) == want) { found = true; break; }
+            slot = (slot + 1) & S.mask;
+        }
+        const uint32_t r0 = (uint32_t)cur - 1u;
+        if (found && (int64_t)r0 < m && same_url(gi, row_gen(S, arena, r0))) {
+            const uint32_t bit = 1u << (r0 & 31u);
+            fresh += (atomicOr(&marks[r0 >> 5], bit) & bit) == 0u;
+        } else {
+            const unsigned long long k = atomicAdd(&out[1], 1ull);   // (rare)
+            if (k < cap) listed[k] = (uint32_t)i;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) fresh += __shfl_xor(fresh, d, 64);
+    if ((threadIdx.x & 63) == 0 && fresh) atomicAdd(&out[0], (unsigned long long)fresh);
+}
+
+// the exclude rows the keep-first run coded KW_URL_KEPT: the distinct strings of the exclude file
+__global__ __launch_bounds__(BLOCK) void dd_count_kept_kernel(const uint8_t *__restrict__ code, int64_t m,
+                                                              unsigned long long *__restrict__ out)
+{
+    uint32_t c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < m; i += (int64_t)gridDim.x * BLOCK)
+        c += code[i] == KW_URL_KEPT;
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
+}
+
 }  // namespace dd
 
 using namespace dd;
@@ -1966,6 +2019,83 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
     h->ex_dup = h->ex_links - h->ex_seen - h->n_kept;   // (0 unless unique: every link row not seen stays)
     h->ex_serial = h->run_serial;
     return KW_OK;
+}
+
+// After kw_dedup_exclude_pass over the same rows: out[0] the distinct strings among the link rows coded KW_URL_SEEN,
+// out[1] the exclude rows the keep-first run coded KW_URL_KEPT.
+int kw_dedup_distinct_seen(kw_dedup *h, const uint8_t *d_arena, int64_t m, const uint8_t *d_code, int64_t *out,
+                           hipStream_t st)
+{
+    const int64_t n = h->n;
+    out[0] = out[1] = 0;
+    if (m <= 0 || m > n) return KW_OK;
+    const uint32_t cap = 1024;
+    const size_t words = (size_t)((m + 31) / 32);
+    uint8_t *buf = nullptr;   // [0, 32): the counters (listed rows' bits, rows listed, kept exclude rows); the list; the marks
+    const size_t marks_at = 32 + 4 * (size_t)cap;
+    DDCHK(h, hipMalloc((void **)&buf, marks_at + 4 * words));
+    auto done = [&](int rc) { (void)hipFree(buf); return rc; };
+    unsigned long long *cnt = (unsigned long long *)buf;
+    uint32_t *listed = (uint32_t *)(buf + 32), *marks = (uint32_t *)(buf + marks_at);
+    hipError_t e = hipMemsetAsync(buf, 0, marks_at + 4 * words, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(dd_count_kept_kernel, dim3((int)std::min<int64_t>((m + BLOCK - 1) / BLOCK, (int64_t)h->cus * 8)),
+                           dim3(BLOCK), 0, st, d_code, m, cnt + 2);
+        if (n > m)
+            hipLaunchKernelGGL(dd_seen_marks_kernel,
+                               dim3((int)std::min<int64_t>((n - m + BLOCK - 1) / BLOCK, (int64_t)h->cus * 8)), dim3(BLOCK), 0,
+                               st, d_arena, d_code, h->S, m, n, marks, cnt, listed, cap);
+        e = hipGetLastError();
+    }
+    unsigned long long hc[3] = {0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        h->err = std::string("HIP error ") + hipGetErrorString(e) + " in kw_cdx_exclude_distinct_seen";
+        return done(KW_EHIP);
+    }
+    int64_t distinct = (int64_t)hc[0];
+    if (hc[1]) {
+        // the listed rows: their first holders from the host's exact pass of the run, as kw_dedup_exclude_pass
+        std::vector<uint32_t> rows;
+        if (hc[1] <= cap) {
+            rows.resize(hc[1]);
+            e = hipMemcpy(rows.data(), listed, 4 * (size_t)hc[1], hipMemcpyDeviceToHost);
+        } else {
+            std::vector<uint8_t> code((size_t)(n - m));
+            e = hipMemcpy(code.data(), d_code + m, (size_t)(n - m), hipMemcpyDeviceToHost);
+            for (int64_t i = 0; i < n - m; ++i)
+                if (code[i] == KW_URL_SEEN) rows.push_back((uint32_t)(m + i));   // (a row marked twice counts once)
+        }
+        std::vector<uint32_t> hm(words);
+        if (e == hipSuccess) e = hipMemcpy(hm.data(), marks, 4 * words, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            h->err = std::string("HIP error ") + hipGetErrorString(e) + " in kw_cdx_exclude_distinct_seen";
+            return done(KW_EHIP);
+        }
+        std::sort(rows.begin(), rows.end());
+        std::vector<uint32_t> len;
+        std::vector<uint64_t> boff;
+        std::vector<uint8_t> bytes;
+        int rc = fetch_rows(h, d_arena, nullptr, rows, st, len, boff, bytes);
+        if (rc) return done(rc);
+        for (size_t q = 0; q < rows.size(); ++q) {
+            const auto it = h->collide_first.find(std::string((const char *)bytes.data() + boff[q], len[q]));
+            if (it == h->collide_first.end()) {
+                if (hc[1] > cap) continue;   // (a row of the scan that the kernel had marked itself)
+                h->err = "kw_cdx_exclude_distinct_seen: a row without a first holder";
+                return done(KW_ESTATE);
+            }
+            const int64_t f = (int64_t)it->second;
+            if (f < 0 || f >= m) { h->err = "kw_cdx_exclude_distinct_seen: a first holder outside the exclude rows"; return done(KW_ESTATE); }
+            const uint32_t bit = 1u << (f & 31);
+            distinct += (hm[(size_t)f >> 5] & bit) == 0u;
+            hm[(size_t)f >> 5] |= bit;
+        }
+    }
+    out[0] = distinct;
+    out[1] = (int64_t)hc[2];
+    return done(KW_OK);
 }
 
 static int exclude_state(kw_dedup *h, const char *who)

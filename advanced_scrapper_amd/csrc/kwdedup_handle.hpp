@@ -89,7 +89,12 @@ struct kw_dedup {
 // codes): the first m rows are the exclude rows; unique: repeats among the link rows are dropped too
 int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_t *d_code, bool unique, hipStream_t st);
 
-#define DDCHK(h, x)                                                                    \
+// dedup.hip: after kw_dedup_exclude_pass over the same rows, out[0] = the distinct strings among the link rows coded
+// KW_URL_SEEN, out[1] = the exclude rows the keep-first run coded KW_URL_KEPT
+int kw_dedup_distinct_seen(kw_dedup *h, const uint8_t *d_arena, int64_t m, const uint8_t *d_code, int64_t *out,
+                           hipStream_t st);
+
+#define DDCHK(h, x)                                                                   \
     do {                                                                               \
         hipError_t e_ = (x);                                                           \
         if (e_ != hipSuccess) {                                                        \

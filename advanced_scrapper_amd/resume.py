@@ -12,6 +12,10 @@ The device parser is used only where its result provably equals ``pd.read_csv(fi
 DESIGN.md §7, tests/resume_rule.py).  A file it refuses, and everything under ``KW_RESUME_NATIVE=0``, sends the whole
 call down the reference's pandas lines, so its exceptions and messages stay as they are (a missing links file
 included).  What ``csv.writer`` / ``csv.DictWriter`` write is always eligible.
+
+A file of ``stream_from`` bytes or more goes to the device window by window
+(``cdx_dedup.GpuUrlDedup.csv_append_file``: two pinned slots of ``window_bytes``, a reader thread one window ahead), so
+host and device memory for text do not depend on the file's size; ``Resume.windows`` holds the windows each file took.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _native, cdx_dedup
+from .links import MAX_RECORD_BYTES, STREAM_FROM, WINDOW_BYTES   # (the streamed route's geometry and threshold)
 
 SUCCESS_FIELDS = ["url", "datetime", "ticker_symbols", "author", "source", "source_url", "title", "article"]
 FAILED_FIELDS = ["url", "error"]
@@ -31,12 +36,14 @@ class Resume:
     """What the reference knows after :312-360."""
 
     def __init__(self, initial_total: int, scraped_success: int, scraped_fails: int, remaining: int, route: str,
-                 urls: Optional[List[str]] = None, arrays: Optional[Tuple[np.ndarray, np.ndarray]] = None):
+                 urls: Optional[List[str]] = None, arrays: Optional[Tuple[np.ndarray, np.ndarray]] = None,
+                 windows: Tuple[int, int, int] = (0, 0, 0)):
         self.initial_total = initial_total      # rows of the links file
         self.scraped_success = scraped_success  # rows of the success file (0: missing)
         self.scraped_fails = scraped_fails      # rows of the failed file (0: missing)
         self.remaining = remaining              # links whose URL is in neither
         self.route = route                      # 'device' or 'pandas'
+        self.windows = windows                  # the windows the success, failed and links files took (0: one piece)
         self._urls, self._arrays = urls, arrays
 
     def arrays(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -97,39 +104,54 @@ def _pandas_route(links_csv: str, success_csv: str, failed_csv: str) -> Resume:
     return Resume(initial_total, scraped_success, scraped_fails, len(urls), 'pandas', urls=urls)
 
 
-def _device_route(links_csv: str, success_csv: str, failed_csv: str) -> Optional[Resume]:
+def _device_route(links_csv: str, success_csv: str, failed_csv: str, stream_from: int = STREAM_FROM,
+                  window_bytes: int = WINDOW_BYTES, max_record_bytes: int = MAX_RECORD_BYTES) -> Optional[Resume]:
     """The result when every file there is is eligible, else None."""
     if not os.path.exists(links_csv):
         return None   # (the pandas route raises the reference's error)
     files = [(success_csv, SUCCESS_FIELDS), (failed_csv, FAILED_FIELDS), (links_csv, LINKS_FIELDS)]
     g = None
-    rows = []
+    rows, windows = [], [0, 0, 0]
     for k, (path, fields) in enumerate(files):
         if k < 2 and not os.path.exists(path):
             rows.append(0)
             continue
-        data = cdx_dedup._file_bytes(path)
-        if data is None or not len(data):
+        try:
+            size = os.path.getsize(path)
+        except OSError:
+            return None
+        data = None
+        if size < stream_from:
+            data = cdx_dedup._file_bytes(path)
+            size = 0 if data is None else len(data)
+        if not size:
             return None
         if g is None:
             g = cdx_dedup._dedup()
             g.cdx_begin()
-        verdict, _, n = g.csv_append(data, ','.join(fields), fields.index('url'))
+        if data is None:
+            verdict, n, stats = g.csv_append_file(path, ','.join(fields), fields.index('url'), window_bytes,
+                                                  max_record_bytes)
+            windows[k] = stats['windows']
+        else:
+            verdict, _, n = g.csv_append(data, ','.join(fields), fields.index('url'))
         if verdict != _native.KW_CSV_OK:
             return None
         rows.append(n)
     n_links, _, remaining = g.run_exclude(rows[0] + rows[1])
     b, off, _ = g.remaining()
-    return Resume(n_links, rows[0], rows[1], remaining, 'device', arrays=(b, off))
+    return Resume(n_links, rows[0], rows[1], remaining, 'device', arrays=(b, off), windows=tuple(windows))
 
 
 def remaining_urls(links_csv: str = 'yfin_urls.csv', website: str = 'yfin', success_csv: Optional[str] = None,
-                   failed_csv: Optional[str] = None) -> Resume:
+                   failed_csv: Optional[str] = None, *, stream_from: int = STREAM_FROM,
+                   window_bytes: int = WINDOW_BYTES, max_record_bytes: int = MAX_RECORD_BYTES) -> Resume:
     """constant_rate_scrapper.py:312-360: the links whose URL is in neither the success nor the failed file, with
     the reference's counts (rows, not unique URLs) and its three printed lines."""
     success_csv = success_csv or f"success_articles_{website}.csv"
     failed_csv = failed_csv or f"failed_articles_{website}.csv"
-    res = _device_route(links_csv, success_csv, failed_csv) if native_enabled() else None
+    res = _device_route(links_csv, success_csv, failed_csv, stream_from, window_bytes,
+                        max_record_bytes) if native_enabled() else None
     if res is None:
         res = _pandas_route(links_csv, success_csv, failed_csv)
     print(f"Total URLs in CSV: {res.initial_total}")

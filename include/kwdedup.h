@@ -188,6 +188,46 @@ int kw_cdx_tile_bytes(void);
 int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, const char *header_line, int32_t url_col,
                   int32_t n_fields, int64_t *n_rows, int32_t *verdict, int64_t *bad_pos, void *stream);
 
+/* ---- kw_csv_append window by window: a file of any size through device texts of a fixed size
+ *
+ * kw_csv_stream_begin takes kw_csv_append's header arguments, notes the store's rows and bytes and sets the stream's
+ * file position to 0.  One stream a handle at a time; kw_csv_append and a second begin return KW_ESTATE while one is
+ * open, kw_cdx_begin drops it.
+ *
+ * kw_csv_stream_window parses one window (alignment and readable bytes as kw_csv_append).  The text begins at a record
+ * start outside quotes: the first window with the header line, every later one at the byte where the previous
+ * window's *consumed ended.  *consumed is the position after the terminator of the last record that ends inside the
+ * window, outside quotes (after the last '\n' outside quotes); with final != 0 it is n_bytes, and the end of the text
+ * ends a record that has bytes.  A window that is not final and holds no record end gives *consumed = 0, verdict OK and
+ * no rows: the caller comes back with more bytes.  So does a first window that is not final and is shorter than the
+ * header line plus one terminator byte.
+ *
+ * Only the bytes before *consumed are judged, by kw_csv_append's conditions in its order, except that
+ *   - HEADER is tested in the first window only (the first with *consumed > 0);
+ *   - "the text ends inside quotes" is tested at a final window only;
+ *   - ROWS is tested against the store's running total; "no record after the header" is kw_csv_stream_end's;
+ *   - an offender at or beyond *consumed belongs to the next window (the bytes of a UTF-8 sequence the window cuts, a
+ *     '\r' or a closing '"' that is the window's last byte): the first NUL and the first UTF-8 offender of the window
+ *     count iff they lie before *consumed;
+ *   - *bad_pos is a position in the file: the sum of the *consumed so far plus the offender's position in the window.
+ * After a verdict other than OK, a KW_E* code or a final window the stream takes no more windows (KW_ESTATE).
+ *
+ * kw_csv_stream_end closes the stream.  With commit = 0, or after a window that was refused or failed, the store is
+ * put back to the rows and bytes noted by begin and the call returns KW_OK (*n_rows_total = 0).  With commit != 0
+ * after OK windows the last of which was final it returns KW_OK and the rows the stream appended, or, when it appended
+ * none, the positive code KW_CSV_ROWS (the one-piece call's verdict for "no record after the header"; KW_E* codes are
+ * negative, so the return value names it without a verdict parameter).  commit != 0 before a final window: KW_ESTATE,
+ * the store put back.
+ *
+ * For a text cut into windows in this way, at any window sizes: every verdict is OK iff kw_csv_append over the whole
+ * text says OK, and the store then holds exactly the same rows (arena bytes, offsets, timestamps 0); for a text with
+ * one single offender the code and file position equal the whole-text call's ("Windowed CSV append").
+ * kw_cdx_last_ms [0] and [1] go on summing over the windows. */
+int kw_csv_stream_begin(kw_dedup *h, const char *header_line, int32_t url_col, int32_t n_fields);
+int kw_csv_stream_window(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes, int32_t final, int64_t *consumed,
+                         int64_t *n_rows, int32_t *verdict, int64_t *bad_pos, void *stream);
+int kw_csv_stream_end(kw_dedup *h, int32_t commit, int64_t *n_rows_total);
+
 /* per-row code of a link row of kw_cdx_run_exclude whose string is among the exclude rows (KW_URL_* above are
  * 0..3; libkwmatch keeps 4 for itself) */
 #define KW_URL_SEEN 5
@@ -230,6 +270,14 @@ int kw_cdx_exclude_last_ms(kw_dedup *h, float *ms, int32_t k);
  * kw_cdx_run_exclude). */
 int kw_cdx_run_exclude_unique(kw_dedup *h, int64_t n_exclude, void *stream);
 int kw_cdx_exclude_duplicates(kw_dedup *h, int64_t *n_duplicate);
+
+/* The unique-URL counts of experiental/new_links.py (len(set(...))), after kw_cdx_run_exclude or
+ * kw_cdx_run_exclude_unique: *n_distinct_seen = the distinct strings among the link rows coded KW_URL_SEEN (each such
+ * row marks its first holder among the exclude rows, every index checked before use; the marks are counted),
+ * *n_exclude_kept = the exclude rows the keep-first run coded KW_URL_KEPT (the distinct strings of the exclude rows).
+ * With kw_dedup_counts' KEPT total U over the union: the link rows hold U - *n_exclude_kept + *n_distinct_seen
+ * distinct strings, of which U - *n_exclude_kept are in no exclude row.  Returns when both are final. */
+int kw_cdx_exclude_distinct_seen(kw_dedup *h, int64_t *n_distinct_seen, int64_t *n_exclude_kept, void *stream);
 
 /* The "surviving rows" of the last run over the store are kw_cdx_run's kept rows, kw_cdx_run_exclude's remaining
  * rows or kw_cdx_run_exclude_unique's KEPT rows: n of them (kw_dedup_kept_size), numbered in row order.  The three

@@ -18,6 +18,13 @@ host argsort time on its own line, and the select copy's bytes in + out over its
 (kw_cdx_csv_copy over the same links file, after the clocks stopped).
 
     python scripts/e2e_links.py [--rows 1000000] [--out profiles/e2e_links.json]
+
+``--stream`` measures the streamed route instead ("Windowed CSV append") and writes
+profiles/e2e_links_stream.json: over the same workload, one after the other in one call, the one-piece route
+(``stream_from`` above any size), the streamed route with ``stream_from=0`` at the default window and at a
+64 MiB window, and, with ``--parent-tree DIR`` (a built checkout of the parent commit), that tree's route.  With
+``--pandas`` the pandas route runs too (the large-input comparison: ``--rows 10000000 --runs 1``).  Every
+configuration must write the same bytes; each child reports its peak resident memory (``ru_maxrss``).
 """
 import argparse
 import csv
@@ -32,7 +39,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARTS = 4
 
 CHILD = r'''
-import hashlib, json, os, sys, time
+import hashlib, json, os, resource, sys, time
 tree, folder = sys.argv[1:3]
 sys.path.insert(0, tree)
 os.chdir(folder)
@@ -51,14 +58,16 @@ def timed_order(keys):
     return r
 links.descending_order = timed_order
 sys.stdout = open(os.devnull, 'w')
+kw = {k: int(os.environ[e]) for k, e in (('stream_from', 'E2E_STREAM_FROM'), ('window_bytes', 'E2E_WINDOW_BYTES'))
+      if e in os.environ}
 t0 = time.perf_counter()
-a = links.refresh_links()
+a = links.refresh_links(**kw)
 t1 = time.perf_counter()
 spans_a = None
 if a.route == 'device':
     spans_a = {'cdx_last_ms': g.cdx_last_ms(), 'exclude_last_ms': g.exclude_last_ms(), 'select_last_ms': g.select_last_ms()}
 t2 = time.perf_counter()
-b = links.split_links('yahoo_links_new.csv', 'part', %d, 'success_articles_yfin.csv')
+b = links.split_links('yahoo_links_new.csv', 'part', %d, 'success_articles_yfin.csv', **kw)
 t3 = time.perf_counter()
 sys.stdout = sys.__stdout__
 spans_b = None
@@ -72,7 +81,9 @@ for name in ['yahoo_links_new.csv'] + ['part_%%d.csv' %% i for i in range(%d)]:
     sha.update(data)
     sizes.append(len(data))
 res = {'refresh_s': t1 - t0, 'split_s': t3 - t2, 'routes': [a.route, b.route], 'refresh_counts': list(a.counts()),
-       'split_counts': list(b.counts()), 'split_parts': b.parts, 'sha256': sha.hexdigest(), 'out_bytes': sizes}
+       'split_counts': list(b.counts()), 'split_parts': b.parts, 'sha256': sha.hexdigest(), 'out_bytes': sizes,
+       'windows': [list(getattr(a, 'windows', ())), list(getattr(b, 'windows', ()))],
+       'maxrss_kb': resource.getrusage(resource.RUSAGE_SELF).ru_maxrss}
 if spans_a and spans_b:
     res['refresh_spans'], res['split_spans'] = spans_a, spans_b
     res['argsort_s'] = argsort_s[0]
@@ -119,14 +130,15 @@ def write_workload(folder, rows, seed):
     return {f: os.path.getsize(os.path.join(folder, f)) for f in sorted(os.listdir(folder))}
 
 
-def run_config(folder, env_extra, runs):
+def run_config(folder, env_extra, runs, tree=REPO):
     env = dict(os.environ)
-    env.pop('KW_LINKS_NATIVE', None)
+    for k in ('KW_LINKS_NATIVE', 'E2E_STREAM_FROM', 'E2E_WINDOW_BYTES'):
+        env.pop(k, None)
     env.update(env_extra)
     got = []
     for _ in range(runs + 1):   # the first is the warm-up
-        p = subprocess.run([sys.executable, '-c', CHILD, REPO, folder], env=env, cwd=REPO, capture_output=True,
-                           text=True, timeout=900)
+        p = subprocess.run([sys.executable, '-c', CHILD, tree, folder], env=env, cwd=tree, capture_output=True,
+                           text=True, timeout=1500)
         if p.returncode != 0:
             raise RuntimeError(f"child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
         line = [ln for ln in p.stdout.splitlines() if ln.startswith('E2E_LINKS ')][-1]
@@ -138,7 +150,8 @@ def run_config(folder, env_extra, runs):
     last = timed[-1]
     res = {'env': env_extra, 'routes': last['routes'], 'refresh_counts': last['refresh_counts'],
            'split_counts': last['split_counts'], 'split_parts': last['split_parts'], 'sha256': last['sha256'],
-           'out_bytes': last['out_bytes']}
+           'out_bytes': last['out_bytes'], 'windows': last['windows'],
+           'peak_rss_MB': max(r['maxrss_kb'] for r in timed) / 1024.0}
     for key in ('refresh_s', 'split_s'):
         v = [r[key] for r in timed]
         res[key] = {'runs': v, 'median_s': statistics.median(v), 'min_s': min(v), 'max_s': max(v)}
@@ -157,13 +170,50 @@ def run_config(folder, env_extra, runs):
     return res
 
 
+def stream_main(args):
+    """--stream: the streamed route against the one-piece route (and the parent's, and pandas)."""
+    out = args.out or os.path.join(REPO, 'profiles', 'e2e_links_stream.json')
+    with tempfile.TemporaryDirectory(prefix='e2e_links_', dir=args.tmp) as tmp:
+        sizes = write_workload(tmp, args.rows, args.seed)
+        res = {'rows': args.rows, 'seed': args.seed, 'num_parts': PARTS, 'input_bytes': sizes,
+               'runs_per_config': args.runs,
+               'timed': 'links.refresh_links() and links.split_links() in a fresh child per run, GPU initialised and '
+                        'handle created before the clocks; 1 warm-up + the median of the runs; the configurations one '
+                        'after the other in one call'}
+        configs = [('one_piece', {'E2E_STREAM_FROM': str(1 << 62)}, REPO), ('streamed', {'E2E_STREAM_FROM': '0'}, REPO),
+                   ('streamed_64MiB', {'E2E_STREAM_FROM': '0', 'E2E_WINDOW_BYTES': str(64 << 20)}, REPO)]
+        if args.parent_tree:
+            configs.append(('parent', {}, os.path.abspath(args.parent_tree)))
+        if args.pandas:
+            configs.append(('pandas', {'KW_LINKS_NATIVE': '0'}, REPO))
+        for name, env, tree in configs:
+            res[name] = run_config(tmp, env, args.runs, tree)
+    res['same_result'] = len({res[name]['sha256'] for name, _, _ in configs}) == 1
+    for call in ('refresh', 'split'):
+        res['streamed_over_one_piece_' + call] = (res['streamed'][call + '_s']['median_s'] /
+                                                  res['one_piece'][call + '_s']['median_s'])
+    with open(out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res))
+    if not res['same_result']:
+        sys.exit('the configurations wrote different bytes')
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--rows', type=int, default=1_000_000)
     ap.add_argument('--seed', type=int, default=20240229)
     ap.add_argument('--runs', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'e2e_links.json'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--stream', action='store_true', help='measure the streamed route (see above)')
+    ap.add_argument('--parent-tree', default=None, help='--stream: a built checkout of the parent commit')
+    ap.add_argument('--pandas', action='store_true', help='--stream: the pandas route too')
+    ap.add_argument('--tmp', default=None, help='--stream: where the workload is written')
     args = ap.parse_args()
+    if args.stream:
+        return stream_main(args)
+    args.out = args.out or os.path.join(REPO, 'profiles', 'e2e_links.json')
     with tempfile.TemporaryDirectory(prefix='e2e_links_') as tmp:
         sizes = write_workload(tmp, args.rows, args.seed)
         res = {'rows': args.rows, 'seed': args.seed, 'num_parts': PARTS, 'input_bytes': sizes,

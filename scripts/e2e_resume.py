@@ -18,6 +18,12 @@ compaction of kw_csv_append, the keep-first run, the set-difference pass, the re
 CSV bytes over the parse + compaction time.
 
     python scripts/e2e_resume.py [--rows 1000000] [--out profiles/e2e_resume.json]
+
+``--stream`` measures the streamed route instead ("Windowed CSV append") and writes
+profiles/e2e_resume_stream.json: over the same workload, one after the other in one call, the one-piece route, the
+streamed route with ``stream_from=0`` at the default window and at a 64 MiB window, and, with ``--parent-tree DIR`` (a
+built checkout of the parent commit), that tree's route; ``--pandas`` adds the pandas route.  Every configuration
+must give the same URLs; each child reports its peak resident memory (``ru_maxrss``).
 """
 import argparse
 import csv
@@ -31,7 +37,7 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CHILD = r'''
-import hashlib, json, os, sys, time
+import hashlib, json, os, resource, sys, time
 tree, folder = sys.argv[1:3]
 sys.path.insert(0, tree)
 os.chdir(folder)
@@ -41,15 +47,18 @@ torch.cuda.init()
 g = cdx_dedup._dedup()
 torch.cuda.synchronize()
 sys.stdout = open(os.devnull, 'w')
+kw = {k: int(os.environ[e]) for k, e in (('stream_from', 'E2E_STREAM_FROM'), ('window_bytes', 'E2E_WINDOW_BYTES'))
+      if e in os.environ}
 t0 = time.perf_counter()
-r = resume.remaining_urls()
+r = resume.remaining_urls(**kw)
 t1 = time.perf_counter()
 urls = r.urls()
 t2 = time.perf_counter()
 sys.stdout = sys.__stdout__
 res = {'seconds': t1 - t0, 'seconds_with_urls': t2 - t0, 'route': r.route,
        'counts': [r.initial_total, r.scraped_success, r.scraped_fails, r.remaining],
-       'sha256': hashlib.sha256('\n'.join(urls).encode('utf-8')).hexdigest()}
+       'sha256': hashlib.sha256('\n'.join(urls).encode('utf-8')).hexdigest(),
+       'windows': list(getattr(r, 'windows', ())), 'maxrss_kb': resource.getrusage(resource.RUSAGE_SELF).ru_maxrss}
 if r.route == 'device':
     res['cdx_last_ms'] = g.cdx_last_ms()
     res['exclude_last_ms'] = g.exclude_last_ms()
@@ -85,21 +94,23 @@ def write_workload(folder, rows, seed):
     return sum(os.path.getsize(os.path.join(folder, f)) for f in os.listdir(folder))
 
 
-def run_config(folder, env_extra, runs):
+def run_config(folder, env_extra, runs, tree=REPO):
     env = dict(os.environ)
-    env.pop('KW_RESUME_NATIVE', None)
+    for k in ('KW_RESUME_NATIVE', 'E2E_STREAM_FROM', 'E2E_WINDOW_BYTES'):
+        env.pop(k, None)
     env.update(env_extra)
     got = []
     for _ in range(runs + 1):   # the first is the warm-up
-        p = subprocess.run([sys.executable, '-c', CHILD, REPO, folder], env=env, cwd=REPO, capture_output=True,
-                           text=True, timeout=900)
+        p = subprocess.run([sys.executable, '-c', CHILD, tree, folder], env=env, cwd=tree, capture_output=True,
+                           text=True, timeout=1500)
         if p.returncode != 0:
             raise RuntimeError(f"child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
         line = [ln for ln in p.stdout.splitlines() if ln.startswith('E2E_RESUME ')][-1]
         got.append(json.loads(line[len('E2E_RESUME '):]))
     timed = got[1:]
     assert len({r['sha256'] for r in got}) == 1, 'runs of one configuration gave different URLs'
-    res = {'env': env_extra, 'route': timed[-1]['route'], 'counts': timed[-1]['counts'], 'sha256': timed[-1]['sha256']}
+    res = {'env': env_extra, 'route': timed[-1]['route'], 'counts': timed[-1]['counts'], 'sha256': timed[-1]['sha256'],
+           'windows': timed[-1]['windows'], 'peak_rss_MB': max(r['maxrss_kb'] for r in timed) / 1024.0}
     for key in ('seconds', 'seconds_with_urls'):
         v = [r[key] for r in timed]
         res[key] = {'runs': v, 'median_s': statistics.median(v), 'min_s': min(v), 'max_s': max(v)}
@@ -111,13 +122,48 @@ def run_config(folder, env_extra, runs):
     return res
 
 
+def stream_main(args):
+    """--stream: the streamed route against the one-piece route (and the parent's, and pandas)."""
+    out = args.out or os.path.join(REPO, 'profiles', 'e2e_resume_stream.json')
+    with tempfile.TemporaryDirectory(prefix='e2e_resume_', dir=args.tmp) as tmp:
+        n_bytes = write_workload(tmp, args.rows, args.seed)
+        res = {'rows': args.rows, 'seed': args.seed, 'csv_bytes': n_bytes, 'runs_per_config': args.runs,
+               'input_bytes': {f: os.path.getsize(os.path.join(tmp, f)) for f in sorted(os.listdir(tmp))},
+               'timed': 'resume.remaining_urls() in a fresh child per run, GPU initialised and handle created before '
+                        'the clock; 1 warm-up + the median of the runs; the configurations one after the other in one '
+                        'call'}
+        configs = [('one_piece', {'E2E_STREAM_FROM': str(1 << 62)}, REPO), ('streamed', {'E2E_STREAM_FROM': '0'}, REPO),
+                   ('streamed_64MiB', {'E2E_STREAM_FROM': '0', 'E2E_WINDOW_BYTES': str(64 << 20)}, REPO)]
+        if args.parent_tree:
+            configs.append(('parent', {}, os.path.abspath(args.parent_tree)))
+        if args.pandas:
+            configs.append(('pandas', {'KW_RESUME_NATIVE': '0'}, REPO))
+        for name, env, tree in configs:
+            res[name] = run_config(tmp, env, args.runs, tree)
+    res['same_result'] = len({(res[name]['sha256'], tuple(res[name]['counts'])) for name, _, _ in configs}) == 1
+    res['streamed_over_one_piece'] = res['streamed']['seconds']['median_s'] / res['one_piece']['seconds']['median_s']
+    with open(out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+        fh.write('\n')
+    print(json.dumps(res))
+    if not res['same_result']:
+        sys.exit('the configurations gave different results')
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--rows', type=int, default=1_000_000)
     ap.add_argument('--seed', type=int, default=20240229)
     ap.add_argument('--runs', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'e2e_resume.json'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--stream', action='store_true', help='measure the streamed route (see above)')
+    ap.add_argument('--parent-tree', default=None, help='--stream: a built checkout of the parent commit')
+    ap.add_argument('--pandas', action='store_true', help='--stream: the pandas route too')
+    ap.add_argument('--tmp', default=None, help='--stream: where the workload is written')
     args = ap.parse_args()
+    if args.stream:
+        return stream_main(args)
+    args.out = args.out or os.path.join(REPO, 'profiles', 'e2e_resume.json')
     with tempfile.TemporaryDirectory(prefix='e2e_resume_') as tmp:
         n_bytes = write_workload(tmp, args.rows, args.seed)
         res = {'rows': args.rows, 'seed': args.seed, 'csv_bytes': n_bytes, 'runs_per_config': args.runs,
