@@ -8,9 +8,8 @@
 //                           '\r' and NUL bytes as 16-bit masks; a byte starts a row when it is not '\n' and the
 //                           byte before it is (or it is the text's first), so blank-line runs and lines longer
 //                           than a tile need nothing special.  Rows per tile; the first '"' / '\r' / NUL position.
-//   cx_scan_*               exclusive scan of 64-bit counts in two levels (chunk sums, their scan in one block,
-//                           each chunk from its prefix; as dd_tile_sums / dd_scan_tiles), used for the rows per
-//                           tile, the URL lengths and the CSV line lengths.
+//   scan_launch             the device scan of kwhandle.hpp (kwscan.hip), used for the rows per tile, the URL
+//                           lengths and the CSV line lengths.
 //   cx_lines_kernel<true>   the same masks again: every row's start position, at its rank.
 //   cx_parse_kernel         lane = row, 8 bytes a step with per-byte masks: fields counted, the timestamp and URL
 //                           cells located, UTF-8 validated (bytewise only in words with a byte >= 0x80), ':'
@@ -26,7 +25,7 @@
 //
 //   cx_sel_*                the surviving rows rendered in a given order into several files (kw_cdx_csv_select_*; the
 //                           link list's refresh and split, experiental/drop.py and split.py): the order's indices and
-//                           the files' bounds checked, the lines' lengths gathered through the order, cx_scan_*, then
+//                           the files' bounds checked, the lines' lengths gathered through the order, scan_launch, then
 //                           cx_fill_kernel with SelGen; described above the kernels.
 //
 //   cv_*                    quoted CSV, one column out (kw_csv_append, the scraper's resume filter:
@@ -42,14 +41,12 @@
 #include <string>
 
 #include "kwdedup_handle.hpp"
-#include "kwenv.hpp"
+#include "kwdev.hpp"
 
 namespace cx {
 
-constexpr int BLOCK = 256;
-constexpr int TILE = BLOCK * 16;     // bytes of text a block classifies at once
-constexpr int SCAN_CHUNKS = 512;
-constexpr unsigned long long NONE = ~0ull;
+using namespace kwd;   // BLOCK, TILE, NONE and the primitives
+using namespace kwh;
 constexpr int HEADER_LEN = 14;       // "date_time,url\n"
 __constant__ const char HEADER[HEADER_LEN + 2] = "date_time,url\n";
 static const char HEADER_HOST[HEADER_LEN + 2] = "date_time,url\n";
@@ -67,56 +64,11 @@ struct Dialect {
     int ts_col, url_col, skip, exact;
 };
 
-__device__ __forceinline__ uint32_t eq4(uint32_t v, uint32_t pat)   // 0x80 in exactly the bytes equal to pat's
-{
-    const uint32_t d = v ^ pat;
-    return ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
-}
 __device__ __forceinline__ uint64_t eq8(uint64_t v, uint64_t pat)
 {
     const uint64_t d = v ^ pat;
     return ~(((d & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | d) & 0x8080808080808080ull;
 }
-__device__ __forceinline__ uint32_t bits4(uint32_t m) { return (((m >> 7) & 0x01010101u) * 0x01020408u) >> 24; }
-// bit k set iff byte k of the 16 equals c
-__device__ __forceinline__ uint32_t mask16(uint4 v, uint32_t c)
-{
-    const uint32_t pat = c * 0x01010101u;
-    return bits4(eq4(v.x, pat)) | (bits4(eq4(v.y, pat)) << 4) | (bits4(eq4(v.z, pat)) << 8) | (bits4(eq4(v.w, pat)) << 12);
-}
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long x)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long y = __shfl_xor(x, d, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-// exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
-__device__ __forceinline__ unsigned long long block_scan(unsigned long long x, unsigned long long *ws,
-                                                         unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    __syncthreads();   // ws free again
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (int k = 0; k < BLOCK / 64; ++k) {
-        const unsigned long long s = ws[k];
-        if (k < wv) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - x;
-}
-
 // The text's rows: a row starts at a byte that is not '\n' and follows a '\n' (or starts the text).
 // WRITE = false: rows per tile into tile_cnt, the first '"', '\r', NUL into errs.
 // WRITE = true:  tile_cnt holds the tiles' exclusive prefix; every row's start goes to row_start at its rank.
@@ -167,49 +119,6 @@ __global__ __launch_bounds__(BLOCK) void cx_lines_kernel(const uint8_t *__restri
                 starts &= starts - 1u;
             }
         }
-    }
-}
-
-// ---- exclusive scan of m 64-bit values in place, in two levels: chunk c = values [c * per, (c + 1) * per)
-__global__ __launch_bounds__(BLOCK) void cx_scan_sums_kernel(const unsigned long long *__restrict__ a, int64_t m,
-                                                             int64_t per, unsigned long long *__restrict__ chunk)
-{
-    __shared__ unsigned long long ws[BLOCK / 64];
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
-    unsigned long long s = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) s += a[i];
-    unsigned long long total;
-    (void)block_scan(s, ws, &total);
-    if (threadIdx.x == 0) chunk[blockIdx.x] = total;
-}
-
-// one block: the chunk sums' exclusive scan in place (nchunk <= SCAN_CHUNKS = 2 * BLOCK), the grand total
-__global__ __launch_bounds__(BLOCK) void cx_scan_chunks_kernel(unsigned long long *__restrict__ chunk, int nchunk,
-                                                               unsigned long long *__restrict__ grand)
-{
-    __shared__ unsigned long long ws[BLOCK / 64];
-    const int i0 = 2 * (int)threadIdx.x, i1 = i0 + 1;
-    const unsigned long long x0 = i0 < nchunk ? chunk[i0] : 0ull, x1 = i1 < nchunk ? chunk[i1] : 0ull;
-    unsigned long long total;
-    const unsigned long long before = block_scan(x0 + x1, ws, &total);
-    if (i0 < nchunk) chunk[i0] = before;
-    if (i1 < nchunk) chunk[i1] = before + x0;
-    if (threadIdx.x == 0) *grand = total;
-}
-
-__global__ __launch_bounds__(BLOCK) void cx_scan_apply_kernel(unsigned long long *__restrict__ a, int64_t m, int64_t per,
-                                                              const unsigned long long *__restrict__ chunk)
-{
-    __shared__ unsigned long long ws[BLOCK / 64];
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
-    unsigned long long carry = chunk[blockIdx.x];
-    for (int64_t i0 = lo; i0 < hi; i0 += BLOCK) {   // (block-uniform trip count)
-        const int64_t i = i0 + threadIdx.x;
-        const unsigned long long x = i < hi ? a[i] : 0ull;
-        unsigned long long total;
-        const unsigned long long before = block_scan(x, ws, &total);
-        if (i < hi) a[i] = carry + before;
-        carry += total;
     }
 }
 
@@ -482,7 +391,7 @@ __global__ __launch_bounds__(BLOCK) void cx_linelen_kernel(int64_t n_kept, const
 // order[0, n_order) indexes the last run's surviving rows; seg[0 .. n_seg] bounds the files in it.  The output is a
 // list of m = n_order + n_seg lines: file s is its header line (line seg[s] + s) and then one line a selected row
 // (order position j of file s is line j + s + 1).  src[line] = -1 for a header, else the surviving row's index with
-// bit 62 set when its URL is quoted; len[line] its bytes, scanned in place by cx_scan_* into the lines' offsets.
+// bit 62 set when its URL is quoted; len[line] its bytes, scanned in place by scan_launch into the lines' offsets.
 // The copy is cx_fill_kernel<SelGen>: a lane owns 16 bytes of the output, so the stores are full and coalesced
 // whatever the order; the gather is on the read side.
 constexpr int64_t SEL_QUOTED = (int64_t)1 << 62;
@@ -601,7 +510,7 @@ __global__ __launch_bounds__(BLOCK) void cx_sel_ts_kernel(int64_t n_kept, const 
 //                       quotes, ':' looked for and '"' / '\n' / '\r' refused 8 bytes a step.
 //   cv_last_end_kernel  a window of a stream (kw_csv_stream_window): the position after the last '\n' outside quotes,
 //                       from the same masks and carried parity; every pass after it runs over the bytes before it.
-//   then cx_scan_*, cx_off_kernel and cx_fill_kernel<ArenaGen> as kw_cdx_append.
+//   then scan_launch, cx_off_kernel and cx_fill_kernel<ArenaGen> as kw_cdx_append.
 enum { CV_COUNT = 0, CV_ENDS = 1, CV_CELLS = 2 };
 
 // positions of the first offenders (NONE), in the words after a parse's four totals
@@ -609,74 +518,11 @@ struct CsvErrs {
     unsigned long long nul, utf8, quote, cr, fields, url;
 };
 
-// The first byte in [q0, ...) a strict UTF-8 decoder stops at, looking at the code points that start in
-// [p, p + 16): from the code point boundary at or before p (a continuation byte at p belongs to a lead at most 3
-// bytes back; four continuation bytes in a row hold an error at or before p, which its own lane reports).
-__device__ unsigned long long cv_utf8_lane(const uint8_t *__restrict__ text, int64_t n, int64_t p)
-{
-    int64_t q = p;
-    if ((text[p] & 0xC0u) == 0x80u) {
-        int back = 1;
-        while (back <= 3 && p - back >= 0 && (text[p - back] & 0xC0u) == 0x80u) ++back;
-        if (back > 3 || p - back < 0) return (unsigned long long)p;
-        q = p - back;
-    }
-    const int64_t stop = p + 16 < n ? p + 16 : n;
-    while (q < stop) {
-        const uint32_t c = text[q];
-        if (c < 0x80u) { ++q; continue; }
-        int need;
-        uint32_t lo = 0x80u, hi = 0xBFu;
-        if (c >= 0xC2u && c <= 0xDFu) need = 1;
-        else if (c == 0xE0u) { need = 2; lo = 0xA0u; }
-        else if (c == 0xEDu) { need = 2; hi = 0x9Fu; }
-        else if (c >= 0xE1u && c <= 0xEFu) need = 2;
-        else if (c == 0xF0u) { need = 3; lo = 0x90u; }
-        else if (c >= 0xF1u && c <= 0xF3u) need = 3;
-        else if (c == 0xF4u) { need = 3; hi = 0x8Fu; }
-        else return (unsigned long long)q;
-        for (int k = 1; k <= need; ++k) {
-            if (q + k >= n) return (unsigned long long)q;
-            const uint32_t b = text[q + k];
-            if (b < lo || b > hi) return (unsigned long long)q;
-            lo = 0x80u; hi = 0xBFu;
-        }
-        q += need + 1;
-    }
-    return NONE;
-}
-
 __global__ __launch_bounds__(BLOCK) void cv_quotes_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t ntiles,
                                                           unsigned long long *__restrict__ tile_q,
                                                           CsvErrs *__restrict__ errs)
 {
-    __shared__ unsigned long long ws[BLOCK / 64];
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t p = tile * TILE + (int64_t)threadIdx.x * 16;
-        uint32_t q = 0;
-        unsigned long long ez = NONE, e8 = NONE;
-        if (p < n) {
-            const uint4 v = *(const uint4 *)(text + p);
-            const uint32_t valid = n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u;
-            q = mask16(v, 0x22u) & valid;
-            const uint32_t z = mask16(v, 0u) & valid;
-            const uint32_t hb = (bits4(v.x & 0x80808080u) | (bits4(v.y & 0x80808080u) << 4) |
-                                 (bits4(v.z & 0x80808080u) << 8) | (bits4(v.w & 0x80808080u) << 12)) & valid;
-            if (z) ez = (unsigned long long)p + __builtin_ctz(z);
-            if (hb) e8 = cv_utf8_lane(text, n, p);
-        }
-        if (__any((ez & e8) != NONE)) {
-            ez = wave_min(ez);
-            e8 = wave_min(e8);
-            if ((threadIdx.x & 63) == 0) {
-                if (ez != NONE) atomicMin(&errs->nul, ez);
-                if (e8 != NONE) atomicMin(&errs->utf8, e8);
-            }
-        }
-        unsigned long long total;
-        (void)block_scan((unsigned long long)__popc(q), ws, &total);
-        if (threadIdx.x == 0) tile_q[tile] = total;
-    }
+    quotes_tiles(text, n, ntiles, tile_q, &errs->nul, &errs->utf8);
 }
 
 struct CsvArgs {
@@ -926,14 +772,12 @@ void kw_cdx_store_destroy(kw_cdx_store *s)
     delete s;
 }
 
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int store_get(kw_dedup *h, kw_cdx_store **out)
 {
     if (!h->cdx) {
         kw_cdx_store *s = new kw_cdx_store();
         h->cdx = s;
-        for (auto &e : s->ev) DDCHK(h, hipEventCreate(&e));
+        for (auto &e : s->ev) KWCHK(h, hipEventCreate(&e));
     }
     *out = h->cdx;
     return KW_OK;
@@ -942,68 +786,30 @@ static int store_get(kw_dedup *h, kw_cdx_store **out)
 // a scratch buffer of at least `bytes`
 static int scratch_fit(kw_dedup *h, void **buf, size_t *have, size_t bytes)
 {
-    if (bytes <= *have) return KW_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    bytes += bytes / 4;
-    DDCHK(h, hipMalloc(buf, bytes));
-    *have = bytes;
-    return KW_OK;
+    return ensure(h, buf, have, bytes, bytes + bytes / 4);
 }
 
 // a store buffer of at least `need` bytes that keeps its first `used` bytes
 static int grow_keep(kw_dedup *h, void **buf, size_t *cap, size_t need, size_t used, hipStream_t st)
 {
-    if (need <= *cap) return KW_OK;
-    const size_t want = std::max(need, *cap * 2);
-    void *nb = nullptr;
-    DDCHK(h, hipMalloc(&nb, want));
-    if (*buf && used) {
-        hipError_t e = hipMemcpyAsync(nb, *buf, used, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            (void)hipFree(nb);
-            h->err = std::string("HIP error ") + hipGetErrorString(e) + " growing the row store";
-            return KW_EHIP;
-        }
-    }
-    if (*buf) (void)hipFree(*buf);
-    *buf = nb;
-    *cap = want;
-    return KW_OK;
+    return ensure_keep(h, buf, cap, need, used, std::max(need, *cap * 2), false, st);
 }
 
-// exclusive scan of a[0, m) in place; *d_grand (device) receives the total.  chunk: SCAN_CHUNKS words of scratch
-static void scan_launch(unsigned long long *a, int64_t m, unsigned long long *chunk, unsigned long long *d_grand,
-                        hipStream_t st)
-{
-    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(SCAN_CHUNKS, (m + 4 * BLOCK - 1) / (4 * BLOCK)));
-    const int64_t per = std::max<int64_t>(1, (m + nchunk - 1) / nchunk);
-    hipLaunchKernelGGL(cx_scan_sums_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st, (const unsigned long long *)a, m,
-                       per, chunk);
-    hipLaunchKernelGGL(cx_scan_chunks_kernel, dim3(1), dim3(BLOCK), 0, st, chunk, (int)nchunk, d_grand);
-    hipLaunchKernelGGL(cx_scan_apply_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st, a, m, per,
-                       (const unsigned long long *)chunk);
-}
-
-static int grid_for(const kw_dedup *h, int64_t items)
-{
-    return (int)std::max<int64_t>(1, std::min<int64_t>((items + BLOCK - 1) / BLOCK, (int64_t)h->cus * 16));
-}
+// the blocks for `items` lanes, 16 a CU at most
+static int cus_grid(const kw_dedup *h, int64_t items) { return (int)grid_for(items, BLOCK, (int64_t)h->cus * 16).x; }
 
 // the line (the '\n' bytes before it) of byte position pos
 static int line_of(kw_dedup *h, const uint8_t *d_text, int64_t pos, unsigned long long *d_cnt, hipStream_t st,
                    int64_t *line)
 {
     unsigned long long c = 0;
-    DDCHK(h, hipMemsetAsync(d_cnt, 0, 8, st));
+    KWCHK(h, hipMemsetAsync(d_cnt, 0, 8, st));
     if (pos > 0) {
-        hipLaunchKernelGGL(cx_count_nl_kernel, dim3(grid_for(h, (pos + 15) / 16)), dim3(BLOCK), 0, st, d_text, pos, d_cnt);
-        DDCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(cx_count_nl_kernel, dim3(cus_grid(h, (pos + 15) / 16)), dim3(BLOCK), 0, st, d_text, pos, d_cnt);
+        KWCHK(h, hipGetLastError());
     }
-    DDCHK(h, hipMemcpyAsync(&c, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(&c, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     *line = (int64_t)c;
     return KW_OK;
 }
@@ -1041,7 +847,7 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
         h->err = "kw_cdx_append: unsupported dialect";
         return KW_EINVAL;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     kw_cdx_store *s = nullptr;
     int rc = store_get(h, &s);
     if (rc) return rc;
@@ -1056,22 +862,22 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     }
     // ---- rows per tile, the byte conditions
     const int64_t ntiles = (n_bytes + TILE - 1) / TILE;
-    rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, up256(8 * (size_t)ntiles) + up256(8 * SCAN_CHUNKS) + 256);
+    rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, align256(8 * (size_t)ntiles) + align256(8 * SCAN_CHUNKS) + 256);
     if (rc) return rc;
     unsigned long long *tile_cnt = (unsigned long long *)s->d_tiles;
-    unsigned long long *chunk = (unsigned long long *)((uint8_t *)s->d_tiles + up256(8 * (size_t)ntiles));
-    unsigned long long *small = chunk + up256(8 * SCAN_CHUNKS) / 8;   // [0] a scan's total, [1] a line count, [4..8) Errs
+    unsigned long long *chunk = (unsigned long long *)((uint8_t *)s->d_tiles + align256(8 * (size_t)ntiles));
+    unsigned long long *small = chunk + align256(8 * SCAN_CHUNKS) / 8;   // [0] a scan's total, [1] a line count, [4..8) Errs
     Errs *errs = (Errs *)(small + 4);
-    DDCHK(h, hipMemsetAsync(small, 0xFF, 64, st));
-    DDCHK(h, hipEventRecord(s->ev[0], st));
+    KWCHK(h, hipMemsetAsync(small, 0xFF, 64, st));
+    KWCHK(h, hipEventRecord(s->ev[0], st));
     const int tgrid = (int)std::min<int64_t>(ntiles, (int64_t)h->cus * 16);
     hipLaunchKernelGGL(cx_lines_kernel<false>, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_cnt, errs,
                        (int64_t *)nullptr);
     scan_launch(tile_cnt, ntiles, chunk, small, st);
-    DDCHK(h, hipGetLastError());
+    KWCHK(h, hipGetLastError());
     unsigned long long hs[8];
-    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     const int64_t n_lines = (int64_t)hs[0];
     for (int k = 0; k < 3; ++k) {
         if (hs[4 + k] == NONE) continue;
@@ -1093,19 +899,19 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
         if (rc) return rc;
         s->rows_cap = cap / 8;
     }
-    rc = scratch_fit(h, &s->d_rows, &s->rows_bytes, 3 * up256(8 * ((size_t)n_lines + 1)));
+    rc = scratch_fit(h, &s->d_rows, &s->rows_bytes, 3 * align256(8 * ((size_t)n_lines + 1)));
     if (rc) return rc;
     int64_t *row_start = (int64_t *)s->d_rows;
-    int64_t *url_pos = (int64_t *)((uint8_t *)s->d_rows + up256(8 * ((size_t)n_lines + 1)));
-    unsigned long long *url_len = (unsigned long long *)((uint8_t *)s->d_rows + 2 * up256(8 * ((size_t)n_lines + 1)));
+    int64_t *url_pos = (int64_t *)((uint8_t *)s->d_rows + align256(8 * ((size_t)n_lines + 1)));
+    unsigned long long *url_len = (unsigned long long *)((uint8_t *)s->d_rows + 2 * align256(8 * ((size_t)n_lines + 1)));
     hipLaunchKernelGGL(cx_lines_kernel<true>, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_cnt, errs,
                        row_start);
-    hipLaunchKernelGGL(cx_parse_kernel, dim3(grid_for(h, n_lines)), dim3(BLOCK), 0, st, d_text, n_bytes,
+    hipLaunchKernelGGL(cx_parse_kernel, dim3(cus_grid(h, n_lines)), dim3(BLOCK), 0, st, d_text, n_bytes,
                        (const int64_t *)row_start, n_lines, D, s->ts + s->n, url_pos, url_len, errs);
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipEventRecord(s->ev[1], st));
-    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(s->ev[1], st));
+    KWCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     if (hs[7] != NONE) {
         static const int32_t codes[5] = {KW_CDX_HEADER, KW_CDX_UTF8, KW_CDX_FIELDS, KW_CDX_TS, KW_CDX_URL};
         *verdict = codes[std::min<unsigned long long>(hs[7] & 7, 4)];
@@ -1115,24 +921,24 @@ extern "C" int kw_cdx_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
     int64_t total = 0;
     if (n_new > 0) {
         scan_launch(url_len, n_new, chunk, small, st);
-        DDCHK(h, hipGetLastError());
-        DDCHK(h, hipMemcpyAsync(hs, small, 8, hipMemcpyDeviceToHost, st));
-        DDCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipGetLastError());
+        KWCHK(h, hipMemcpyAsync(hs, small, 8, hipMemcpyDeviceToHost, st));
+        KWCHK(h, hipStreamSynchronize(st));
         total = (int64_t)hs[0];
         rc = grow_keep(h, (void **)&s->arena, &s->arena_cap, (size_t)(s->n_bytes + total) + 64, (size_t)s->n_bytes, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(cx_off_kernel, dim3(grid_for(h, n_new + 1)), dim3(BLOCK), 0, st, s->off + s->n,
+        hipLaunchKernelGGL(cx_off_kernel, dim3(cus_grid(h, n_new + 1)), dim3(BLOCK), 0, st, s->off + s->n,
                            (const unsigned long long *)url_len, (const unsigned long long *)small, n_new, s->n_bytes);
         if (total > 0)
-            hipLaunchKernelGGL(cx_fill_kernel<ArenaGen>, dim3(grid_for(h, (total + 31) / 16)), dim3(BLOCK), 0, st, s->arena,
+            hipLaunchKernelGGL(cx_fill_kernel<ArenaGen>, dim3(cus_grid(h, (total + 31) / 16)), dim3(BLOCK), 0, st, s->arena,
                                (const int64_t *)(s->off + s->n), n_new, ArenaGen{d_text, url_pos});
-        DDCHK(h, hipGetLastError());
+        KWCHK(h, hipGetLastError());
     }
-    DDCHK(h, hipEventRecord(s->ev[2], st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipEventRecord(s->ev[2], st));
+    KWCHK(h, hipStreamSynchronize(st));
     float a = 0.f, b = 0.f;
-    DDCHK(h, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-    DDCHK(h, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+    KWCHK(h, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
     s->ms[0] += a;
     s->ms[1] += b;
     s->n += n_new;
@@ -1159,17 +965,9 @@ static bool csv_header_ok(const char *header_line, int32_t url_col, int32_t n_fi
     return plain && n_fields == commas + 1 && url_col >= 0 && url_col < n_fields;
 }
 
-// The cap on the tile kernels' launch grids: the device's, or the tests' KW_TEST_CSV_GRID in [1, 2048] (read per call
-// through kw_env: the kernels' loops then make several trips on a text of a few tiles).
-static int csv_grid_cap(const kw_dedup *h)
-{
-    if (const char *e = kw_env("KW_TEST_CSV_GRID")) {
-        char *end = nullptr;
-        const long g = strtol(e, &end, 10);
-        if (end != e && *end == '\0' && g >= 1 && g <= 2048) return (int)g;
-    }
-    return h->cus * 16;
-}
+// The cap on the tile kernels' launch grids: the device's, or the tests' KW_TEST_CSV_GRID in [1, 2048] (read per call:
+// the kernels' loops then make several trips on a text of a few tiles).
+static int csv_grid_cap(const kw_dedup *h) { return (int)env_int("KW_TEST_CSV_GRID", 1, 2048, h->cus * 16); }
 
 // How csv_parse reads a text: the whole file (kw_csv_append), or one window of a stream (kw_csv_stream_window).
 struct CsvMode {
@@ -1196,8 +994,8 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     // ---- '"' bytes per tile, the byte conditions
     int64_t n_bytes = n_win;
     int64_t ntiles = (n_bytes + TILE - 1) / TILE;
-    const size_t tw = up256(8 * (size_t)ntiles);
-    rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, 3 * tw + up256(8 * SCAN_CHUNKS) + 256);
+    const size_t tw = align256(8 * (size_t)ntiles);
+    rc = scratch_fit(h, &s->d_tiles, &s->tiles_bytes, 3 * tw + align256(8 * SCAN_CHUNKS) + 256);
     if (rc) return rc;
     unsigned long long *tile_q = (unsigned long long *)s->d_tiles;
     unsigned long long *tile_e = (unsigned long long *)((uint8_t *)s->d_tiles + tw);
@@ -1205,12 +1003,12 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     unsigned long long *chunk = (unsigned long long *)((uint8_t *)s->d_tiles + 3 * tw);
     // small: the totals [0] '"' bytes, [1] record ends, [2] delimiters, [3] record starts, then CsvErrs; [12] a
     // scan's total; [13] a window's consumed bytes
-    unsigned long long *small = chunk + up256(8 * SCAN_CHUNKS) / 8;
+    unsigned long long *small = chunk + align256(8 * SCAN_CHUNKS) / 8;
     CsvErrs *errs = (CsvErrs *)(small + 4);
-    DDCHK(h, hipMemsetAsync(small, 0, 32, st));
-    DDCHK(h, hipMemsetAsync(small + 4, 0xFF, sizeof(CsvErrs), st));
-    DDCHK(h, hipMemsetAsync(small + 13, 0, 8, st));
-    DDCHK(h, hipEventRecord(s->ev[0], st));
+    KWCHK(h, hipMemsetAsync(small, 0, 32, st));
+    KWCHK(h, hipMemsetAsync(small + 4, 0xFF, sizeof(CsvErrs), st));
+    KWCHK(h, hipMemsetAsync(small + 13, 0, 8, st));
+    KWCHK(h, hipEventRecord(s->ev[0], st));
     const int gcap = csv_grid_cap(h);
     int tgrid = (int)std::min<int64_t>(ntiles, (int64_t)gcap);
     hipLaunchKernelGGL(cv_quotes_kernel, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles, tile_q, errs);
@@ -1218,12 +1016,12 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     if (M.window && !M.final)
         hipLaunchKernelGGL(cv_last_end_kernel, dim3(tgrid), dim3(BLOCK), 0, st, d_text, n_bytes, ntiles,
                            (const unsigned long long *)tile_q, small + 13);
-    DDCHK(h, hipGetLastError());
+    KWCHK(h, hipGetLastError());
     unsigned long long hs[14];
     uint8_t head[260] = {0};
-    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipMemcpyAsync(head, d_text, (size_t)std::min<int64_t>(n_bytes, (int64_t)hl + 2), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(head, d_text, (size_t)std::min<int64_t>(n_bytes, (int64_t)hl + 2), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     if (M.window && !M.final) {
         // only the records that end inside the window are judged: every pass below runs over [0, consumed)
         if (hs[13] > (unsigned long long)n_win) { h->err = "kw_csv_stream_window: a record end past the window"; return KW_ESTATE; }
@@ -1257,9 +1055,9 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     hipLaunchKernelGGL(cv_tile_kernel<CV_COUNT>, dim3(tgrid), dim3(BLOCK), 0, st, A);
     scan_launch(tile_e, ntiles, chunk, small + 1, st);
     scan_launch(tile_d, ntiles, chunk, small + 2, st);
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     if (hs[6] != NONE || ends_quoted) return refuse(KW_CSV_QUOTE, hs[6] != NONE ? (int64_t)hs[6] : n_bytes);
     if (hs[7] != NONE) return refuse(KW_CSV_CR, (int64_t)hs[7]);
     const int64_t n_ends = (int64_t)hs[1], n_delims = (int64_t)hs[2], n_rec = (int64_t)hs[3];
@@ -1271,7 +1069,7 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     if (n_new == 0 && M.window) return KW_OK;   // (blank lines, or the header alone: kw_csv_stream_end tests the total)
     if (n_new == 0 || s->n + n_new >= ((int64_t)1 << 32)) return refuse(KW_CSV_ROWS, n_bytes);
     // ---- the records located, their cells checked
-    const size_t rw = up256(8 * ((size_t)n_rec + 1));
+    const size_t rw = align256(8 * ((size_t)n_rec + 1));
     rc = scratch_fit(h, &s->d_rows, &s->rows_bytes, 5 * rw);
     if (rc) return rc;
     A.rec_start = (int64_t *)s->d_rows;
@@ -1280,16 +1078,16 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     A.cell_start = (int64_t *)((uint8_t *)s->d_rows + 3 * rw);
     A.cell_end = (int64_t *)((uint8_t *)s->d_rows + 4 * rw);
     A.cap = n_rec + 1;
-    DDCHK(h, hipMemsetAsync(s->d_rows, 0, 5 * rw, st));   // (an entry nobody wrote is an empty cell at 0, not a wild one)
+    KWCHK(h, hipMemsetAsync(s->d_rows, 0, 5 * rw, st));   // (an entry nobody wrote is an empty cell at 0, not a wild one)
     hipLaunchKernelGGL(cv_tile_kernel<CV_ENDS>, dim3(tgrid), dim3(BLOCK), 0, st, A);
     hipLaunchKernelGGL(cv_tile_kernel<CV_CELLS>, dim3(tgrid), dim3(BLOCK), 0, st, A);
-    hipLaunchKernelGGL(cv_rows_kernel, dim3(std::min(grid_for(h, n_new), gcap)), dim3(BLOCK), 0, st, d_text, n_bytes, r0,
+    hipLaunchKernelGGL(cv_rows_kernel, dim3(std::min(cus_grid(h, n_new), gcap)), dim3(BLOCK), 0, st, d_text, n_bytes, r0,
                        n_rec, n_ends, n_delims, (int)n_fields, (int)url_col, (const int64_t *)A.rec_start,
                        (const int64_t *)A.end_pos, (const int64_t *)A.end_dcnt, A.cell_start, A.cell_end, errs);
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipEventRecord(s->ev[1], st));
-    DDCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(s->ev[1], st));
+    KWCHK(h, hipMemcpyAsync(hs, small, sizeof(hs), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     if (hs[8] != NONE) return refuse(KW_CSV_FIELDS, (int64_t)hs[8]);
     if (hs[9] != NONE) return refuse(KW_CSV_URL, (int64_t)hs[9]);
     // ---- compaction (as kw_cdx_append): the cell lengths scanned, the offsets, the cells copied into the arena
@@ -1304,24 +1102,24 @@ static int csv_parse(kw_dedup *h, kw_cdx_store *s, const uint8_t *d_text, int64_
     const int64_t *url_pos = A.cell_start + r0;
     unsigned long long *url_len = (unsigned long long *)(A.cell_end + r0);
     unsigned long long *grand = small + 12;
-    DDCHK(h, hipMemsetAsync(s->ts + s->n, 0, 8 * (size_t)n_new, st));
+    KWCHK(h, hipMemsetAsync(s->ts + s->n, 0, 8 * (size_t)n_new, st));
     scan_launch(url_len, n_new, chunk, grand, st);
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipMemcpyAsync(hs, grand, 8, hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(hs, grand, 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     const int64_t total = (int64_t)hs[0];
     rc = grow_keep(h, (void **)&s->arena, &s->arena_cap, (size_t)(s->n_bytes + total) + 64, (size_t)s->n_bytes, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(cx_off_kernel, dim3(grid_for(h, n_new + 1)), dim3(BLOCK), 0, st, s->off + s->n,
+    hipLaunchKernelGGL(cx_off_kernel, dim3(cus_grid(h, n_new + 1)), dim3(BLOCK), 0, st, s->off + s->n,
                        (const unsigned long long *)url_len, (const unsigned long long *)grand, n_new, s->n_bytes);
-    hipLaunchKernelGGL(cx_fill_kernel<ArenaGen>, dim3(grid_for(h, (total + 31) / 16)), dim3(BLOCK), 0, st, s->arena,
+    hipLaunchKernelGGL(cx_fill_kernel<ArenaGen>, dim3(cus_grid(h, (total + 31) / 16)), dim3(BLOCK), 0, st, s->arena,
                        (const int64_t *)(s->off + s->n), n_new, ArenaGen{d_text, url_pos});
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipEventRecord(s->ev[2], st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(s->ev[2], st));
+    KWCHK(h, hipStreamSynchronize(st));
     float a = 0.f, b = 0.f;
-    DDCHK(h, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-    DDCHK(h, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
+    KWCHK(h, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&b, s->ev[1], s->ev[2]));
     s->ms[0] += a;
     s->ms[1] += b;
     s->n += n_new;
@@ -1348,7 +1146,7 @@ extern "C" int kw_csv_append(kw_dedup *h, const uint8_t *d_text, int64_t n_bytes
         h->err = "kw_csv_append: unsupported header line or column";
         return KW_EINVAL;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     kw_cdx_store *s = nullptr;
     int rc = store_get(h, &s);
     if (rc) return rc;
@@ -1404,7 +1202,7 @@ extern "C" int kw_csv_stream_window(kw_dedup *h, const uint8_t *d_text, int64_t 
         h->err = "kw_csv_stream_window: no open stream, or one that has had its final or a refused window";
         return KW_ESTATE;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     const int rc = csv_parse(h, s, d_text, n_bytes, s->stream_header.c_str(), s->stream_col, s->stream_fields,
                              CsvMode{true, s->stream_first, final != 0}, consumed, n_rows, verdict, bad_pos,
                              (hipStream_t)stream);
@@ -1447,7 +1245,7 @@ extern "C" int kw_csv_stream_end(kw_dedup *h, int32_t commit, int64_t *n_rows_to
 static int run_exclude(kw_dedup *h, int64_t n_exclude, bool unique, void *stream)
 {
     if (!h) return KW_EINVAL;
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     kw_cdx_store *s = nullptr;
     int rc = store_get(h, &s);
     if (rc) return rc;
@@ -1486,7 +1284,7 @@ extern "C" int kw_cdx_exclude_distinct_seen(kw_dedup *h, int64_t *n_distinct_see
         h->err = "kw_cdx_exclude_distinct_seen: the last run was not kw_cdx_run_exclude";
         return KW_ESTATE;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int64_t out[2] = {0, 0};
     const int rc = kw_dedup_distinct_seen(h, s->arena, s->n - h->ex_links, s->code, out, (hipStream_t)stream);
     if (rc) return rc;
@@ -1503,10 +1301,10 @@ extern "C" int kw_cdx_exclude_codes(kw_dedup *h, uint8_t *d_code, void *stream)
         h->err = "kw_cdx_exclude_codes: the last run was not kw_cdx_run_exclude";
         return KW_ESTATE;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     if (h->ex_links > 0) {
         if (!d_code) { h->err = "kw_cdx_exclude_codes: bad arguments"; return KW_EINVAL; }
-        DDCHK(h, hipMemcpyAsync(d_code, s->code + (s->n - h->ex_links), (size_t)h->ex_links, hipMemcpyDeviceToDevice,
+        KWCHK(h, hipMemcpyAsync(d_code, s->code + (s->n - h->ex_links), (size_t)h->ex_links, hipMemcpyDeviceToDevice,
                                 (hipStream_t)stream));
     }
     return KW_OK;
@@ -1523,23 +1321,23 @@ extern "C" int kw_cdx_rows(kw_dedup *h, int64_t *n_rows, int64_t *n_bytes)
 extern "C" int kw_cdx_store_copy(kw_dedup *h, uint8_t *d_arena, int64_t *d_off, int64_t *d_ts, void *stream)
 {
     if (!h) return KW_EINVAL;
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     kw_cdx_store *s = h->cdx;
     if (!s || s->n == 0) {
-        if (d_off) DDCHK(h, hipMemsetAsync(d_off, 0, 8, st));
+        if (d_off) KWCHK(h, hipMemsetAsync(d_off, 0, 8, st));
         return KW_OK;
     }
-    if (d_arena && s->n_bytes) DDCHK(h, hipMemcpyAsync(d_arena, s->arena, (size_t)s->n_bytes, hipMemcpyDeviceToDevice, st));
-    if (d_off) DDCHK(h, hipMemcpyAsync(d_off, s->off, 8 * ((size_t)s->n + 1), hipMemcpyDeviceToDevice, st));
-    if (d_ts) DDCHK(h, hipMemcpyAsync(d_ts, s->ts, 8 * (size_t)s->n, hipMemcpyDeviceToDevice, st));
+    if (d_arena && s->n_bytes) KWCHK(h, hipMemcpyAsync(d_arena, s->arena, (size_t)s->n_bytes, hipMemcpyDeviceToDevice, st));
+    if (d_off) KWCHK(h, hipMemcpyAsync(d_off, s->off, 8 * ((size_t)s->n + 1), hipMemcpyDeviceToDevice, st));
+    if (d_ts) KWCHK(h, hipMemcpyAsync(d_ts, s->ts, 8 * (size_t)s->n, hipMemcpyDeviceToDevice, st));
     return KW_OK;
 }
 
 extern "C" int kw_cdx_run(kw_dedup *h, int32_t flags, void *stream)
 {
     if (!h) return KW_EINVAL;
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     kw_cdx_store *s = nullptr;
     int rc = store_get(h, &s);
     if (rc) return rc;
@@ -1564,7 +1362,7 @@ extern "C" int kw_cdx_csv_size(kw_dedup *h, int64_t *n_bytes, void *stream)
         h->err = "kw_cdx_csv_size: the last run was not kw_cdx_run over this store";
         return KW_ESTATE;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     s->csv_kept = h->n_kept;
     s->ms[2] = 0.f;
@@ -1572,24 +1370,24 @@ extern "C" int kw_cdx_csv_size(kw_dedup *h, int64_t *n_bytes, void *stream)
         s->csv_bytes = HEADER_LEN;
     } else {
         const size_t nk = (size_t)h->n_kept;
-        int rc = scratch_fit(h, &s->d_csv, &s->csv_scratch, up256(8 * (nk + 2)) + up256(nk) + up256(8 * SCAN_CHUNKS) + 256);
+        int rc = scratch_fit(h, &s->d_csv, &s->csv_scratch, align256(8 * (nk + 2)) + align256(nk) + align256(8 * SCAN_CHUNKS) + 256);
         if (rc) return rc;
         unsigned long long *seg = (unsigned long long *)s->d_csv;
-        uint8_t *quoted = (uint8_t *)s->d_csv + up256(8 * (nk + 2));
-        unsigned long long *chunk = (unsigned long long *)(quoted + up256(nk));
-        unsigned long long *grand = chunk + up256(8 * SCAN_CHUNKS) / 8;
-        DDCHK(h, hipEventRecord(s->ev[3], st));
-        hipLaunchKernelGGL(cx_linelen_kernel, dim3(grid_for(h, h->n_kept)), dim3(BLOCK), 0, st, h->n_kept,
+        uint8_t *quoted = (uint8_t *)s->d_csv + align256(8 * (nk + 2));
+        unsigned long long *chunk = (unsigned long long *)(quoted + align256(nk));
+        unsigned long long *grand = chunk + align256(8 * SCAN_CHUNKS) / 8;
+        KWCHK(h, hipEventRecord(s->ev[3], st));
+        hipLaunchKernelGGL(cx_linelen_kernel, dim3(cus_grid(h, h->n_kept)), dim3(BLOCK), 0, st, h->n_kept,
                            (const int64_t *)s->ts, (const int64_t *)h->kept_row, (const int64_t *)h->kept_off,
                            (const uint8_t *)h->kept_bytes, seg, quoted);
         scan_launch(seg, h->n_kept + 1, chunk, grand, st);
-        DDCHK(h, hipGetLastError());
-        DDCHK(h, hipMemcpyAsync(seg + nk + 1, grand, 8, hipMemcpyDeviceToDevice, st));
+        KWCHK(h, hipGetLastError());
+        KWCHK(h, hipMemcpyAsync(seg + nk + 1, grand, 8, hipMemcpyDeviceToDevice, st));
         unsigned long long tot = 0;
-        DDCHK(h, hipMemcpyAsync(&tot, grand, 8, hipMemcpyDeviceToHost, st));
-        DDCHK(h, hipEventRecord(s->ev[4], st));
-        DDCHK(h, hipStreamSynchronize(st));
-        DDCHK(h, hipEventElapsedTime(&s->ms[2], s->ev[3], s->ev[4]));
+        KWCHK(h, hipMemcpyAsync(&tot, grand, 8, hipMemcpyDeviceToHost, st));
+        KWCHK(h, hipEventRecord(s->ev[4], st));
+        KWCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipEventElapsedTime(&s->ms[2], s->ev[3], s->ev[4]));
         s->csv_bytes = (int64_t)tot;
     }
     s->csv_ready = true;
@@ -1606,25 +1404,25 @@ extern "C" int kw_cdx_csv_copy(kw_dedup *h, uint8_t *d_out, void *stream)
         return KW_ESTATE;
     }
     if (!d_out || ((uintptr_t)d_out & 15) != 0) { h->err = "kw_cdx_csv_copy: d_out must be 16-byte aligned"; return KW_EINVAL; }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     if (s->csv_kept == 0) {
-        DDCHK(h, hipMemcpyAsync(d_out, HEADER_HOST, HEADER_LEN, hipMemcpyHostToDevice, st));
-        DDCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipMemcpyAsync(d_out, HEADER_HOST, HEADER_LEN, hipMemcpyHostToDevice, st));
+        KWCHK(h, hipStreamSynchronize(st));
         return KW_OK;
     }
     const size_t nk = (size_t)s->csv_kept;
-    const uint8_t *quoted = (const uint8_t *)s->d_csv + up256(8 * (nk + 2));
-    DDCHK(h, hipEventRecord(s->ev[3], st));
-    hipLaunchKernelGGL(cx_fill_kernel<CsvGen>, dim3(grid_for(h, (s->csv_bytes + 31) / 16)), dim3(BLOCK), 0, st, d_out,
+    const uint8_t *quoted = (const uint8_t *)s->d_csv + align256(8 * (nk + 2));
+    KWCHK(h, hipEventRecord(s->ev[3], st));
+    hipLaunchKernelGGL(cx_fill_kernel<CsvGen>, dim3(cus_grid(h, (s->csv_bytes + 31) / 16)), dim3(BLOCK), 0, st, d_out,
                        (const int64_t *)s->d_csv, s->csv_kept + 1,
                        CsvGen{(const int64_t *)s->ts, (const int64_t *)h->kept_row, (const int64_t *)h->kept_off,
                               (const uint8_t *)h->kept_bytes, quoted});
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipEventRecord(s->ev[4], st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(s->ev[4], st));
+    KWCHK(h, hipStreamSynchronize(st));
     float w = 0.f;
-    DDCHK(h, hipEventElapsedTime(&w, s->ev[3], s->ev[4]));
+    KWCHK(h, hipEventElapsedTime(&w, s->ev[3], s->ev[4]));
     s->ms[2] += w;
     return KW_OK;
 }
@@ -1660,10 +1458,10 @@ extern "C" int kw_cdx_selected_ts(kw_dedup *h, int64_t *d_ts, void *stream)
     if (int rc = select_state(h, "kw_cdx_selected_ts", &s, &base)) return rc;
     if (h->n_kept == 0) return KW_OK;
     if (!d_ts) { h->err = "kw_cdx_selected_ts: bad arguments"; return KW_EINVAL; }
-    DDCHK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(cx_sel_ts_kernel, dim3(grid_for(h, h->n_kept)), dim3(BLOCK), 0, (hipStream_t)stream, h->n_kept,
+    KWCHK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(cx_sel_ts_kernel, dim3(cus_grid(h, h->n_kept)), dim3(BLOCK), 0, (hipStream_t)stream, h->n_kept,
                        (const int64_t *)s->ts, base, (const int64_t *)h->kept_row, d_ts);
-    DDCHK(h, hipGetLastError());
+    KWCHK(h, hipGetLastError());
     return KW_OK;
 }
 
@@ -1673,11 +1471,11 @@ static void select_carve(kw_cdx_store *s, size_t m, unsigned long long **off, in
 {
     uint8_t *p = (uint8_t *)s->d_sel;
     *off = (unsigned long long *)p;
-    p += up256(8 * (m + 1));
+    p += align256(8 * (m + 1));
     *src = (int64_t *)p;
-    p += up256(8 * m);
+    p += align256(8 * m);
     *chunk = (unsigned long long *)p;
-    p += up256(8 * SCAN_CHUNKS);
+    p += align256(8 * SCAN_CHUNKS);
     *grand = (unsigned long long *)p;
     *errs = (SelErrs *)(p + 64);
 }
@@ -1695,7 +1493,7 @@ extern "C" int kw_cdx_csv_select_size(kw_dedup *h, const int64_t *d_order, int64
         h->err = "kw_cdx_csv_select_size: bad arguments";
         return KW_EINVAL;
     }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     s->sel_ms[0] = s->sel_ms[1] = 0.f;
     const int64_t m = n_order + n_seg;
@@ -1703,46 +1501,46 @@ extern "C" int kw_cdx_csv_select_size(kw_dedup *h, const int64_t *d_order, int64
     s->sel_bytes = 0;
     if (m > 0) {
         int rc = scratch_fit(h, &s->d_sel, &s->sel_scratch,
-                             up256(8 * ((size_t)m + 1)) + up256(8 * (size_t)m) + up256(8 * SCAN_CHUNKS) + 256);
+                             align256(8 * ((size_t)m + 1)) + align256(8 * (size_t)m) + align256(8 * SCAN_CHUNKS) + 256);
         if (rc) return rc;
         unsigned long long *off, *chunk, *grand;
         int64_t *src;
         SelErrs *errs;
         select_carve(s, (size_t)m, &off, &src, &chunk, &grand, &errs);
-        DDCHK(h, hipEventRecord(s->ev[3], st));
-        DDCHK(h, hipMemsetAsync(errs, 0xFF, sizeof(SelErrs), st));
-        hipLaunchKernelGGL(cx_sel_seg_kernel, dim3(grid_for(h, n_seg + 1)), dim3(BLOCK), 0, st, d_seg, n_seg, n_order, off,
+        KWCHK(h, hipEventRecord(s->ev[3], st));
+        KWCHK(h, hipMemsetAsync(errs, 0xFF, sizeof(SelErrs), st));
+        hipLaunchKernelGGL(cx_sel_seg_kernel, dim3(cus_grid(h, n_seg + 1)), dim3(BLOCK), 0, st, d_seg, n_seg, n_order, off,
                            src, errs);
         if (n_order > 0)
-            hipLaunchKernelGGL(cx_sel_len_kernel, dim3(grid_for(h, n_order)), dim3(BLOCK), 0, st, d_order, n_order, d_seg,
+            hipLaunchKernelGGL(cx_sel_len_kernel, dim3(cus_grid(h, n_order)), dim3(BLOCK), 0, st, d_order, n_order, d_seg,
                                n_seg, h->n_kept, (const int64_t *)s->ts, base, (const int64_t *)h->kept_row,
                                (const int64_t *)h->kept_off, (const uint8_t *)h->kept_bytes, off, src, errs);
-        DDCHK(h, hipGetLastError());
+        KWCHK(h, hipGetLastError());
         SelErrs e;
-        DDCHK(h, hipMemcpyAsync(&e, errs, sizeof(e), hipMemcpyDeviceToHost, st));
-        DDCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipMemcpyAsync(&e, errs, sizeof(e), hipMemcpyDeviceToHost, st));
+        KWCHK(h, hipStreamSynchronize(st));
         if (e.seg != NONE) {
             h->err = "kw_cdx_csv_select_size: d_seg[" + std::to_string(e.seg) + "] is not an ascending bound from 0 to n_order";
             return KW_EINVAL;
         }
         if (e.order != NONE) {
             int64_t v = 0;
-            DDCHK(h, hipMemcpy(&v, d_order + e.order, 8, hipMemcpyDeviceToHost));
+            KWCHK(h, hipMemcpy(&v, d_order + e.order, 8, hipMemcpyDeviceToHost));
             h->err = "kw_cdx_csv_select_size: d_order[" + std::to_string(e.order) + "] = " + std::to_string(v) +
                      " is outside the " + std::to_string(h->n_kept) + " surviving rows";
             return KW_EINVAL;
         }
         scan_launch(off, m, chunk, grand, st);
-        DDCHK(h, hipGetLastError());
-        DDCHK(h, hipMemcpyAsync(off + m, grand, 8, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(cx_sel_bytes_kernel, dim3(grid_for(h, n_seg)), dim3(BLOCK), 0, st, d_seg, n_seg,
+        KWCHK(h, hipGetLastError());
+        KWCHK(h, hipMemcpyAsync(off + m, grand, 8, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(cx_sel_bytes_kernel, dim3(cus_grid(h, n_seg)), dim3(BLOCK), 0, st, d_seg, n_seg,
                            (const int64_t *)off, d_seg_bytes);
-        DDCHK(h, hipGetLastError());
+        KWCHK(h, hipGetLastError());
         unsigned long long tot = 0;
-        DDCHK(h, hipMemcpyAsync(&tot, grand, 8, hipMemcpyDeviceToHost, st));
-        DDCHK(h, hipEventRecord(s->ev[4], st));
-        DDCHK(h, hipStreamSynchronize(st));
-        DDCHK(h, hipEventElapsedTime(&s->sel_ms[0], s->ev[3], s->ev[4]));
+        KWCHK(h, hipMemcpyAsync(&tot, grand, 8, hipMemcpyDeviceToHost, st));
+        KWCHK(h, hipEventRecord(s->ev[4], st));
+        KWCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipEventElapsedTime(&s->sel_ms[0], s->ev[3], s->ev[4]));
         s->sel_bytes = (int64_t)tot;
     }
     s->sel_ready = true;
@@ -1759,21 +1557,21 @@ extern "C" int kw_cdx_csv_select_copy(kw_dedup *h, uint8_t *d_out, void *stream)
     if (!s->sel_ready) { h->err = "kw_cdx_csv_select_copy: no kw_cdx_csv_select_size since the last run"; return KW_ESTATE; }
     if (s->sel_bytes == 0) return KW_OK;
     if (!d_out || ((uintptr_t)d_out & 15) != 0) { h->err = "kw_cdx_csv_select_copy: d_out must be 16-byte aligned"; return KW_EINVAL; }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *off, *chunk, *grand;
     int64_t *src;
     SelErrs *errs;
     select_carve(s, (size_t)s->sel_lines, &off, &src, &chunk, &grand, &errs);
-    DDCHK(h, hipEventRecord(s->ev[3], st));
-    hipLaunchKernelGGL(cx_fill_kernel<SelGen>, dim3(grid_for(h, (s->sel_bytes + 31) / 16)), dim3(BLOCK), 0, st, d_out,
+    KWCHK(h, hipEventRecord(s->ev[3], st));
+    hipLaunchKernelGGL(cx_fill_kernel<SelGen>, dim3(cus_grid(h, (s->sel_bytes + 31) / 16)), dim3(BLOCK), 0, st, d_out,
                        (const int64_t *)off, s->sel_lines,
                        SelGen{(const int64_t *)s->ts, (const int64_t *)h->kept_row, (const int64_t *)h->kept_off,
                               (const uint8_t *)h->kept_bytes, (const int64_t *)src, base});
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipEventRecord(s->ev[4], st));
-    DDCHK(h, hipStreamSynchronize(st));
-    DDCHK(h, hipEventElapsedTime(&s->sel_ms[1], s->ev[3], s->ev[4]));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(s->ev[4], st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipEventElapsedTime(&s->sel_ms[1], s->ev[3], s->ev[4]));
     return KW_OK;
 }
 

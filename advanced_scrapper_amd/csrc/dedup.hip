@@ -62,14 +62,15 @@
 #include "../../include/kwmatch.h"
 #include "../../include/kwdedup.h"
 #include "kwdedup_handle.hpp"
-#include "kwenv.hpp"
+#include "kwdev.hpp"
 
 namespace dd {
 
 constexpr int BLOCK = 256;
 constexpr int SCAN_ROWS = 4;                       // rows per thread in the scan kernels
 constexpr int SCAN_TILE = BLOCK * SCAN_ROWS;
-constexpr int SCAN_CHUNKS = 512;                   // chunks of tiles in the two-level tile scan
+using kwd::eq4;
+using kwh::SCAN_CHUNKS;                             // chunks of tiles in the two-level tile scan
 constexpr uint32_t HTML4 = 0x6C6D7468u;            // "html"
 constexpr uint32_t NEWS4 = 0x7377656Eu;            // "news"
 constexpr uint64_t DOTHTML = 0x6C6D74682Eull;      // ".html"
@@ -98,12 +99,6 @@ __device__ __forceinline__ uint64_t ld64(const uint8_t *__restrict__ a, int64_t 
     const uint32_t x1 = *(const uint32_t *)(a + a0 + 4);
     const uint32_t x2 = *(const uint32_t *)(a + a0 + 8);
     return (uint64_t)__builtin_amdgcn_alignbyte(x1, x0, s) | ((uint64_t)__builtin_amdgcn_alignbyte(x2, x1, s) << 32);
-}
-
-__device__ __forceinline__ uint32_t eq_bytes(uint32_t v, uint32_t pat)   // 0x80 in exactly the bytes equal to pat's
-{
-    const uint32_t d = v ^ pat;
-    return ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
 }
 
 __host__ __device__ __forceinline__ uint64_t mix1(uint64_t h, uint64_t w)
@@ -414,7 +409,7 @@ __device__ __forceinline__ int64_t transform_row(const Src &src, int64_t b, int6
         const int64_t r = L - t;
         const uint32_t in = r >= 4 ? 0x80808080u : 0x80808080u & ((1u << (8 * r)) - 1u);   // positions < L
         // extra colons: the first two positions (all new positions lie past the recorded ones)
-        uint32_t cm = eq_bytes(x, 0x3A3A3A3Au) & in;
+        uint32_t cm = eq4(x, 0x3A3A3A3Au) & in;
         if (t == 4) cm &= ~excl;
         if (cm) {   // rare once the scheme's ':' is masked out
             const uint32_t cm1 = cm & (cm - 1u);
@@ -424,7 +419,7 @@ __device__ __forceinline__ int64_t transform_row(const Src &src, int64_t b, int6
             ec = ec == INT64_MAX ? c0 : ec;
         }
         // 'news/%' | "news/'": from the (rare) '%' / "'" byte p back to its "news/" (kf = p = q + 5)
-        uint32_t pm = eq_bytes(x | 0x02020202u, 0x27272727u) & in;   // '%' (0x25) and "'" (0x27) differ in bit 1 only
+        uint32_t pm = eq4(x | 0x02020202u, 0x27272727u) & in;   // '%' (0x25) and "'" (0x27) differ in bit 1 only
         while (pm) {
             const int64_t p = t + (__builtin_ctz(pm) >> 3);
             pm &= pm - 1u;
@@ -437,7 +432,7 @@ __device__ __forceinline__ int64_t transform_row(const Src &src, int64_t b, int6
         if (hm) {   // (once a row, at its end) validate: q + 4 <= L, q >= 1, no '\n' before q
             const int64_t r3 = r - 3;
             hm &= r3 >= 4 ? 0x80808080u : (r3 <= 0 ? 0u : 0x80808080u & ((1u << (8 * r3)) - 1u));
-            hm &= ~eq_bytes(__builtin_amdgcn_alignbyte(x, xp, 3), 0x0A0A0A0Au);
+            hm &= ~eq4(__builtin_amdgcn_alignbyte(x, xp, 3), 0x0A0A0A0Au);
             if (t == 0) hm &= ~0x80u;
         }
         if (hm) {
@@ -593,7 +588,7 @@ __device__ __forceinline__ int64_t transform_row_lds(const LdsRow &R, int L, int
                       (__builtin_amdgcn_alignbyte(hi, lo, 3) == HTML4 ? 0x80000000u : 0u);
         const int r3 = L - tt - 3;   // q + 4 <= L
         hm &= r3 >= 4 ? 0x80808080u : (r3 <= 0 ? 0u : 0x80808080u & ((1u << (8 * r3)) - 1u));
-        hm &= ~eq_bytes(__builtin_amdgcn_alignbyte(lo, prev, 3), 0x0A0A0A0Au);
+        hm &= ~eq4(__builtin_amdgcn_alignbyte(lo, prev, 3), 0x0A0A0A0Au);
         if (tt == 0) hm &= ~0x80u;
         return hm;
     };
@@ -604,13 +599,13 @@ __device__ __forceinline__ int64_t transform_row_lds(const LdsRow &R, int L, int
             y = __builtin_amdgcn_alignbyte(d3, d2, R.s);
             d1 = d3;
             d2 = d4;
-            const uint32_t cmA = eq_bytes(x, 0x3A3A3A3Au);
-            const uint32_t cmB = eq_bytes(x2, 0x3A3A3A3Au) & (t == 0 ? ~excl : ~0u);
+            const uint32_t cmA = eq4(x, 0x3A3A3A3Au);
+            const uint32_t cmB = eq4(x2, 0x3A3A3A3Au) & (t == 0 ? ~excl : ~0u);
             if (cmA | cmB) {
                 if (cmA) colons(cmA, t);
                 if (cmB) colons(cmB, t + 4);
             }
-            const uint32_t pmA = eq_bytes(x | 0x02020202u, 0x27272727u), pmB = eq_bytes(x2 | 0x02020202u, 0x27272727u);
+            const uint32_t pmA = eq4(x | 0x02020202u, 0x27272727u), pmB = eq4(x2 | 0x02020202u, 0x27272727u);
             if (pmA | pmB) {
                 filt(pmA, t);
                 filt(pmB, t + 4);
@@ -1598,7 +1593,7 @@ __global__ __launch_bounds__(BLOCK) void dd_count_kept_kernel(const uint8_t *__r
 
 using namespace dd;
 
-// struct kw_dedup, DDCHK: kwdedup_handle.hpp (shared with cdx.hip)
+// struct kw_dedup, KWCHK: kwdedup_handle.hpp (shared with cdx.hip)
 
 extern "C" int kw_dedup_create(int32_t device, kw_dedup **out)
 {
@@ -1606,21 +1601,21 @@ extern "C" int kw_dedup_create(int32_t device, kw_dedup **out)
     kw_dedup *h = new kw_dedup();
     *out = h;
     h->device = device;
-    DDCHK(h, hipSetDevice(device));
+    KWCHK(h, hipSetDevice(device));
     hipDeviceProp_t prop;
-    DDCHK(h, hipGetDeviceProperties(&prop, device));
+    KWCHK(h, hipGetDeviceProperties(&prop, device));
     h->cus = prop.multiProcessorCount;
-    DDCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->copy_bpc, dd_copy_kernel, BLOCK, 0));
-    DDCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->pairs_bpc, dd_pairs_kernel, BLOCK, 0));
-    DDCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->copys_bpc, dd_copy_staged_kernel, 64, 0));
+    KWCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->copy_bpc, dd_copy_kernel, BLOCK, 0));
+    KWCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->pairs_bpc, dd_pairs_kernel, BLOCK, 0));
+    KWCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->copys_bpc, dd_copy_staged_kernel, 64, 0));
     h->copy_bpc = std::max(1, h->copy_bpc);
     h->copys_bpc = std::max(1, h->copys_bpc);
     h->pairs_bpc = std::max(1, h->pairs_bpc);
-    for (auto &e : h->ev) DDCHK(h, hipEventCreate(&e));
+    for (auto &e : h->ev) KWCHK(h, hipEventCreate(&e));
     return KW_OK;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using kwh::align256;
 
 // The normalised bytes of the listed rows on the host, regenerated on the device: row rows[q] is
 // buf[boff[q], boff[q] + len[q]) (8-aligned slots).
@@ -1676,21 +1671,21 @@ static int resolve_collisions(kw_dedup *h, const uint8_t *d_arena, const int64_t
     unsigned long long *d_cnt = (unsigned long long *)h->d_collide;
     unsigned long long m = listed;   // the recheck kernel's list (its rows: the CODE_COLLIDE rows)
     if (m > CAP) {   // (a longer list: the codes scanned again, by the kernel up to CAP, then on the host)
-        DDCHK(h, hipMemsetAsync(d_cnt, 0, 8, st));
+        KWCHK(h, hipMemsetAsync(d_cnt, 0, 8, st));
         const int grid = (int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, (int64_t)h->cus * 16);
         hipLaunchKernelGGL(dd_collect_kernel, dim3(grid), dim3(BLOCK), 0, st, (const uint8_t *)d_code, n, d_cnt,
                            (uint32_t *)(d_cnt + 1), CAP);
-        DDCHK(h, hipGetLastError());
-        DDCHK(h, hipMemcpyAsync(&m, d_cnt, 8, hipMemcpyDeviceToHost, st));
-        DDCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipGetLastError());
+        KWCHK(h, hipMemcpyAsync(&m, d_cnt, 8, hipMemcpyDeviceToHost, st));
+        KWCHK(h, hipStreamSynchronize(st));
     }
     if (m <= CAP) {
         rows.resize(m);
-        if (m) DDCHK(h, hipMemcpy(rows.data(), d_cnt + 1, 4 * m, hipMemcpyDeviceToHost));
+        if (m) KWCHK(h, hipMemcpy(rows.data(), d_cnt + 1, 4 * m, hipMemcpyDeviceToHost));
         std::sort(rows.begin(), rows.end());
     } else {
         std::vector<uint8_t> code(n);
-        DDCHK(h, hipMemcpy(code.data(), d_code, n, hipMemcpyDeviceToHost));
+        KWCHK(h, hipMemcpy(code.data(), d_code, n, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i)
             if (code[i] == CODE_COLLIDE) rows.push_back((uint32_t)i);
     }
@@ -1709,7 +1704,7 @@ static int resolve_collisions(kw_dedup *h, const uint8_t *d_arena, const int64_t
         codes[q] = ins.second ? (uint8_t)KW_URL_KEPT : (uint8_t)KW_URL_DUPLICATE;
         ++h->counts[codes[q]];
     }
-    for (uint32_t q = 0; q < k; ++q) DDCHK(h, hipMemcpy(d_code + rows[q], &codes[q], 1, hipMemcpyHostToDevice));
+    for (uint32_t q = 0; q < k; ++q) KWCHK(h, hipMemcpy(d_code + rows[q], &codes[q], 1, hipMemcpyHostToDevice));
     return KW_OK;
 }
 
@@ -1736,18 +1731,18 @@ static int compact_kept(kw_dedup *h, const uint8_t *d_arena, const uint8_t *d_co
     }
     hipLaunchKernelGGL(dd_place_kernel, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, (const uint8_t *)d_code, n, S,
                        h->tile_cnt, h->tile_bytes, h->kept_off, h->kept_row);
-    DDCHK(h, hipGetLastError());
+    KWCHK(h, hipGetLastError());
     unsigned long long tot[2];
-    DDCHK(h, hipMemcpyAsync(tot, h->totals, sizeof(tot), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(tot, h->totals, sizeof(tot), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     h->n_kept = (int64_t)tot[0];
     h->n_kept_bytes = (int64_t)tot[1];
-    DDCHK(h, hipMemcpyAsync(h->kept_off + h->n_kept, &h->n_kept_bytes, 8, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemcpyAsync(h->kept_off + h->n_kept, &h->n_kept_bytes, 8, hipMemcpyHostToDevice, st));
     if ((size_t)h->n_kept_bytes + 64 > h->kept_bytes_cap) {
         if (h->d_kept) (void)hipFree(h->d_kept);
         h->d_kept = nullptr;
         h->kept_bytes_cap = 0;
-        DDCHK(h, hipMalloc(&h->d_kept, (size_t)h->n_kept_bytes + 64));
+        KWCHK(h, hipMalloc(&h->d_kept, (size_t)h->n_kept_bytes + 64));
         h->kept_bytes_cap = (size_t)h->n_kept_bytes + 64;
     }
     h->kept_bytes = (uint8_t *)h->d_kept;
@@ -1761,7 +1756,7 @@ static int compact_kept(kw_dedup *h, const uint8_t *d_arena, const uint8_t *d_co
                                                                                 (int64_t)h->cus * h->copys_bpc)),
                                dim3(64), 0, st, h->n_kept, (const int64_t *)h->kept_off, (const int64_t *)h->kept_row,
                                d_arena, S, h->kept_bytes);
-        DDCHK(h, hipGetLastError());
+        KWCHK(h, hipGetLastError());
     }
     return KW_OK;
 }
@@ -1773,7 +1768,7 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
     if (n < 0 || (n > 0 && (!d_arena || !d_off || !d_code))) { h->err = "kw_dedup_run: bad arguments"; return KW_EINVAL; }
     if (((uintptr_t)d_arena & 15) != 0) { h->err = "kw_dedup_run: arena must be 16-byte aligned"; return KW_EINVAL; }
     if (n >= ((int64_t)1 << 32)) { h->err = "kw_dedup_run: more than 2^32 - 1 rows"; return KW_EUNSUPPORTED; }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     h->n = n;
     h->have_run = true;
@@ -1802,7 +1797,7 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
         if (h->d_buf) (void)hipFree(h->d_buf);
         h->d_buf = nullptr;
         h->buf_bytes = 0;
-        DDCHK(h, hipMalloc(&h->d_buf, need));
+        KWCHK(h, hipMalloc(&h->d_buf, need));
         h->buf_bytes = need;
     }
     uint8_t *p = (uint8_t *)h->d_buf;
@@ -1820,7 +1815,7 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
     S.nslow = (unsigned long long *)carve(8 * 4);
     S.slow = (uint2 *)carve(8 * (size_t)n);
     S.sarena = (uint64_t *)h->d_sarena;
-    if (!h->d_collide) DDCHK(h, hipMalloc(&h->d_collide, 8 + 4 * (size_t)COLLIDE_CAP));
+    if (!h->d_collide) KWCHK(h, hipMalloc(&h->d_collide, 8 + 4 * (size_t)COLLIDE_CAP));
     S.collide = (uint32_t *)((unsigned long long *)h->d_collide + 1);
     S.weak = kw_env("KW_TEST_DEDUP_WEAK_HASH") ? 1 : 0;
     S.stats = kw_env("KW_DEDUP_STATS") ? 1 : 0;
@@ -1832,47 +1827,47 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
     h->chunk_bytes = (unsigned long long *)carve(8 * SCAN_CHUNKS);
     h->kept_off = (int64_t *)carve(8 * ((size_t)n + 1));
     h->kept_row = (int64_t *)carve(8 * ((size_t)n + 1));
-    DDCHK(h, hipMemsetAsync(S.cnt, 0, 128, st));
-    DDCHK(h, hipMemsetAsync(S.nslow, 0, 32, st));
+    KWCHK(h, hipMemsetAsync(S.cnt, 0, 128, st));
+    KWCHK(h, hipMemsetAsync(S.nslow, 0, 32, st));
     // the table is cleared when it moved or grew, or when the epoch wraps; else this run's epoch marks its slots
     if ((void *)S.table != h->table_at || tsize != h->table_slots || h->epoch >= 255) {
-        DDCHK(h, hipMemsetAsync(S.table, 0, 8 * tsize, st));
+        KWCHK(h, hipMemsetAsync(S.table, 0, 8 * tsize, st));
         h->table_at = (void *)S.table;
         h->table_slots = tsize;
         h->epoch = 0;
     }
     S.epoch = ++h->epoch;
-    DDCHK(h, hipEventRecord(h->ev[0], st));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
     hipLaunchKernelGGL(dd_transform_kernel, dim3(tgrid), dim3(BLOCK), 0, st, d_arena, d_off, n, d_code, S);
-    DDCHK(h, hipGetLastError());
-    DDCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(h->ev[1], st));
     // the byte-serial rows (rare): their slow-arena words are sized from the transform's count
     unsigned long long ns2[2];
-    DDCHK(h, hipMemcpyAsync(ns2, S.nslow, sizeof(ns2), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(ns2, S.nslow, sizeof(ns2), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     if (ns2[0]) {
         const size_t sbytes = 8 * (size_t)ns2[1] + 64;
         if (sbytes > h->sarena_bytes) {
             if (h->d_sarena) (void)hipFree(h->d_sarena);
             h->d_sarena = nullptr;
             h->sarena_bytes = 0;
-            DDCHK(h, hipMalloc(&h->d_sarena, sbytes + sbytes / 4));
+            KWCHK(h, hipMalloc(&h->d_sarena, sbytes + sbytes / 4));
             h->sarena_bytes = sbytes + sbytes / 4;
         }
         S.sarena = (uint64_t *)h->d_sarena;
         const int sgrid = (int)std::min<uint64_t>((ns2[0] + BLOCK - 1) / BLOCK, (uint64_t)h->cus * 16);
         hipLaunchKernelGGL(dd_slow_kernel, dim3(sgrid), dim3(BLOCK), 0, st, d_arena, d_off, d_code, S, (uint64_t)ns2[0]);
-        DDCHK(h, hipGetLastError());
+        KWCHK(h, hipGetLastError());
     }
-    DDCHK(h, hipEventRecord(h->ev[2], st));
+    KWCHK(h, hipEventRecord(h->ev[2], st));
     // decide: the pairs compared (4 lanes a pair), then the later rows of the differing ones against the table
     hipLaunchKernelGGL(dd_pairs_kernel, dim3((int)std::min<int64_t>((n_claims + 3) / 4, (int64_t)h->cus * h->pairs_bpc)),
                        dim3(BLOCK), 0, st, d_arena, d_code, S, n_claims, (uint64_t)ns2[0]);
     hipLaunchKernelGGL(dd_recheck_kernel, dim3(h->cus * 4), dim3(BLOCK), 0, st, d_arena, d_code, S);
-    DDCHK(h, hipGetLastError());
+    KWCHK(h, hipGetLastError());
     unsigned long long cnt[10];
-    DDCHK(h, hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     h->route[0] = (int64_t)ns2[0];
     h->route[1] = (int64_t)cnt[5];
     h->route[2] = (int64_t)cnt[CODE_COLLIDE];
@@ -1889,13 +1884,13 @@ extern "C" int kw_dedup_run(kw_dedup *h, const uint8_t *d_arena, const int64_t *
         int rc = resolve_collisions(h, d_arena, d_off, n, d_code, st, cnt[9]);
         if (rc) return rc;
     }
-    DDCHK(h, hipEventRecord(h->ev[3], st));
+    KWCHK(h, hipEventRecord(h->ev[3], st));
     if (!h->no_compact) {   // (kw_cdx_run_exclude compacts the link rows after its pass instead)
         int rc = compact_kept(h, d_arena, d_code, n, S, st);
         if (rc) return rc;
     }
-    DDCHK(h, hipEventRecord(h->ev[4], st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipEventRecord(h->ev[4], st));
+    KWCHK(h, hipStreamSynchronize(st));
     return KW_OK;
 }
 
@@ -1937,16 +1932,16 @@ extern "C" int kw_dedup_kept_copy(kw_dedup *h, uint8_t *d_bytes, int64_t *d_off,
 {
     if (!h) return KW_EINVAL;
     if (!h->have_run) { h->err = "kw_dedup_kept_copy: no run"; return KW_ESTATE; }
-    DDCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     if (h->n == 0 || h->n_kept == 0) {
-        if (d_off) DDCHK(h, hipMemsetAsync(d_off, 0, 8, st));
+        if (d_off) KWCHK(h, hipMemsetAsync(d_off, 0, 8, st));
         return KW_OK;
     }
     if (d_bytes && h->n_kept_bytes)
-        DDCHK(h, hipMemcpyAsync(d_bytes, h->kept_bytes, (size_t)h->n_kept_bytes, hipMemcpyDeviceToDevice, st));
-    if (d_off) DDCHK(h, hipMemcpyAsync(d_off, h->kept_off, 8 * ((size_t)h->n_kept + 1), hipMemcpyDeviceToDevice, st));
-    if (d_rows) DDCHK(h, hipMemcpyAsync(d_rows, h->kept_row, 8 * (size_t)h->n_kept, hipMemcpyDeviceToDevice, st));
+        KWCHK(h, hipMemcpyAsync(d_bytes, h->kept_bytes, (size_t)h->n_kept_bytes, hipMemcpyDeviceToDevice, st));
+    if (d_off) KWCHK(h, hipMemcpyAsync(d_off, h->kept_off, 8 * ((size_t)h->n_kept + 1), hipMemcpyDeviceToDevice, st));
+    if (d_rows) KWCHK(h, hipMemcpyAsync(d_rows, h->kept_row, 8 * (size_t)h->n_kept, hipMemcpyDeviceToDevice, st));
     return KW_OK;
 }
 
@@ -1959,27 +1954,27 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
     h->ex_dup = 0;
     h->n_kept = h->n_kept_bytes = 0;
     for (auto &e : h->ex_ev)
-        if (!e) DDCHK(h, hipEventCreate(&e));
-    DDCHK(h, hipEventRecord(h->ex_ev[0], st));
+        if (!e) KWCHK(h, hipEventCreate(&e));
+    KWCHK(h, hipEventRecord(h->ex_ev[0], st));
     if (n > m) {
         // (without exclude rows every link row stays, the duplicates among them too: no holder is below m)
         const int grid = (int)std::min<int64_t>((n - m + BLOCK - 1) / BLOCK, (int64_t)h->cus * 8);
         hipLaunchKernelGGL(dd_exclude_kernel, dim3(grid), dim3(BLOCK), 0, st, d_arena, d_code, S, m, n,
                            unique ? 1 : 0);
-        DDCHK(h, hipGetLastError());
+        KWCHK(h, hipGetLastError());
         unsigned long long cnt[2];
-        DDCHK(h, hipMemcpyAsync(cnt, S.cnt + 11, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        DDCHK(h, hipStreamSynchronize(st));
+        KWCHK(h, hipMemcpyAsync(cnt, S.cnt + 11, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        KWCHK(h, hipStreamSynchronize(st));
         h->ex_seen = (int64_t)cnt[1];
         if (cnt[0]) {
             // the listed rows: their first holders from the host's exact pass of the run
             std::vector<uint32_t> rows;
             if (cnt[0] <= COLLIDE_CAP) {
                 rows.resize(cnt[0]);
-                DDCHK(h, hipMemcpy(rows.data(), S.collide, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost));
+                KWCHK(h, hipMemcpy(rows.data(), S.collide, 4 * (size_t)cnt[0], hipMemcpyDeviceToHost));
             } else {
                 std::vector<uint8_t> code((size_t)(n - m));
-                DDCHK(h, hipMemcpy(code.data(), d_code + m, (size_t)(n - m), hipMemcpyDeviceToHost));
+                KWCHK(h, hipMemcpy(code.data(), d_code + m, (size_t)(n - m), hipMemcpyDeviceToHost));
                 for (int64_t i = 0; i < n - m; ++i)
                     if (code[i] == CODE_COLLIDE) rows.push_back((uint32_t)(m + i));
             }
@@ -2001,11 +1996,11 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
                 const bool seen = (int64_t)it->second < m;
                 const uint8_t c = seen ? (uint8_t)KW_URL_SEEN : unique ? (uint8_t)KW_URL_DUPLICATE : (uint8_t)KW_URL_KEPT;
                 h->ex_seen += seen;
-                DDCHK(h, hipMemcpy(d_code + rows[q], &c, 1, hipMemcpyHostToDevice));
+                KWCHK(h, hipMemcpy(d_code + rows[q], &c, 1, hipMemcpyHostToDevice));
             }
         }
     }
-    DDCHK(h, hipEventRecord(h->ex_ev[1], st));
+    KWCHK(h, hipEventRecord(h->ex_ev[1], st));
     if (n > m) {
         // the remaining rows, dense: the run's compaction over the link rows (row indices from the first link row)
         Scratch L = S;
@@ -2014,8 +2009,8 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
         int rc = compact_kept(h, d_arena, d_code + m, n - m, L, st);
         if (rc) return rc;
     }
-    DDCHK(h, hipEventRecord(h->ex_ev[2], st));
-    DDCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipEventRecord(h->ex_ev[2], st));
+    KWCHK(h, hipStreamSynchronize(st));
     h->ex_dup = h->ex_links - h->ex_seen - h->n_kept;   // (0 unless unique: every link row not seen stays)
     h->ex_serial = h->run_serial;
     return KW_OK;
@@ -2033,7 +2028,7 @@ int kw_dedup_distinct_seen(kw_dedup *h, const uint8_t *d_arena, int64_t m, const
     const size_t words = (size_t)((m + 31) / 32);
     uint8_t *buf = nullptr;   // [0, 32): the counters (listed rows' bits, rows listed, kept exclude rows); the list; the marks
     const size_t marks_at = 32 + 4 * (size_t)cap;
-    DDCHK(h, hipMalloc((void **)&buf, marks_at + 4 * words));
+    KWCHK(h, hipMalloc((void **)&buf, marks_at + 4 * words));
     auto done = [&](int rc) { (void)hipFree(buf); return rc; };
     unsigned long long *cnt = (unsigned long long *)buf;
     uint32_t *listed = (uint32_t *)(buf + 32), *marks = (uint32_t *)(buf + marks_at);
@@ -2143,8 +2138,8 @@ extern "C" int kw_cdx_exclude_last_ms(kw_dedup *h, float *ms, int32_t k)
     if (int rc = exclude_state(h, "kw_cdx_exclude_last_ms")) return rc;
     for (int i = 0; i < k && i < 3; ++i) ms[i] = 0.f;
     if (h->n == 0) return KW_OK;
-    if (k > 0) DDCHK(h, hipEventElapsedTime(&ms[0], h->ev[0], h->ev[4]));
-    for (int i = 1; i < k && i < 3; ++i) DDCHK(h, hipEventElapsedTime(&ms[i], h->ex_ev[i - 1], h->ex_ev[i]));
+    if (k > 0) KWCHK(h, hipEventElapsedTime(&ms[0], h->ev[0], h->ev[4]));
+    for (int i = 1; i < k && i < 3; ++i) KWCHK(h, hipEventElapsedTime(&ms[i], h->ex_ev[i - 1], h->ex_ev[i]));
     return KW_OK;
 }
 
@@ -2152,8 +2147,8 @@ extern "C" int kw_dedup_last_ms(kw_dedup *h, float *ms, int32_t k)
 {
     if (!h || !ms) return KW_EINVAL;
     if (!h->have_run || h->n == 0) { for (int i = 0; i < k; ++i) ms[i] = 0.f; return KW_OK; }
-    for (int i = 0; i < k && i < 4; ++i) DDCHK(h, hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
-    if (k > 4) DDCHK(h, hipEventElapsedTime(&ms[4], h->ev[0], h->ev[4]));
+    for (int i = 0; i < k && i < 4; ++i) KWCHK(h, hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
+    if (k > 4) KWCHK(h, hipEventElapsedTime(&ms[4], h->ev[0], h->ev[4]));
     return KW_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "../../include/kwmatch.h"
 #include "../../include/kwdedup.h"
+#include "kwhandle.hpp"
 
 namespace dd {
 
@@ -93,12 +94,3 @@ int kw_dedup_exclude_pass(kw_dedup *h, const uint8_t *d_arena, int64_t m, uint8_
 // KW_URL_SEEN, out[1] = the exclude rows the keep-first run coded KW_URL_KEPT
 int kw_dedup_distinct_seen(kw_dedup *h, const uint8_t *d_arena, int64_t m, const uint8_t *d_code, int64_t *out,
                            hipStream_t st);
-
-#define DDCHK(h, x)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            (h)->err = std::string("HIP error ") + hipGetErrorString(e_) + " at " #x; \
-            return KW_EHIP;                                                            \
-        }                                                                              \
-    } while (0)

@@ -32,20 +32,18 @@
 #include <string>
 
 #include "../../include/kwrows.h"
+#include "kwdev.hpp"
 #include "kwrows_handle.hpp"
 
 namespace rw {
 
+using kwd::ieq;
 constexpr uint32_t BAD = 0xFFFFFFFFu;
 constexpr uint8_t CELL_NA = 2;          // KWCSV_NA (csrc/kwcsv.c)
 constexpr size_t SCRATCH_PAD = 16;      // the shifted copy reads up to 3 bytes past a part's end
 // the emit's counters (device, 64-bit words)
 enum { E_BAD = 0, E_NUL = 1, E_SCRATCH = 2, E_BYTES = 3, E_TROWS = 4, E_WORDS = 8 };
 
-struct Pin {
-    void *p = nullptr;
-    size_t cap = 0;
-};
 
 struct Emit {
     Buf c_buf, c_off, c_fl;             // the chunk's tokenized cells
@@ -57,7 +55,7 @@ struct Emit {
     int32_t ncols = 0;
     Buf stamps, tcnt, tcur, seg, ord, used, dfl, slen, cq, llen, jl, flags, o_doc, o_ti, o_stamp, scratch, out;
     unsigned long long *tot = nullptr;
-    Pin p_out, p_off, p_flags, p_doc, p_ti, p_stamp;
+    Buf p_out, p_off, p_flags, p_doc, p_ti, p_stamp;   // pinned host memory
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [5]: the fill's start
     float ms[4] = {0, 0, 0, 0};
     bool have = false;
@@ -101,18 +99,6 @@ __device__ __forceinline__ CellStat wave_stat(const uint8_t *__restrict__ s, lon
         }
     }
     return S;
-}
-
-// s[0, m) equals lit (lower case) without regard to ASCII case
-__device__ __forceinline__ bool ieq(const uint8_t *__restrict__ s, long long m, const char *lit, int len)
-{
-    if (m != len) return false;
-    for (int i = 0; i < len; ++i) {
-        uint8_t c = s[i];
-        if (c >= 'A' && c <= 'Z') c = (uint8_t)(c + 32);
-        if (c != (uint8_t)lit[i]) return false;
-    }
-    return true;
 }
 
 // kwcsv_text_witness (csrc/kwcsv.c) of a non-NA cell whose bytes gave S
@@ -389,28 +375,19 @@ __global__ __launch_bounds__(BLOCK) void em_fill_kernel(const uint32_t *__restri
     block_copy(pb, scratch + b0, lb);
 }
 
-static dim3 egrid(uint64_t items) { return dim3((unsigned)std::max<uint64_t>(1, (items + BLOCK - 1) / BLOCK)); }
-
-static int ensure_pinned(kw_rows *h, Pin &b, size_t bytes)
+static int fit_pinned(kw_rows *h, Buf &b, size_t bytes)
 {
-    if (bytes <= b.cap && b.p) return KW_OK;
-    const size_t want = std::max<size_t>(256, bytes + bytes / 4);
-    if (b.p) (void)hipHostFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    RWCHK(h, hipHostMalloc(&b.p, want, hipHostMallocDefault));
-    b.cap = want;
-    return KW_OK;
+    return ensure_pinned(h, &b.p, &b.cap, bytes, std::max<size_t>(256, bytes + bytes / 4));
 }
 
 static int emit_state(kw_rows *h)
 {
     if (h->emit) return KW_OK;
-    RWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     Emit *E = new Emit();
     h->emit = E;
-    RWCHK(h, hipMalloc((void **)&E->tot, E_WORDS * 8));
-    for (auto &e : E->ev) RWCHK(h, hipEventCreate(&e));
+    KWCHK(h, hipMalloc((void **)&E->tot, E_WORDS * 8));
+    for (auto &e : E->ev) KWCHK(h, hipEventCreate(&e));
     return KW_OK;
 }
 
@@ -422,8 +399,8 @@ void emit_destroy(kw_rows *h)
                    &E->slen, &E->cq, &E->llen, &E->jl, &E->flags, &E->o_doc, &E->o_ti, &E->o_stamp, &E->scratch, &E->out};
     for (Buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
-    Pin *pins[] = {&E->p_out, &E->p_off, &E->p_flags, &E->p_doc, &E->p_ti, &E->p_stamp};
-    for (Pin *p : pins)
+    Buf *pins[] = {&E->p_out, &E->p_off, &E->p_flags, &E->p_doc, &E->p_ti, &E->p_stamp};
+    for (Buf *p : pins)
         if (p->p) (void)hipHostFree(p->p);
     if (E->tot) (void)hipFree(E->tot);
     for (auto &e : E->ev)
@@ -455,14 +432,14 @@ extern "C" int kw_rows_cells(kw_rows *h, const uint8_t *cells, const int64_t *co
     if ((rc = emit_state(h))) return rc;
     Emit *E = h->emit;
     hipStream_t st = (hipStream_t)stream;
-    RWCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure(h, E->c_buf, (size_t)nb)) || (rc = ensure(h, E->c_off, (size_t)(nc + 1) * 8)) ||
-        (rc = ensure(h, E->c_fl, (size_t)nc)))
+    KWCHK(h, hipSetDevice(h->device));
+    if ((rc = fit(h, E->c_buf, (size_t)nb)) || (rc = fit(h, E->c_off, (size_t)(nc + 1) * 8)) ||
+        (rc = fit(h, E->c_fl, (size_t)nc)))
         return rc;
-    if (nb) RWCHK(h, hipMemcpyAsync(E->c_buf.p, cells, (size_t)nb, hipMemcpyHostToDevice, st));
-    RWCHK(h, hipMemcpyAsync(E->c_off.p, coff, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, st));
-    if (nc) RWCHK(h, hipMemcpyAsync(E->c_fl.p, cfl, (size_t)nc, hipMemcpyHostToDevice, st));
-    RWCHK(h, hipStreamSynchronize(st));    // the caller's arrays are free again
+    if (nb) KWCHK(h, hipMemcpyAsync(E->c_buf.p, cells, (size_t)nb, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemcpyAsync(E->c_off.p, coff, (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, st));
+    if (nc) KWCHK(h, hipMemcpyAsync(E->c_fl.p, cfl, (size_t)nc, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipStreamSynchronize(st));    // the caller's arrays are free again
     E->cells_docs = n_docs;
     E->ncols = ncols;
     E->borrowed = false;
@@ -499,16 +476,16 @@ extern "C" int kw_rows_cells_device(kw_rows *h, const uint8_t *d_cells, const in
     if ((rc = emit_state(h))) return rc;
     Emit *E = h->emit;
     hipStream_t st = (hipStream_t)stream;
-    RWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     // every later read of the cell bytes must lie inside [0, coff[nc]): the offsets are checked where they are
     unsigned long long bad = 0;
-    RWCHK(h, hipMemsetAsync(E->tot, 0, 8, st));
+    KWCHK(h, hipMemsetAsync(E->tot, 0, 8, st));
     const uint64_t blocks = ((uint64_t)nc + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(em_coff_check_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks))), dim3(BLOCK),
                        0, st, d_coff, (uint64_t)nc, E->tot);
-    RWCHK(h, hipMemcpyAsync(&bad, E->tot, 8, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipStreamSynchronize(st));
-    RWCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(&bad, E->tot, 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     if (bad == (unsigned long long)nc + 1ull) { h->err = "kw_rows_cells_device: a negative offset"; return KW_EINVAL; }
     if (bad) {
         h->err = "kw_rows_cells_device: offsets decrease at cell " + std::to_string((unsigned long long)nc - bad);
@@ -548,13 +525,13 @@ static int emit_rows(const char *who, kw_rows *h, const int32_t *cols, const int
         if (cols[c] < 0 || cols[c] >= E->ncols) { h->err = std::string(who) + ": a column index outside the cells"; return KW_EINVAL; }
     if (n_rows_use < 0 || n_rows_use > h->n_rows) { h->err = std::string(who) + ": n_rows_use outside [0, n_rows]"; return KW_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
-    RWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     for (auto &m : E->ms) m = 0.f;
     const uint32_t nu = (uint32_t)n_rows_use, nd = (uint32_t)n_docs, nt = (uint32_t)h->n_tickers;
     int rc;
-    if ((rc = ensure_pinned(h, E->p_out, 1)) || (rc = ensure_pinned(h, E->p_off, ((size_t)nu + 1) * 8)) ||
-        (rc = ensure_pinned(h, E->p_flags, (size_t)nu * 4)) || (rc = ensure_pinned(h, E->p_doc, (size_t)nu * 4)) ||
-        (rc = ensure_pinned(h, E->p_ti, (size_t)nu * 4)) || (rc = ensure_pinned(h, E->p_stamp, (size_t)nu * 8)))
+    if ((rc = fit_pinned(h, E->p_out, 1)) || (rc = fit_pinned(h, E->p_off, ((size_t)nu + 1) * 8)) ||
+        (rc = fit_pinned(h, E->p_flags, (size_t)nu * 4)) || (rc = fit_pinned(h, E->p_doc, (size_t)nu * 4)) ||
+        (rc = fit_pinned(h, E->p_ti, (size_t)nu * 4)) || (rc = fit_pinned(h, E->p_stamp, (size_t)nu * 8)))
         return rc;
     ((int64_t *)E->p_off.p)[0] = 0;
     if (nu == 0) {
@@ -562,14 +539,14 @@ static int emit_rows(const char *who, kw_rows *h, const int32_t *cols, const int
         return KW_OK;
     }
     const size_t ncell = (size_t)nd * 6;
-    if ((!d_stamp_by_doc && (rc = ensure(h, E->stamps, (size_t)nd * 8))) || (rc = ensure(h, E->tcnt, ((size_t)nt + 1) * 8)) ||
-        (rc = ensure(h, E->tcur, (size_t)nt * 4)) || (rc = ensure(h, E->seg, (size_t)nu * 4)) ||
-        (rc = ensure(h, E->ord, (size_t)nu * 4)) || (rc = ensure(h, E->used, nd)) ||
-        (rc = ensure(h, E->dfl, (size_t)nd * 4)) || (rc = ensure(h, E->slen, (ncell + 1) * 8)) ||
-        (rc = ensure(h, E->cq, ncell)) || (rc = ensure(h, E->llen, ((size_t)nu + 1) * 8)) ||
-        (rc = ensure(h, E->jl, (size_t)nu * 16)) || (rc = ensure(h, E->flags, (size_t)nu * 4)) ||
-        (rc = ensure(h, E->o_doc, (size_t)nu * 4)) || (rc = ensure(h, E->o_ti, (size_t)nu * 4)) ||
-        (rc = ensure(h, E->o_stamp, (size_t)nu * 8)))
+    if ((!d_stamp_by_doc && (rc = fit(h, E->stamps, (size_t)nd * 8))) || (rc = fit(h, E->tcnt, ((size_t)nt + 1) * 8)) ||
+        (rc = fit(h, E->tcur, (size_t)nt * 4)) || (rc = fit(h, E->seg, (size_t)nu * 4)) ||
+        (rc = fit(h, E->ord, (size_t)nu * 4)) || (rc = fit(h, E->used, nd)) ||
+        (rc = fit(h, E->dfl, (size_t)nd * 4)) || (rc = fit(h, E->slen, (ncell + 1) * 8)) ||
+        (rc = fit(h, E->cq, ncell)) || (rc = fit(h, E->llen, ((size_t)nu + 1) * 8)) ||
+        (rc = fit(h, E->jl, (size_t)nu * 16)) || (rc = fit(h, E->flags, (size_t)nu * 4)) ||
+        (rc = fit(h, E->o_doc, (size_t)nu * 4)) || (rc = fit(h, E->o_ti, (size_t)nu * 4)) ||
+        (rc = fit(h, E->o_stamp, (size_t)nu * 8)))
         return rc;
     Cols C;
     for (int c = 0; c < 6; ++c) C.c[c] = cols[c];
@@ -584,73 +561,73 @@ static int emit_rows(const char *who, kw_rows *h, const int32_t *cols, const int
     uint32_t *seg = (uint32_t *)E->seg.p, *ord = (uint32_t *)E->ord.p, *dfl = (uint32_t *)E->dfl.p;
     uint8_t *used = (uint8_t *)E->used.p, *cq = (uint8_t *)E->cq.p;
 
-    RWCHK(h, hipEventRecord(E->ev[0], st));
-    if (!d_stamp_by_doc) RWCHK(h, hipMemcpyAsync(E->stamps.p, stamp_by_doc, (size_t)nd * 8, hipMemcpyHostToDevice, st));
-    RWCHK(h, hipMemsetAsync(E->tot, 0, E_WORDS * 8, st));
-    RWCHK(h, hipMemsetAsync(tcnt, 0, ((size_t)nt + 1) * 8, st));
-    if (nt) RWCHK(h, hipMemsetAsync(E->tcur.p, 0, (size_t)nt * 4, st));
-    RWCHK(h, hipMemsetAsync(seg, 0xFF, (size_t)nu * 4, st));
-    RWCHK(h, hipMemsetAsync(used, 0, nd, st));
-    RWCHK(h, hipMemsetAsync(dfl, 0, (size_t)nd * 4, st));
-    RWCHK(h, hipMemsetAsync(slen, 0, (ncell + 1) * 8, st));
-    RWCHK(h, hipMemsetAsync(llen, 0, ((size_t)nu + 1) * 8, st));
-    RWCHK(h, hipMemsetAsync(jl, 0, (size_t)nu * 16, st));
-    RWCHK(h, hipMemsetAsync(E->flags.p, 0, (size_t)nu * 4, st));
-    RWCHK(h, hipMemsetAsync(E->o_doc.p, 0, (size_t)nu * 4, st));
-    RWCHK(h, hipMemsetAsync(E->o_ti.p, 0, (size_t)nu * 4, st));
-    RWCHK(h, hipMemsetAsync(E->o_stamp.p, 0, (size_t)nu * 8, st));
+    KWCHK(h, hipEventRecord(E->ev[0], st));
+    if (!d_stamp_by_doc) KWCHK(h, hipMemcpyAsync(E->stamps.p, stamp_by_doc, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemsetAsync(E->tot, 0, E_WORDS * 8, st));
+    KWCHK(h, hipMemsetAsync(tcnt, 0, ((size_t)nt + 1) * 8, st));
+    if (nt) KWCHK(h, hipMemsetAsync(E->tcur.p, 0, (size_t)nt * 4, st));
+    KWCHK(h, hipMemsetAsync(seg, 0xFF, (size_t)nu * 4, st));
+    KWCHK(h, hipMemsetAsync(used, 0, nd, st));
+    KWCHK(h, hipMemsetAsync(dfl, 0, (size_t)nd * 4, st));
+    KWCHK(h, hipMemsetAsync(slen, 0, (ncell + 1) * 8, st));
+    KWCHK(h, hipMemsetAsync(llen, 0, ((size_t)nu + 1) * 8, st));
+    KWCHK(h, hipMemsetAsync(jl, 0, (size_t)nu * 16, st));
+    KWCHK(h, hipMemsetAsync(E->flags.p, 0, (size_t)nu * 4, st));
+    KWCHK(h, hipMemsetAsync(E->o_doc.p, 0, (size_t)nu * 4, st));
+    KWCHK(h, hipMemsetAsync(E->o_ti.p, 0, (size_t)nu * 4, st));
+    KWCHK(h, hipMemsetAsync(E->o_stamp.p, 0, (size_t)nu * 8, st));
     // order
-    hipLaunchKernelGGL(em_count_kernel, egrid(nu), dim3(BLOCK), 0, st, row_ti, nu, nt, tcnt, E->tot);
+    hipLaunchKernelGGL(em_count_kernel, grid_of(nu), dim3(BLOCK), 0, st, row_ti, nu, nt, tcnt, E->tot);
     scan_launch(tcnt, (int64_t)nt + 1, h->chunk, E->tot + E_TROWS, st);
-    hipLaunchKernelGGL(em_scatter_kernel, egrid(nu), dim3(BLOCK), 0, st, row_ti, row_doc, nu, nt, nd, (const u64 *)tcnt,
+    hipLaunchKernelGGL(em_scatter_kernel, grid_of(nu), dim3(BLOCK), 0, st, row_ti, row_doc, nu, nt, nd, (const u64 *)tcnt,
                        (uint32_t *)E->tcur.p, seg, used, E->tot);
-    hipLaunchKernelGGL(em_sort_kernel, egrid(nu), dim3(BLOCK), 0, st, (const uint32_t *)seg, nu, row_ti, row_doc,
+    hipLaunchKernelGGL(em_sort_kernel, grid_of(nu), dim3(BLOCK), 0, st, (const uint32_t *)seg, nu, row_ti, row_doc,
                        (const u64 *)tcnt, stamps, ord, (int32_t *)E->o_doc.p, (int32_t *)E->o_ti.p, (int64_t *)E->o_stamp.p);
-    RWCHK(h, hipEventRecord(E->ev[1], st));
+    KWCHK(h, hipEventRecord(E->ev[1], st));
     // measure
-    hipLaunchKernelGGL(em_measure_kernel, egrid((uint64_t)ncell * 64), dim3(BLOCK), 0, st, cbuf, coff, cfl, E->ncols, C, nd,
+    hipLaunchKernelGGL(em_measure_kernel, grid_of((uint64_t)ncell * 64), dim3(BLOCK), 0, st, cbuf, coff, cfl, E->ncols, C, nd,
                        (const uint8_t *)used, slen, cq, dfl, E->tot);
     scan_launch(slen, (int64_t)ncell + 1, h->chunk, E->tot + E_SCRATCH, st);
-    hipLaunchKernelGGL(em_rowlen_kernel, egrid((uint64_t)nu * 64), dim3(BLOCK), 0, st, (const uint32_t *)ord, nu, nd, row_doc,
+    hipLaunchKernelGGL(em_rowlen_kernel, grid_of((uint64_t)nu * 64), dim3(BLOCK), 0, st, (const uint32_t *)ord, nu, nd, row_doc,
                        stamps, (const u64 *)slen, (const uint32_t *)dfl, json, json_off, llen, jl, (uint32_t *)E->flags.p,
                        E->tot);
     scan_launch(llen, (int64_t)nu + 1, h->chunk, E->tot + E_BYTES, st);
-    RWCHK(h, hipEventRecord(E->ev[2], st));
+    KWCHK(h, hipEventRecord(E->ev[2], st));
     u64 tot[E_WORDS];
-    RWCHK(h, hipMemcpyAsync(tot, E->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipStreamSynchronize(st));
-    RWCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(tot, E->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     if (tot[E_BAD]) { h->err = std::string(who) + ": a row's ticker or document is beyond the tables"; return KW_EINVAL; }
-    for (int k = 0; k < 2; ++k) RWCHK(h, hipEventElapsedTime(&E->ms[k], E->ev[k], E->ev[k + 1]));
+    for (int k = 0; k < 2; ++k) KWCHK(h, hipEventElapsedTime(&E->ms[k], E->ev[k], E->ev[k + 1]));
     if (tot[E_NUL]) {
         *verdict = KW_EMIT_NUL;
         E->have = true;
         return KW_OK;
     }
     const u64 nbytes = tot[E_BYTES];
-    if ((rc = ensure(h, E->scratch, (size_t)tot[E_SCRATCH] + SCRATCH_PAD)) || (rc = ensure(h, E->out, (size_t)nbytes)) ||
-        (rc = ensure_pinned(h, E->p_out, (size_t)nbytes)))
+    if ((rc = fit(h, E->scratch, (size_t)tot[E_SCRATCH] + SCRATCH_PAD)) || (rc = fit(h, E->out, (size_t)nbytes)) ||
+        (rc = fit_pinned(h, E->p_out, (size_t)nbytes)))
         return rc;
     // fill (timed from here: the buffers above may just have grown)
-    RWCHK(h, hipEventRecord(E->ev[5], st));
-    hipLaunchKernelGGL(em_render_kernel, egrid((uint64_t)ncell * 64), dim3(BLOCK), 0, st, cbuf, coff, cfl, E->ncols, C, nd,
+    KWCHK(h, hipEventRecord(E->ev[5], st));
+    hipLaunchKernelGGL(em_render_kernel, grid_of((uint64_t)ncell * 64), dim3(BLOCK), 0, st, cbuf, coff, cfl, E->ncols, C, nd,
                        (const uint8_t *)used, (const u64 *)slen, (const uint8_t *)cq, (uint8_t *)E->scratch.p);
     hipLaunchKernelGGL(em_fill_kernel, dim3(nu), dim3(BLOCK), 0, st, (const uint32_t *)ord, nu, nd, row_doc, stamps,
                        (const u64 *)slen, (const uint8_t *)E->scratch.p, json, json_off, (const u64 *)jl, (const u64 *)llen,
                        (uint8_t *)E->out.p);
-    RWCHK(h, hipEventRecord(E->ev[3], st));
+    KWCHK(h, hipEventRecord(E->ev[3], st));
     // copy
-    RWCHK(h, hipMemcpyAsync(E->p_out.p, E->out.p, (size_t)nbytes, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipMemcpyAsync(E->p_off.p, llen, ((size_t)nu + 1) * 8, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipMemcpyAsync(E->p_flags.p, E->flags.p, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipMemcpyAsync(E->p_doc.p, E->o_doc.p, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipMemcpyAsync(E->p_ti.p, E->o_ti.p, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipMemcpyAsync(E->p_stamp.p, E->o_stamp.p, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipEventRecord(E->ev[4], st));
-    RWCHK(h, hipStreamSynchronize(st));
-    RWCHK(h, hipGetLastError());
-    RWCHK(h, hipEventElapsedTime(&E->ms[2], E->ev[5], E->ev[3]));
-    RWCHK(h, hipEventElapsedTime(&E->ms[3], E->ev[3], E->ev[4]));
+    KWCHK(h, hipMemcpyAsync(E->p_out.p, E->out.p, (size_t)nbytes, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(E->p_off.p, llen, ((size_t)nu + 1) * 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(E->p_flags.p, E->flags.p, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(E->p_doc.p, E->o_doc.p, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(E->p_ti.p, E->o_ti.p, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(E->p_stamp.p, E->o_stamp.p, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipEventRecord(E->ev[4], st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventElapsedTime(&E->ms[2], E->ev[5], E->ev[3]));
+    KWCHK(h, hipEventElapsedTime(&E->ms[3], E->ev[3], E->ev[4]));
     *n_out_bytes = (int64_t)nbytes;
     E->have = true;
     return KW_OK;
@@ -693,9 +670,9 @@ extern "C" int kw_rows_copy_index(kw_rows *h, int32_t *row_doc, int32_t *row_ti)
     if (!h->have_run) { h->err = "kw_rows_copy_index: no run"; return KW_ESTATE; }
     if (h->n_rows > 0 && (!row_doc || !row_ti)) { h->err = "kw_rows_copy_index: bad arguments"; return KW_EINVAL; }
     if (h->n_rows == 0) return KW_OK;
-    RWCHK(h, hipSetDevice(h->device));
-    RWCHK(h, hipMemcpy(row_doc, h->row_doc.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
-    RWCHK(h, hipMemcpy(row_ti, h->row_ti.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipMemcpy(row_doc, h->row_doc.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
+    KWCHK(h, hipMemcpy(row_ti, h->row_ti.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
     return KW_OK;
 }
 

@@ -31,15 +31,15 @@
 #include "../../include/kwingest.h"
 #define KWST_FN __device__ __forceinline__ static
 #include "../../include/kwstamps.h"
-#include "kwenv.hpp"
+#include "kwdev.hpp"
+#include "kwhandle.hpp"
 
 namespace ig {
 
+using namespace kwd;   // BLOCK, TILE, NONE and the primitives
+using namespace kwh;
 typedef unsigned long long u64;
-constexpr int BLOCK = 256;
-constexpr int TILE = BLOCK * 16;     // bytes of text a block classifies at once
 constexpr int MAX_GRID = 2048;
-constexpr u64 NONE = ~0ull;
 constexpr uint32_t F_QUOTED = 1u, F_NA = 2u, F_TEXT = 4u, F_CANON = 8u;   // KWCSV_* (csrc/kwcsv.c)
 constexpr uint32_t W_QUOTED = 1u, W_NEEDQ = 2u;                           // the tile pass's bits of a cell
 constexpr int ARENA_PAD = 64;
@@ -69,116 +69,11 @@ struct Args {
     uint8_t *cells;
 };
 
-__device__ __forceinline__ uint32_t eq4(uint32_t v, uint32_t pat)   // 0x80 in exactly the bytes equal to pat's
-{
-    const uint32_t d = v ^ pat;
-    return ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t bits4(uint32_t m) { return (((m >> 7) & 0x01010101u) * 0x01020408u) >> 24; }
-__device__ __forceinline__ uint32_t mask16(uint4 v, uint32_t c)     // bit k set iff byte k of the 16 equals c
-{
-    const uint32_t pat = c * 0x01010101u;
-    return bits4(eq4(v.x, pat)) | (bits4(eq4(v.y, pat)) << 4) | (bits4(eq4(v.z, pat)) << 8) | (bits4(eq4(v.w, pat)) << 12);
-}
-
-__device__ __forceinline__ u64 wave_min(u64 x)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const u64 y = __shfl_xor(x, d, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-// exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
-__device__ __forceinline__ u64 block_scan(u64 x, u64 *ws, u64 *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    __syncthreads();   // ws free again
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (int k = 0; k < BLOCK / 64; ++k) {
-        const u64 s = ws[k];
-        if (k < wv) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - x;
-}
-
-// The first byte a strict UTF-8 decoder stops at among the code points that start in [p, p + 16): from the code
-// point boundary at or before p (four continuation bytes in a row hold an error at or before p).
-__device__ u64 utf8_lane(const uint8_t *__restrict__ text, long long n, long long p)
-{
-    long long q = p;
-    if ((text[p] & 0xC0u) == 0x80u) {
-        int back = 1;
-        while (back <= 3 && p - back >= 0 && (text[p - back] & 0xC0u) == 0x80u) ++back;
-        if (back > 3 || p - back < 0) return (u64)p;
-        q = p - back;
-    }
-    const long long stop = p + 16 < n ? p + 16 : n;
-    while (q < stop) {
-        const uint32_t c = text[q];
-        if (c < 0x80u) { ++q; continue; }
-        int need;
-        uint32_t lo = 0x80u, hi = 0xBFu;
-        if (c >= 0xC2u && c <= 0xDFu) need = 1;
-        else if (c == 0xE0u) { need = 2; lo = 0xA0u; }
-        else if (c == 0xEDu) { need = 2; hi = 0x9Fu; }
-        else if (c >= 0xE1u && c <= 0xEFu) need = 2;
-        else if (c == 0xF0u) { need = 3; lo = 0x90u; }
-        else if (c >= 0xF1u && c <= 0xF3u) need = 3;
-        else if (c == 0xF4u) { need = 3; hi = 0x8Fu; }
-        else return (u64)q;
-        for (int k = 1; k <= need; ++k) {
-            if (q + k >= n) return (u64)q;
-            const uint32_t b = text[q + k];
-            if (b < lo || b > hi) return (u64)q;
-            lo = 0x80u; hi = 0xBFu;
-        }
-        q += need + 1;
-    }
-    return NONE;
-}
-
 __global__ __launch_bounds__(BLOCK) void ig_quotes_kernel(const uint8_t *__restrict__ text, long long n, long long ntiles,
                                                           u64 *__restrict__ tq, Dev *__restrict__ D)
 {
-    __shared__ u64 ws[BLOCK / 64];
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const long long p = tile * TILE + (long long)threadIdx.x * 16;
-        uint32_t q = 0;
-        u64 ez = NONE, e8 = NONE;
-        if (p < n) {
-            // (the text is readable up to the next multiple of 16 past n: kw_ingest_parse's contract)
-            const uint4 v = *(const uint4 *)(text + p);
-            const uint32_t valid = n - p >= 16 ? 0xFFFFu : (1u << (int)(n - p)) - 1u;
-            q = mask16(v, 0x22u) & valid;
-            const uint32_t z = mask16(v, 0u) & valid;
-            const uint32_t hb = (bits4(v.x & 0x80808080u) | (bits4(v.y & 0x80808080u) << 4) |
-                                 (bits4(v.z & 0x80808080u) << 8) | (bits4(v.w & 0x80808080u) << 12)) & valid;
-            if (z) ez = (u64)p + __builtin_ctz(z);
-            if (hb) e8 = utf8_lane(text, n, p);
-        }
-        if (__any((ez & e8) != NONE)) {   // (rare: one atomic a wave and condition)
-            ez = wave_min(ez);
-            e8 = wave_min(e8);
-            if ((threadIdx.x & 63) == 0) {
-                if (ez != NONE) atomicMin(&D->errs.nul, ez);
-                if (e8 != NONE) atomicMin(&D->errs.utf8, e8);
-            }
-        }
-        u64 total;
-        (void)block_scan((u64)__popc(q), ws, &total);
-        if (threadIdx.x == 0) tq[tile] = total;
-    }
+    // (the text is readable up to the next multiple of 16 past n: kw_ingest_parse's contract)
+    quotes_tiles(text, n, ntiles, tq, &D->errs.nul, &D->errs.utf8);
 }
 
 // Block b: the exclusive scan of a[b][0, m) in place (m from *m_dev when given), its total to total[b].  With
@@ -503,18 +398,6 @@ __global__ __launch_bounds__(BLOCK) void ig_spans_kernel(Args A, long long *__re
     }
 }
 
-// s[0, m) equals lit (lower case) without regard to ASCII case
-__device__ __forceinline__ bool ieq(const uint8_t *__restrict__ s, long long m, const char *lit, int len)
-{
-    if (m != len) return false;
-    for (int i = 0; i < len; ++i) {
-        uint8_t c = s[i];
-        if (c >= 'A' && c <= 'Z') c = (uint8_t)(c + 32);
-        if (c != (uint8_t)lit[i]) return false;
-    }
-    return true;
-}
-
 // kwcsv_text_witness (csrc/kwcsv.c)
 __device__ bool text_witness(const uint8_t *__restrict__ s, long long n)
 {
@@ -782,11 +665,6 @@ __global__ __launch_bounds__(BLOCK) void ig_gather_kernel(const Dev *__restrict_
     }
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
 }  // namespace ig
 
 struct kw_ingest {
@@ -817,49 +695,14 @@ struct kw_ingest {
     bool have_spans = false;
 };
 
-#define IGCHK(h, x)                                                                    \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            (h)->err = std::string("HIP error ") + hipGetErrorString(e_) + " at " #x; \
-            return KW_EHIP;                                                            \
-        }                                                                              \
-    } while (0)
-
 namespace ig {
 
 // a buffer of at least `bytes` (contents are not kept when it grows; it grows by half again at least)
-static int ensure(kw_ingest *h, Buf &b, size_t bytes)
-{
-    if (b.cap >= bytes && b.p) return KW_OK;
-    size_t want = bytes + bytes / 2 + 256;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    IGCHK(h, hipMalloc(&b.p, want));
-    b.cap = want;
-    return KW_OK;
-}
+static int fit(kw_ingest *h, Buf &b, size_t bytes) { return ensure(h, b, bytes, bytes + bytes / 2 + 256); }
 
 // The cap on every launch grid of a call: MAX_GRID, or the tests' KW_TEST_INGEST_GRID in [1, MAX_GRID] (read per
-// call through kw_env: the kernels' loops then make several trips on a small text).
-static int grid_cap()
-{
-    if (const char *e = kw_env("KW_TEST_INGEST_GRID")) {
-        char *end = nullptr;
-        const long g = strtol(e, &end, 10);
-        if (end != e && *end == '\0' && g >= 1 && g <= MAX_GRID) return (int)g;
-    }
-    return MAX_GRID;
-}
-
-static dim3 grid_for(long long items, int cap)
-{
-    long long g = (items + BLOCK - 1) / BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return dim3((unsigned)g);
-}
+// call: the kernels' loops then make several trips on a small text).
+static int grid_cap() { return (int)env_int("KW_TEST_INGEST_GRID", 1, MAX_GRID, MAX_GRID); }
 
 }  // namespace ig
 
@@ -944,7 +787,7 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     *bad_pos = 0;
     hipStream_t st = (hipStream_t)stream;
     h->stream = st;
-    IGCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     const long long n = n_bytes, ncols = h->ncols;
     const long long ntiles = (n + TILE - 1) / TILE;
     // a record has ncols - 1 delimiters at least: the text holds at most n / ncols + 1 records that pass
@@ -952,15 +795,15 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     if (rows_cap > max_rows) rows_cap = max_rows;
     const long long cells_cap = rows_cap * ncols;
     int rc;
-    if ((rc = ensure(h, h->tiles, (size_t)(ntiles + 1) * 4 * 8)) || (rc = ensure(h, h->cells, (size_t)n + 32)) ||
-        (rc = ensure(h, h->coff, (size_t)(cells_cap + 1) * 8)) || (rc = ensure(h, h->cflw, (size_t)cells_cap * 4)) ||
-        (rc = ensure(h, h->cfl, (size_t)cells_cap)) ||
-        (rc = ensure(h, h->arena, (size_t)n + 6 * (size_t)rows_cap + ARENA_PAD + 32)) ||
-        (rc = ensure(h, h->aoff, (size_t)(2 * rows_cap + 1) * 8)) || (rc = ensure(h, h->us, (size_t)rows_cap * 8)) ||
-        (rc = ensure(h, h->kind, (size_t)rows_cap)) || (rc = ensure(h, h->doff, (size_t)rows_cap * 4)))
+    if ((rc = fit(h, h->tiles, (size_t)(ntiles + 1) * 4 * 8)) || (rc = fit(h, h->cells, (size_t)n + 32)) ||
+        (rc = fit(h, h->coff, (size_t)(cells_cap + 1) * 8)) || (rc = fit(h, h->cflw, (size_t)cells_cap * 4)) ||
+        (rc = fit(h, h->cfl, (size_t)cells_cap)) ||
+        (rc = fit(h, h->arena, (size_t)n + 6 * (size_t)rows_cap + ARENA_PAD + 32)) ||
+        (rc = fit(h, h->aoff, (size_t)(2 * rows_cap + 1) * 8)) || (rc = fit(h, h->us, (size_t)rows_cap * 8)) ||
+        (rc = fit(h, h->kind, (size_t)rows_cap)) || (rc = fit(h, h->doff, (size_t)rows_cap * 4)))
         return rc;
     const int zn = h->zn;
-    if (zn && ((rc = ensure(h, h->stamps, (size_t)rows_cap * 8)) || (rc = ensure(h, h->native, (size_t)rows_cap)))) return rc;
+    if (zn && ((rc = fit(h, h->stamps, (size_t)rows_cap * 8)) || (rc = fit(h, h->native, (size_t)rows_cap)))) return rc;
     Dev init;
     memset(&init, 0, sizeof(init));
     init.errs.nul = init.errs.utf8 = init.errs.quote = init.errs.cr = init.errs.blank = init.errs.fields = NONE;
@@ -984,10 +827,10 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     const int gcap = grid_cap();
     const dim3 tgrid((unsigned)(ntiles < 1 ? 1 : (ntiles > gcap ? gcap : ntiles)));
 
-    IGCHK(h, hipEventRecord(h->ev[0], st));
-    IGCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
-    IGCHK(h, hipMemsetAsync(A.coff, 0, 8, st));
-    IGCHK(h, hipMemsetAsync(A.cflw, 0, (size_t)cells_cap * 4, st));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
+    KWCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemsetAsync(A.coff, 0, 8, st));
+    KWCHK(h, hipMemsetAsync(A.cflw, 0, (size_t)cells_cap * 4, st));
     // classify
     hipLaunchKernelGGL(ig_quotes_kernel, tgrid, dim3(BLOCK), 0, st, d_text, n, ntiles, A.tq, h->D);
     {
@@ -997,7 +840,7 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
         S.m = ntiles;
         hipLaunchKernelGGL(ig_scan_kernel, dim3(1), dim3(BLOCK), 0, st, S);
     }
-    IGCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipEventRecord(h->ev[1], st));
     // cells
     hipLaunchKernelGGL(ig_tile_kernel<0>, tgrid, dim3(BLOCK), 0, st, A);
     {
@@ -1010,20 +853,20 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
     hipLaunchKernelGGL(ig_tile_kernel<1>, tgrid, dim3(BLOCK), 0, st, A);
     hipLaunchKernelGGL(ig_finish_kernel, dim3(1), dim3(64), 0, st, h->D, (const long long *)A.coff, n, A.final_,
                        (long long)max_rows, (int)ncols);
-    hipLaunchKernelGGL(ig_flags_kernel, grid_for(cells_cap, gcap), dim3(BLOCK), 0, st, h->D, (const uint8_t *)A.cells,
+    hipLaunchKernelGGL(ig_flags_kernel, grid_for(cells_cap, BLOCK, gcap), dim3(BLOCK), 0, st, h->D, (const uint8_t *)A.cells,
                        (const long long *)A.coff, (const uint32_t *)A.cflw, (uint8_t *)h->cfl.p, (int)ncols, h->cols,
                        (const uint8_t *)h->d_na, (const int *)h->d_na_off, h->n_na);
-    IGCHK(h, hipEventRecord(h->ev[2], st));
+    KWCHK(h, hipEventRecord(h->ev[2], st));
     // arena + dates
-    hipLaunchKernelGGL(ig_rows_kernel, grid_for(rows_cap, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
+    hipLaunchKernelGGL(ig_rows_kernel, grid_for(rows_cap, BLOCK, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
                        (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p, (int)ncols, h->cols,
                        (long long *)h->us.p, (uint8_t *)h->kind.p, (int *)h->doff.p, (u64 *)h->aoff.p);
     if (zn) {
-        IGCHK(h, hipEventRecord(h->ev[4], st));
-        hipLaunchKernelGGL(ig_stamps_kernel, grid_for(rows_cap, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
+        KWCHK(h, hipEventRecord(h->ev[4], st));
+        hipLaunchKernelGGL(ig_stamps_kernel, grid_for(rows_cap, BLOCK, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
                            (const long long *)h->us.p, (const uint8_t *)h->kind.p, (const int64_t *)h->zat.p,
                            (const int32_t *)h->zoff.p, zn, (int64_t *)h->stamps.p, (uint8_t *)h->native.p);
-        IGCHK(h, hipEventRecord(h->ev[5], st));
+        KWCHK(h, hipEventRecord(h->ev[5], st));
     }
     {
         ScanArgs S{};
@@ -1035,17 +878,17 @@ extern "C" int kw_ingest_parse(kw_ingest *h, const uint8_t *d_text, int64_t n_by
         S.m_add = 1;
         hipLaunchKernelGGL(ig_scan_kernel, dim3(1), dim3(BLOCK), 0, st, S);
     }
-    hipLaunchKernelGGL(ig_gather_kernel<true>, grid_for((n + 6 * rows_cap + ARENA_PAD) / 16 + 1, gcap), dim3(BLOCK), 0,
+    hipLaunchKernelGGL(ig_gather_kernel<true>, grid_for((n + 6 * rows_cap + ARENA_PAD) / 16 + 1, BLOCK, gcap), dim3(BLOCK), 0,
                        st, (const Dev *)h->D, (const uint8_t *)A.cells, (const long long *)A.coff, (const uint8_t *)h->cfl.p,
                        (int)ncols, h->cols.c[0], h->cols.c[1], (const u64 *)h->aoff.p, (uint8_t *)h->arena.p, ARENA_PAD);
-    IGCHK(h, hipEventRecord(h->ev[3], st));
-    IGCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
-    IGCHK(h, hipStreamSynchronize(st));
-    IGCHK(h, hipGetLastError());
-    for (int k = 0; k < 3; ++k) IGCHK(h, hipEventElapsedTime(&h->ms[k], h->ev[k], h->ev[k + 1]));
-    IGCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[3]));
+    KWCHK(h, hipEventRecord(h->ev[3], st));
+    KWCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    for (int k = 0; k < 3; ++k) KWCHK(h, hipEventElapsedTime(&h->ms[k], h->ev[k], h->ev[k + 1]));
+    KWCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[3]));
     h->ms[4] = 0.f;
-    if (zn) IGCHK(h, hipEventElapsedTime(&h->ms[4], h->ev[4], h->ev[5]));
+    if (zn) KWCHK(h, hipEventElapsedTime(&h->ms[4], h->ev[4], h->ev[5]));
     *verdict = h->H->verdict;
     *bad_pos = h->H->bad_pos;
     *n_rows = h->H->n_rows;
@@ -1065,15 +908,10 @@ extern "C" int kw_ingest_stage(kw_ingest *h, int32_t slot, int64_t n_bytes, uint
         h->err = "kw_ingest_stage: bad arguments";
         return KW_EINVAL;
     }
-    IGCHK(h, hipSetDevice(h->device));
-    if (h->stage_cap[slot] < (size_t)n_bytes || !h->stage[slot]) {
-        if (h->stage[slot]) IGCHK(h, hipHostFree(h->stage[slot]));
-        h->stage[slot] = nullptr;
-        h->stage_cap[slot] = 0;
-        const size_t want = (size_t)n_bytes + (size_t)n_bytes / 4 + 4096;
-        IGCHK(h, hipHostMalloc(&h->stage[slot], want, hipHostMallocDefault));
-        h->stage_cap[slot] = want;
-    }
+    KWCHK(h, hipSetDevice(h->device));
+    const size_t nb = (size_t)n_bytes;
+    const int rc = ensure_pinned(h, &h->stage[slot], &h->stage_cap[slot], nb, nb + nb / 4 + 4096);
+    if (rc) return rc;
     *host = (uint8_t *)h->stage[slot];
     return KW_OK;
 }
@@ -1086,11 +924,11 @@ extern "C" int kw_ingest_upload(kw_ingest *h, int32_t slot, int64_t start, int64
         h->err = "kw_ingest_upload: bad arguments";
         return KW_EINVAL;
     }
-    IGCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure(h, h->text, (size_t)n_bytes + 16))) return rc;
+    if ((rc = fit(h, h->text, (size_t)n_bytes + 16))) return rc;
     if (n_bytes)
-        IGCHK(h, hipMemcpyAsync(h->text.p, (const uint8_t *)h->stage[slot] + start, (size_t)n_bytes,
+        KWCHK(h, hipMemcpyAsync(h->text.p, (const uint8_t *)h->stage[slot] + start, (size_t)n_bytes,
                                 hipMemcpyHostToDevice, (hipStream_t)stream));
     *d_text = (const uint8_t *)h->text.p;
     return KW_OK;
@@ -1127,11 +965,11 @@ extern "C" int kw_ingest_arena(kw_ingest *h, const uint8_t **d_arena, const int6
 // the date arrays of the last parse into host arrays (off_s may be null)
 static int copy_dates(kw_ingest *h, size_t nr, int64_t *us, uint8_t *kind, int32_t *off_s)
 {
-    IGCHK(h, hipSetDevice(h->device));
-    IGCHK(h, hipMemcpyAsync(us, h->us.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipMemcpyAsync(kind, h->kind.p, nr, hipMemcpyDeviceToHost, h->stream));
-    if (off_s) IGCHK(h, hipMemcpyAsync(off_s, h->doff.p, nr * 4, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipMemcpyAsync(us, h->us.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipMemcpyAsync(kind, h->kind.p, nr, hipMemcpyDeviceToHost, h->stream));
+    if (off_s) KWCHK(h, hipMemcpyAsync(off_s, h->doff.p, nr * 4, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipStreamSynchronize(h->stream));
     return KW_OK;
 }
 
@@ -1172,11 +1010,11 @@ extern "C" int kw_ingest_zone(kw_ingest *h, const int64_t *at, const int32_t *of
     }
     h->zn = 0;
     if (n_trans == 0) return KW_OK;
-    IGCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure(h, h->zat, ((size_t)n_trans + 1) * 8)) || (rc = ensure(h, h->zoff, (size_t)n_trans * 4))) return rc;
-    IGCHK(h, hipMemcpy(h->zat.p, at, ((size_t)n_trans + 1) * 8, hipMemcpyHostToDevice));
-    IGCHK(h, hipMemcpy(h->zoff.p, off, (size_t)n_trans * 4, hipMemcpyHostToDevice));
+    if ((rc = fit(h, h->zat, ((size_t)n_trans + 1) * 8)) || (rc = fit(h, h->zoff, (size_t)n_trans * 4))) return rc;
+    KWCHK(h, hipMemcpy(h->zat.p, at, ((size_t)n_trans + 1) * 8, hipMemcpyHostToDevice));
+    KWCHK(h, hipMemcpy(h->zoff.p, off, (size_t)n_trans * 4, hipMemcpyHostToDevice));
     h->zn = n_trans;
     return KW_OK;
 }
@@ -1188,10 +1026,10 @@ extern "C" int kw_ingest_stamps(kw_ingest *h, int64_t *stamps, uint8_t *native)
     const size_t nr = (size_t)h->H->n_rows;
     if (nr && (!stamps || !native)) { h->err = "kw_ingest_stamps: bad arguments"; return KW_EINVAL; }
     if (!nr) return KW_OK;
-    IGCHK(h, hipSetDevice(h->device));
-    IGCHK(h, hipMemcpyAsync(stamps, h->stamps.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipMemcpyAsync(native, h->native.p, nr, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipMemcpyAsync(stamps, h->stamps.p, nr * 8, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipMemcpyAsync(native, h->native.p, nr, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipStreamSynchronize(h->stream));
     return KW_OK;
 }
 
@@ -1217,11 +1055,11 @@ extern "C" int kw_ingest_copy_cells(kw_ingest *h, uint8_t *cells, int64_t *coff,
     IG_NEED_PARSE(h, "kw_ingest_copy_cells");
     const size_t nc = (size_t)h->H->n_rows * (size_t)h->ncols, nb = (size_t)h->H->cell_bytes;
     if (!coff || (nc && !cfl) || (nb && !cells)) { h->err = "kw_ingest_copy_cells: bad arguments"; return KW_EINVAL; }
-    IGCHK(h, hipSetDevice(h->device));
-    if (nb) IGCHK(h, hipMemcpyAsync(cells, h->cells.p, nb, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipMemcpyAsync(coff, h->coff.p, (nc + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-    if (nc) IGCHK(h, hipMemcpyAsync(cfl, h->cfl.p, nc, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipSetDevice(h->device));
+    if (nb) KWCHK(h, hipMemcpyAsync(cells, h->cells.p, nb, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipMemcpyAsync(coff, h->coff.p, (nc + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    if (nc) KWCHK(h, hipMemcpyAsync(cfl, h->cfl.p, nc, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipStreamSynchronize(h->stream));
     return KW_OK;
 }
 
@@ -1230,10 +1068,10 @@ extern "C" int kw_ingest_copy_arena(kw_ingest *h, uint8_t *arena, int64_t *off)
     IG_NEED_PARSE(h, "kw_ingest_copy_arena");
     const size_t nr = (size_t)h->H->n_rows, nb = (size_t)h->H->arena_bytes + ARENA_PAD;
     if (!arena || !off) { h->err = "kw_ingest_copy_arena: bad arguments"; return KW_EINVAL; }
-    IGCHK(h, hipSetDevice(h->device));
-    IGCHK(h, hipMemcpyAsync(arena, h->arena.p, nb, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipMemcpyAsync(off, h->aoff.p, (2 * nr + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipMemcpyAsync(arena, h->arena.p, nb, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipMemcpyAsync(off, h->aoff.p, (2 * nr + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipStreamSynchronize(h->stream));
     return KW_OK;
 }
 
@@ -1248,13 +1086,13 @@ extern "C" int kw_ingest_copy_column(kw_ingest *h, int32_t col, uint8_t *bytes, 
     off[0] = 0;
     if (!nr) return KW_OK;
     hipStream_t st = h->stream;
-    IGCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure(h, h->col_off, (size_t)(nr + 1) * 8)) || (rc = ensure(h, h->col_fl, (size_t)nr)) ||
-        (rc = ensure(h, h->col_buf, (size_t)h->H->cell_bytes + 32)))
+    if ((rc = fit(h, h->col_off, (size_t)(nr + 1) * 8)) || (rc = fit(h, h->col_fl, (size_t)nr)) ||
+        (rc = fit(h, h->col_buf, (size_t)h->H->cell_bytes + 32)))
         return rc;
     const int gcap = grid_cap();
-    hipLaunchKernelGGL(ig_collen_kernel, grid_for(nr, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
+    hipLaunchKernelGGL(ig_collen_kernel, grid_for(nr, BLOCK, gcap), dim3(BLOCK), 0, st, (const Dev *)h->D,
                        (const long long *)h->coff.p, (const uint8_t *)h->cfl.p, h->ncols, (int)col, (u64 *)h->col_off.p,
                        (uint8_t *)h->col_fl.p);
     {
@@ -1264,16 +1102,16 @@ extern "C" int kw_ingest_copy_column(kw_ingest *h, int32_t col, uint8_t *bytes, 
         S.m = nr + 1;
         hipLaunchKernelGGL(ig_scan_kernel, dim3(1), dim3(BLOCK), 0, st, S);
     }
-    hipLaunchKernelGGL(ig_gather_kernel<false>, grid_for(h->H->cell_bytes / 16 + 1, gcap), dim3(BLOCK), 0, st,
+    hipLaunchKernelGGL(ig_gather_kernel<false>, grid_for(h->H->cell_bytes / 16 + 1, BLOCK, gcap), dim3(BLOCK), 0, st,
                        (const Dev *)h->D, (const uint8_t *)h->cells.p, (const long long *)h->coff.p,
                        (const uint8_t *)h->cfl.p, h->ncols, (int)col, 0, (const u64 *)h->col_off.p, (uint8_t *)h->col_buf.p, 0);
-    IGCHK(h, hipMemcpyAsync(off, h->col_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, st));
-    IGCHK(h, hipMemcpyAsync(fl, h->col_fl.p, (size_t)nr, hipMemcpyDeviceToHost, st));
-    IGCHK(h, hipStreamSynchronize(st));
-    IGCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(off, h->col_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(fl, h->col_fl.p, (size_t)nr, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     const int64_t nb = off[nr];
     if (nb > cap) { h->err = "kw_ingest_copy_column: the column holds " + std::to_string(nb) + " bytes"; return KW_EOVERFLOW; }
-    if (nb) IGCHK(h, hipMemcpy(bytes, h->col_buf.p, (size_t)nb, hipMemcpyDeviceToHost));
+    if (nb) KWCHK(h, hipMemcpy(bytes, h->col_buf.p, (size_t)nb, hipMemcpyDeviceToHost));
     return KW_OK;
 }
 
@@ -1287,9 +1125,9 @@ extern "C" int kw_ingest_spans(kw_ingest *h, const int64_t **d_start, const int6
     }
     const long long nr = h->H->n_rows;
     if (!h->have_spans) {
-        IGCHK(h, hipSetDevice(h->device));
+        KWCHK(h, hipSetDevice(h->device));
         int rc;
-        if ((rc = ensure(h, h->spans, (size_t)(2 * nr + 2) * 8))) return rc;
+        if ((rc = fit(h, h->spans, (size_t)(2 * nr + 2) * 8))) return rc;
         if (nr) {
             Args A{};
             A.text = h->ptext;
@@ -1304,7 +1142,7 @@ extern "C" int kw_ingest_spans(kw_ingest *h, const int64_t **d_start, const int6
             const dim3 tgrid((unsigned)(A.ntiles < 1 ? 1 : (A.ntiles > gcap ? gcap : A.ntiles)));
             hipLaunchKernelGGL(ig_spans_kernel, tgrid, dim3(BLOCK), 0, h->stream, A, (long long *)h->spans.p,
                                (long long *)h->spans.p + nr);
-            IGCHK(h, hipGetLastError());
+            KWCHK(h, hipGetLastError());
         }
         h->have_spans = true;
     }
@@ -1328,10 +1166,10 @@ extern "C" int kw_ingest_copy_spans(kw_ingest *h, int64_t *start, int64_t *end)
     if ((rc = kw_ingest_spans(h, &ds, &de, &nr, &nc, &dt, &nb))) return rc;
     if (!nr) return KW_OK;
     if (!start || !end) { h->err = "kw_ingest_copy_spans: bad arguments"; return KW_EINVAL; }
-    IGCHK(h, hipMemcpyAsync(start, ds, (size_t)nr * 8, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipMemcpyAsync(end, de, (size_t)nr * 8, hipMemcpyDeviceToHost, h->stream));
-    IGCHK(h, hipStreamSynchronize(h->stream));
-    IGCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(start, ds, (size_t)nr * 8, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipMemcpyAsync(end, de, (size_t)nr * 8, hipMemcpyDeviceToHost, h->stream));
+    KWCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipGetLastError());
     return KW_OK;
 }
 

@@ -6,8 +6,7 @@
 // Stages of kw_rows_run (kernels exchange data only across launches; every size is found by a count pass and
 // an exclusive scan, the buffers belong to the handle and grow on demand):
 //   order    rw_count_kernel    records per document (documents without a date and doc >= n_docs count nothing)
-//            rw_scan_*          exclusive scan of 64-bit counts in two levels (chunk sums, their scan in one
-//                               block, each chunk from its prefix; the shape of cx_scan_* / dd_tile_sums)
+//            scan_launch        the device scan of kwhandle.hpp (kwscan.hip)
 //            rw_scatter_kernel  records into their document's segment (any order inside it)
 //            rw_sort_kernel     a lane per record ranks it inside its segment by (field, pattern, pos): the
 //                               segment is read by every lane that shares it (broadcast loads), so a document
@@ -36,72 +35,6 @@ namespace rw {
 constexpr uint32_t NOPOS = KW_NOPOS;
 // the run's counters (device, 64-bit words)
 enum { T_VALID = 0, T_ENTRIES = 1, T_INVALID = 2, T_BADPAT = 3, T_BYTES = 4, T_ROWS = 5, T_WORDS = 8 };
-
-// exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
-__device__ __forceinline__ unsigned long long block_scan(unsigned long long x, unsigned long long *ws,
-                                                         unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    __syncthreads();   // ws free again
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (int k = 0; k < BLOCK / 64; ++k) {
-        const unsigned long long s = ws[k];
-        if (k < wv) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - x;
-}
-
-// ---- exclusive scan of m 64-bit values in place, in two levels: chunk c = values [c * per, (c + 1) * per)
-__global__ __launch_bounds__(BLOCK) void rw_scan_sums_kernel(const unsigned long long *__restrict__ a, int64_t m,
-                                                             int64_t per, unsigned long long *__restrict__ chunk)
-{
-    __shared__ unsigned long long ws[BLOCK / 64];
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
-    unsigned long long s = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) s += a[i];
-    unsigned long long total;
-    (void)block_scan(s, ws, &total);
-    if (threadIdx.x == 0) chunk[blockIdx.x] = total;
-}
-
-// one block: the chunk sums' exclusive scan in place (nchunk <= SCAN_CHUNKS = 2 * BLOCK), the grand total
-__global__ __launch_bounds__(BLOCK) void rw_scan_chunks_kernel(unsigned long long *__restrict__ chunk, int nchunk,
-                                                               unsigned long long *__restrict__ grand)
-{
-    __shared__ unsigned long long ws[BLOCK / 64];
-    const int i0 = 2 * (int)threadIdx.x, i1 = i0 + 1;
-    const unsigned long long x0 = i0 < nchunk ? chunk[i0] : 0ull, x1 = i1 < nchunk ? chunk[i1] : 0ull;
-    unsigned long long total;
-    const unsigned long long before = block_scan(x0 + x1, ws, &total);
-    if (i0 < nchunk) chunk[i0] = before;
-    if (i1 < nchunk) chunk[i1] = before + x0;
-    if (threadIdx.x == 0) *grand = total;
-}
-
-__global__ __launch_bounds__(BLOCK) void rw_scan_apply_kernel(unsigned long long *__restrict__ a, int64_t m, int64_t per,
-                                                              const unsigned long long *__restrict__ chunk)
-{
-    __shared__ unsigned long long ws[BLOCK / 64];
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
-    unsigned long long carry = chunk[blockIdx.x];
-    for (int64_t i0 = lo; i0 < hi; i0 += BLOCK) {   // (block-uniform trip count)
-        const int64_t i = i0 + threadIdx.x;
-        const unsigned long long x = i < hi ? a[i] : 0ull;
-        unsigned long long total;
-        const unsigned long long before = block_scan(x, ws, &total);
-        if (i < hi) a[i] = carry + before;
-        carry += total;
-    }
-}
 
 // ---- order
 // a record as one 16-byte word: x = doc, y = pattern, z = pos, w = field (kw_hit)
@@ -349,36 +282,6 @@ __global__ __launch_bounds__(BLOCK) void rw_fill_kernel(const uint4 *__restrict_
     if (j + 1 == n_ent) out_off[2 * tot[T_ROWS]] = (int64_t)(w - out);
 }
 
-// a buffer of at least `bytes` (contents are not kept when it grows)
-int ensure(kw_rows *h, Buf &b, size_t bytes)
-{
-    if (bytes <= b.cap && b.p) return KW_OK;
-    const size_t want = std::max<size_t>(256, bytes + bytes / 4);
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    RWCHK(h, hipMalloc(&b.p, want));
-    b.cap = want;
-    return KW_OK;
-}
-
-// exclusive scan of a[0, m) in place; *d_grand (device) receives the total.  chunk: SCAN_CHUNKS words of scratch
-void scan_launch(unsigned long long *a, int64_t m, unsigned long long *chunk, unsigned long long *d_grand,
-                 hipStream_t st)
-{
-    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(SCAN_CHUNKS, (m + 4 * BLOCK - 1) / (4 * BLOCK)));
-    const int64_t per = std::max<int64_t>(1, (m + nchunk - 1) / nchunk);
-    hipLaunchKernelGGL(rw_scan_sums_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st, (const unsigned long long *)a, m,
-                       per, chunk);
-    hipLaunchKernelGGL(rw_scan_chunks_kernel, dim3(1), dim3(BLOCK), 0, st, chunk, (int)nchunk, d_grand);
-    hipLaunchKernelGGL(rw_scan_apply_kernel, dim3((unsigned)nchunk), dim3(BLOCK), 0, st, a, m, per,
-                       (const unsigned long long *)chunk);
-}
-
-static dim3 grid_of(uint64_t items) { return dim3((unsigned)std::max<uint64_t>(1, (items + BLOCK - 1) / BLOCK)); }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace rw
 
 extern "C" int kw_rows_create(int32_t device, const int64_t *occ_off, const int32_t *occ_ti, const int32_t *occ_rank,
@@ -422,17 +325,17 @@ extern "C" int kw_rows_create(int32_t device, const int64_t *occ_off, const int3
             }
         }
     }
-    RWCHK(h, hipSetDevice(device));
+    KWCHK(h, hipSetDevice(device));
     const size_t np1 = (size_t)n_patterns + 1, no = (size_t)n_occ;
     const size_t sizes[9] = {np1 * 8, no * 4, no * 4, no * 4, no * 8, no * 8, (size_t)n_patterns, (size_t)n_key, np1 * 8};
     const void *src[9] = {occ_off, occ_ti, occ_rank, prev.data(), occ_lo, occ_hi, invalid_rx, keys, key_off};
     size_t at[10];
     at[0] = 0;
     for (int k = 0; k < 9; ++k) at[k + 1] = at[k] + align256(sizes[k]);
-    RWCHK(h, hipMalloc(&h->d_tables, std::max<size_t>(256, at[9])));
+    KWCHK(h, hipMalloc(&h->d_tables, std::max<size_t>(256, at[9])));
     uint8_t *base = (uint8_t *)h->d_tables;
     for (int k = 0; k < 9; ++k)
-        if (sizes[k]) RWCHK(h, hipMemcpy(base + at[k], src[k], sizes[k], hipMemcpyHostToDevice));
+        if (sizes[k]) KWCHK(h, hipMemcpy(base + at[k], src[k], sizes[k], hipMemcpyHostToDevice));
     h->T.occ_off = (const int64_t *)(base + at[0]);
     h->T.occ_ti = (const int32_t *)(base + at[1]);
     h->T.occ_rank = (const int32_t *)(base + at[2]);
@@ -443,9 +346,9 @@ extern "C" int kw_rows_create(int32_t device, const int64_t *occ_off, const int3
     h->T.keys = base + at[7];
     h->T.key_off = (const int64_t *)(base + at[8]);
     h->T.n_patterns = (uint32_t)n_patterns;
-    RWCHK(h, hipMalloc((void **)&h->tot, T_WORDS * 8));
-    RWCHK(h, hipMalloc((void **)&h->chunk, SCAN_CHUNKS * 8));
-    for (auto &e : h->ev) RWCHK(h, hipEventCreate(&e));
+    KWCHK(h, hipMalloc((void **)&h->tot, T_WORDS * 8));
+    KWCHK(h, hipMalloc((void **)&h->chunk, SCAN_CHUNKS * 8));
+    for (auto &e : h->ev) KWCHK(h, hipEventCreate(&e));
     return KW_OK;
 }
 
@@ -478,13 +381,13 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
         h->have_run = h->run_rows = true;
         return KW_OK;
     }
-    RWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     const uint32_t nh = (uint32_t)n_hits, nd = (uint32_t)n_docs;
     int rc;
-    if ((rc = ensure(h, h->date_us, (size_t)nd * 8)) || (rc = ensure(h, h->date_ok, nd)) ||
-        (rc = ensure(h, h->doc_off, ((size_t)nd + 1) * 8)) || (rc = ensure(h, h->cursor, (size_t)nd * 4)) ||
-        (rc = ensure(h, h->tmp, (size_t)nh * 16)) || (rc = ensure(h, h->rec, (size_t)nh * 16)) ||
-        (rc = ensure(h, h->ecnt, ((size_t)nh + 1) * 8)))
+    if ((rc = fit(h, h->date_us, (size_t)nd * 8)) || (rc = fit(h, h->date_ok, nd)) ||
+        (rc = fit(h, h->doc_off, ((size_t)nd + 1) * 8)) || (rc = fit(h, h->cursor, (size_t)nd * 4)) ||
+        (rc = fit(h, h->tmp, (size_t)nh * 16)) || (rc = fit(h, h->rec, (size_t)nh * 16)) ||
+        (rc = fit(h, h->ecnt, ((size_t)nh + 1) * 8)))
         return rc;
     const uint4 *hits = (const uint4 *)d_hits;
     u64 *doc_off = (u64 *)h->doc_off.p, *ecnt = (u64 *)h->ecnt.p;
@@ -492,13 +395,13 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
     const int64_t *d_date = (const int64_t *)h->date_us.p;
     const uint8_t *d_ok = (const uint8_t *)h->date_ok.p;
 
-    RWCHK(h, hipEventRecord(h->ev[0], st));
-    RWCHK(h, hipMemcpyAsync(h->date_us.p, date_us, (size_t)nd * 8, hipMemcpyHostToDevice, st));
-    RWCHK(h, hipMemcpyAsync(h->date_ok.p, date_ok, nd, hipMemcpyHostToDevice, st));
-    RWCHK(h, hipMemsetAsync(h->tot, 0, T_WORDS * 8, st));
-    RWCHK(h, hipMemsetAsync(doc_off, 0, ((size_t)nd + 1) * 8, st));
-    RWCHK(h, hipMemsetAsync(h->cursor.p, 0, (size_t)nd * 4, st));
-    RWCHK(h, hipMemsetAsync(ecnt, 0, ((size_t)nh + 1) * 8, st));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
+    KWCHK(h, hipMemcpyAsync(h->date_us.p, date_us, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemcpyAsync(h->date_ok.p, date_ok, nd, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemsetAsync(h->tot, 0, T_WORDS * 8, st));
+    KWCHK(h, hipMemsetAsync(doc_off, 0, ((size_t)nd + 1) * 8, st));
+    KWCHK(h, hipMemsetAsync(h->cursor.p, 0, (size_t)nd * 4, st));
+    KWCHK(h, hipMemsetAsync(ecnt, 0, ((size_t)nh + 1) * 8, st));
     // order
     hipLaunchKernelGGL(rw_count_kernel, grid_of(nh), dim3(BLOCK), 0, st, hits, nh, nd, d_ok, doc_off);
     scan_launch(doc_off, (int64_t)nd + 1, h->chunk, h->tot + T_VALID, st);
@@ -506,15 +409,15 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
                        (uint32_t *)h->cursor.p, tmp);
     hipLaunchKernelGGL(rw_sort_kernel, grid_of(nh), dim3(BLOCK), 0, st, (const uint4 *)tmp, (const u64 *)h->tot,
                        (const u64 *)doc_off, rec);
-    RWCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipEventRecord(h->ev[1], st));
     // expand: count, scan, write, order
     hipLaunchKernelGGL(rw_groups_kernel<false>, grid_of(nh), dim3(BLOCK), 0, st, (const uint4 *)rec, h->tot,
                        (const u64 *)doc_off, d_date, h->T, ecnt, (uint4 *)nullptr);
     scan_launch(ecnt, (int64_t)nh + 1, h->chunk, h->tot + T_ENTRIES, st);
     u64 tot[T_WORDS];
-    RWCHK(h, hipMemcpyAsync(tot, h->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipStreamSynchronize(st));
-    RWCHK(h, hipGetLastError());
+    KWCHK(h, hipMemcpyAsync(tot, h->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     if (tot[T_BADPAT]) {
         h->err = "kw_rows_run: a record's pattern index is beyond the tables";
         return KW_EINVAL;
@@ -530,8 +433,8 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
         h->have_run = h->run_rows = true;
         return KW_OK;
     }
-    if ((rc = ensure(h, h->ent_raw, (size_t)n_ent * 32)) || (rc = ensure(h, h->ent, (size_t)n_ent * 32)) ||
-        (rc = ensure(h, h->len, (size_t)n_ent * 8)) || (rc = ensure(h, h->head, (size_t)n_ent * 8)))
+    if ((rc = fit(h, h->ent_raw, (size_t)n_ent * 32)) || (rc = fit(h, h->ent, (size_t)n_ent * 32)) ||
+        (rc = fit(h, h->len, (size_t)n_ent * 8)) || (rc = fit(h, h->head, (size_t)n_ent * 8)))
         return rc;
     uint4 *ent_raw = (uint4 *)h->ent_raw.p, *ent = (uint4 *)h->ent.p;
     u64 *len = (u64 *)h->len.p, *head = (u64 *)h->head.p;
@@ -540,25 +443,25 @@ extern "C" int kw_rows_run(kw_rows *h, const kw_hit *d_hits, int64_t n_hits, con
                        (const u64 *)doc_off, d_date, h->T, ecnt, ent_raw);
     hipLaunchKernelGGL(rw_esort_kernel, grid_of(ne), dim3(BLOCK), 0, st, (const uint4 *)ent_raw, ne, (const u64 *)doc_off,
                        (const u64 *)ecnt, ent);
-    RWCHK(h, hipEventRecord(h->ev[2], st));
+    KWCHK(h, hipEventRecord(h->ev[2], st));
     // render: size, then fill
     hipLaunchKernelGGL(rw_len_kernel, grid_of(ne), dim3(BLOCK), 0, st, (const uint4 *)ent, ne, h->T, len, head);
     scan_launch(len, (int64_t)ne, h->chunk, h->tot + T_BYTES, st);
     scan_launch(head, (int64_t)ne, h->chunk, h->tot + T_ROWS, st);
-    RWCHK(h, hipMemcpyAsync(tot, h->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-    RWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipMemcpyAsync(tot, h->tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
     const u64 nb = tot[T_BYTES], nr = tot[T_ROWS];
-    if ((rc = ensure(h, h->json, (size_t)nb)) || (rc = ensure(h, h->json_off, (size_t)(2 * nr + 1) * 8)) ||
-        (rc = ensure(h, h->row_doc, (size_t)nr * 4)) || (rc = ensure(h, h->row_ti, (size_t)nr * 4)))
+    if ((rc = fit(h, h->json, (size_t)nb)) || (rc = fit(h, h->json_off, (size_t)(2 * nr + 1) * 8)) ||
+        (rc = fit(h, h->row_doc, (size_t)nr * 4)) || (rc = fit(h, h->row_ti, (size_t)nr * 4)))
         return rc;
     hipLaunchKernelGGL(rw_fill_kernel, grid_of(ne), dim3(BLOCK), 0, st, (const uint4 *)ent, ne, (const uint4 *)rec, h->T,
                        (const u64 *)len, (const u64 *)head, (const u64 *)h->tot, (uint8_t *)h->json.p,
                        (int64_t *)h->json_off.p, (int32_t *)h->row_doc.p, (int32_t *)h->row_ti.p);
-    RWCHK(h, hipEventRecord(h->ev[3], st));
-    RWCHK(h, hipStreamSynchronize(st));
-    RWCHK(h, hipGetLastError());
-    for (int k = 0; k < 3; ++k) RWCHK(h, hipEventElapsedTime(&h->ms[k], h->ev[k], h->ev[k + 1]));
-    RWCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[3]));
+    KWCHK(h, hipEventRecord(h->ev[3], st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    for (int k = 0; k < 3; ++k) KWCHK(h, hipEventElapsedTime(&h->ms[k], h->ev[k], h->ev[k + 1]));
+    KWCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[3]));
     h->n_rows = *n_rows = (int64_t)nr;
     h->n_bytes = *n_bytes = (int64_t)nb;
     h->have_run = h->run_rows = true;
@@ -577,11 +480,11 @@ extern "C" int kw_rows_copy(kw_rows *h, int32_t *row_doc, int32_t *row_ti, uint8
         json_off[0] = 0;
         return KW_OK;
     }
-    RWCHK(h, hipSetDevice(h->device));
-    RWCHK(h, hipMemcpy(row_doc, h->row_doc.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
-    RWCHK(h, hipMemcpy(row_ti, h->row_ti.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
-    RWCHK(h, hipMemcpy(json, h->json.p, (size_t)h->n_bytes, hipMemcpyDeviceToHost));
-    RWCHK(h, hipMemcpy(json_off, h->json_off.p, (size_t)(2 * h->n_rows + 1) * 8, hipMemcpyDeviceToHost));
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipMemcpy(row_doc, h->row_doc.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
+    KWCHK(h, hipMemcpy(row_ti, h->row_ti.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost));
+    KWCHK(h, hipMemcpy(json, h->json.p, (size_t)h->n_bytes, hipMemcpyDeviceToHost));
+    KWCHK(h, hipMemcpy(json_off, h->json_off.p, (size_t)(2 * h->n_rows + 1) * 8, hipMemcpyDeviceToHost));
     return KW_OK;
 }
 

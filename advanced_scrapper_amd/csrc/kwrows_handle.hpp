@@ -4,12 +4,16 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 
 #include "../../include/kwrows.h"
+#include "kwhandle.hpp"
 
 namespace rw {
+
+using namespace kwh;   // Buf, ensure, scan_launch, SCAN_CHUNKS, ...
 
 struct Tables {
     const int64_t *occ_off;
@@ -19,11 +23,6 @@ struct Tables {
     const uint8_t *keys;
     const int64_t *key_off;
     uint32_t n_patterns;
-};
-
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
 };
 
 struct Emit;   // kwemit.hip: the state of kw_rows_cells / kw_rows_emit
@@ -48,25 +47,14 @@ struct kw_rows {
     rw::Emit *emit = nullptr;
 };
 
-#define RWCHK(h, x)                                                                    \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            (h)->err = std::string("HIP error ") + hipGetErrorString(e_) + " at " #x; \
-            return KW_EHIP;                                                            \
-        }                                                                              \
-    } while (0)
-
 namespace rw {
 
 constexpr int BLOCK = 256;
-constexpr int SCAN_CHUNKS = 512;
 
 // a buffer of at least `bytes` (contents are not kept when it grows)
-int ensure(kw_rows *h, Buf &b, size_t bytes);
-// exclusive scan of a[0, m) in place; *d_grand (device) receives the total.  chunk: SCAN_CHUNKS words of scratch
-void scan_launch(unsigned long long *a, int64_t m, unsigned long long *chunk, unsigned long long *d_grand,
-                 hipStream_t st);
+inline int fit(kw_rows *h, Buf &b, size_t bytes) { return ensure(h, b, bytes, std::max<size_t>(256, bytes + bytes / 4)); }
+// the blocks for `items` lanes
+inline dim3 grid_of(uint64_t items) { return grid_for((long long)items, BLOCK, INT64_MAX); }
 // kwemit.hip: frees what kw_rows_cells / kw_rows_emit allocated
 void emit_destroy(kw_rows *h);
 

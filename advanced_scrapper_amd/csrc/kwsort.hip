@@ -42,14 +42,15 @@
 #include <string>
 
 #include "../../include/kwsort.h"
-#include "kwenv.hpp"
+#include "kwdev.hpp"
+#include "kwhandle.hpp"
 
 namespace ks {
 
+using namespace kwd;   // BLOCK, NONE and the primitives
+using namespace kwh;
 typedef unsigned long long u64;
-constexpr int BLOCK = 256;
 constexpr int MAX_GRID = 2048;
-constexpr u64 NONE = ~0ull;
 constexpr uint32_t F_QUOTED = 1u, F_NA = 2u, F_TEXT = 4u, F_CANON = 8u;   // KWCSV_* (csrc/kwcsv.c)
 constexpr int COL_BITS = 12;                                              // ncols <= 4096 (kw_ingest_create)
 
@@ -61,21 +62,6 @@ struct Dev {
     int not_asc, bad_order;
     u64 first_len, first_term;                // the index route: the first row of a bad length, of a missing '\n' (NONE)
 };
-
-__device__ __forceinline__ u64 wave_min(u64 x)
-{
-    for (int d = 32; d >= 1; d >>= 1) {
-        const u64 y = __shfl_xor(x, d, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 x)
-{
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
 
 // The int64 a cell of the canonical decimal form `0` or `-?[1-9][0-9]*` holds; false for any other cell.
 __device__ __forceinline__ bool parse_key(const uint8_t *__restrict__ s, long long len, long long *key)
@@ -163,28 +149,6 @@ __global__ __launch_bounds__(BLOCK) void ks_check_kernel(const long long *__rest
         if (keys[r] <= keys[r - 1] && !D->not_asc) D->not_asc = 1;
     for (long long i = t; i < nbc; i += step)
         if ((int)(i % ncols) != ti && !btext[i] && bnonna[i]) atomicMin(&D->first_dtype, (u64)i);
-}
-
-// exclusive scan of one value a thread over the block; *total: the block's sum (ws: BLOCK / 64 words of LDS)
-__device__ __forceinline__ u64 block_scan(u64 x, u64 *ws, u64 *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    __syncthreads();   // ws free again
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (int k = 0; k < BLOCK / 64; ++k) {
-        const u64 s = ws[k];
-        if (k < wv) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - x;
 }
 
 // A tile = BLOCK order entries: each one's range check and its record's bytes + 1, scanned inside the tile into
@@ -424,10 +388,6 @@ __global__ __launch_bounds__(BLOCK) void ks_copy_kernel(const uint8_t *__restric
     }
 }
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
 
 }  // namespace ks
 
@@ -471,95 +431,30 @@ struct kw_sort {
     hipEvent_t wev[2][2] = {};
 };
 
-#define KSCHK(h, x)                                                                    \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            (h)->err = std::string("HIP error ") + hipGetErrorString(e_) + " at " #x; \
-            return KW_EHIP;                                                            \
-        }                                                                              \
-    } while (0)
 
 namespace ks {
 
 // a device buffer of at least `bytes` (contents are not kept when it grows)
-static int ensure(kw_sort *h, Buf &b, size_t bytes)
-{
-    if (b.cap >= bytes && b.p) return KW_OK;
-    const size_t want = bytes + bytes / 4 + 256;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    KSCHK(h, hipMalloc(&b.p, want));
-    b.cap = want;
-    return KW_OK;
-}
+static int fit(kw_sort *h, Buf &b, size_t bytes) { return ensure(h, b, bytes, bytes + bytes / 4 + 256); }
 
 // a device buffer of at least `bytes` that keeps its first `keep` bytes when it grows (to twice the bytes asked
 // for: a file's windows ask for a little more each); what a grown buffer holds beyond them is zero
-static int ensure_keep(kw_sort *h, Buf &b, size_t bytes, size_t keep, hipStream_t st)
+static int fit_keep(kw_sort *h, Buf &b, size_t bytes, size_t keep, hipStream_t st)
 {
-    if (b.cap >= bytes && b.p) return KW_OK;
-    const size_t want = 2 * bytes + 256;
-    void *p = nullptr;
-    KSCHK(h, hipMalloc(&p, want));
-    if (keep > b.cap) keep = b.cap;
-    hipError_t e = hipSuccess;
-    if (b.p && keep) e = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)p + keep, 0, want - keep, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        KSCHK(h, e);
-    }
-    if (b.p) (void)hipFree(b.p);
-    b.p = p;
-    b.cap = want;
-    return KW_OK;
+    return ensure_keep(h, b, bytes, keep, 2 * bytes + 256, true, st);
 }
 
-static int ensure_pinned(kw_sort *h, void **p, size_t *cap, size_t bytes)
+static int fit_pinned(kw_sort *h, void **p, size_t *cap, size_t bytes)
 {
-    if (*cap >= bytes && *p) return KW_OK;
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    KSCHK(h, hipHostMalloc(p, want, hipHostMallocDefault));
-    *cap = want;
-    return KW_OK;
+    return ensure_pinned(h, p, cap, bytes, bytes + bytes / 4 + 4096);
 }
 
 // The cap on every launch grid of a call: MAX_GRID, or the tests' KW_TEST_SORT_GRID in [1, MAX_GRID] (read per
-// call through kw_env: the kernels' loops then make several trips on a small file).
-static int grid_cap()
-{
-    if (const char *e = kw_env("KW_TEST_SORT_GRID")) {
-        char *end = nullptr;
-        const long g = strtol(e, &end, 10);
-        if (end != e && *end == '\0' && g >= 1 && g <= MAX_GRID) return (int)g;
-    }
-    return MAX_GRID;
-}
+// call: the kernels' loops then make several trips on a small file).
+static int grid_cap() { return (int)env_int("KW_TEST_SORT_GRID", 1, MAX_GRID, MAX_GRID); }
 
-// The most bytes a store may hold: the tests' KW_TEST_SORT_STORE_MAX (through kw_env), else no cap of its own.
-static long long store_cap()
-{
-    if (const char *e = kw_env("KW_TEST_SORT_STORE_MAX")) {
-        char *end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end != e && *end == '\0' && v >= 0) return v;
-    }
-    return INT64_MAX;
-}
-
-static dim3 grid_for(long long items, int cap)
-{
-    long long g = (items + BLOCK - 1) / BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return dim3((unsigned)g);
-}
+// The most bytes a store may hold: the tests' KW_TEST_SORT_STORE_MAX, else no cap of its own.
+static long long store_cap() { return env_int("KW_TEST_SORT_STORE_MAX", 0, INT64_MAX, INT64_MAX); }
 
 }  // namespace ks
 
@@ -621,19 +516,19 @@ static int reset_state(kw_sort *h, hipStream_t st)
     memset(&init, 0, sizeof(init));
     init.first_key = init.first_form = init.first_dtype = init.first_len = init.first_term = NONE;
     *h->H = init;   // (pinned: the copy below reads it in stream order; the last call's copy back has finished)
-    KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
     return KW_OK;
 }
 
 // after ev[1]: the n keys and the state to the host; the copies' time to ms_keys_copy
 static int fetch_state(kw_sort *h, long long n, hipStream_t st)
 {
-    KSCHK(h, hipMemcpyAsync(h->h_keys, h->keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipEventRecord(h->ev[2], st));
-    KSCHK(h, hipStreamSynchronize(st));
-    KSCHK(h, hipGetLastError());
-    KSCHK(h, hipEventElapsedTime(&h->ms_keys_copy, h->ev[1], h->ev[2]));
+    KWCHK(h, hipMemcpyAsync(h->h_keys, h->keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipEventRecord(h->ev[2], st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventElapsedTime(&h->ms_keys_copy, h->ev[1], h->ev[2]));
     return KW_OK;
 }
 
@@ -678,8 +573,8 @@ extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t
     *verdict = KW_SORT_OK;
     *bad_col = *ascending = 0;
     hipStream_t st = (hipStream_t)stream;
-    KSCHK(h, hipSetDevice(h->device));
-    KSCHK(h, hipEventRecord(h->ev[0], st));
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
     const int64_t *rs, *re, *coff;
     const uint8_t *text, *cells, *cfl;
     int64_t n, n_bytes, cell_bytes;
@@ -695,24 +590,24 @@ extern "C" int kw_sort_keys(kw_sort *h, kw_ingest *ig, int32_t time_col, int64_t
     }
     const long long nblk = (n + block_rows - 1) / block_rows, nbc = nblk * ncols;
     int rc;
-    if ((rc = ensure(h, h->keys, (size_t)n * 8)) || (rc = ensure(h, h->btext, (size_t)nbc)) ||
-        (rc = ensure(h, h->bnonna, (size_t)nbc)) || (rc = ensure_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8)))
+    if ((rc = fit(h, h->keys, (size_t)n * 8)) || (rc = fit(h, h->btext, (size_t)nbc)) ||
+        (rc = fit(h, h->bnonna, (size_t)nbc)) || (rc = fit_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8)))
         return rc;
     uint8_t *btext = (uint8_t *)h->btext.p, *bnonna = (uint8_t *)h->bnonna.p;
     const int gcap = grid_cap();
     if ((rc = reset_state(h, st))) return rc;
-    KSCHK(h, hipMemsetAsync(btext, 0, (size_t)nbc, st));
-    KSCHK(h, hipMemsetAsync(bnonna, 0, (size_t)nbc, st));
-    hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
+    KWCHK(h, hipMemsetAsync(btext, 0, (size_t)nbc, st));
+    KWCHK(h, hipMemsetAsync(bnonna, 0, (size_t)nbc, st));
+    hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, BLOCK, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
                        (const long long *)rs, (const long long *)re, (long long)n, (int)ncols, (int)time_col,
                        (long long)block_rows, (long long *)h->keys.p, btext, bnonna, h->D, 0ll, 0ll,
                        (long long *)nullptr, (long long *)nullptr);
-    hipLaunchKernelGGL(ks_check_kernel, grid_for(n > nbc ? n : nbc, gcap), dim3(BLOCK), 0, st,
+    hipLaunchKernelGGL(ks_check_kernel, grid_for(n > nbc ? n : nbc, BLOCK, gcap), dim3(BLOCK), 0, st,
                        (const long long *)h->keys.p, 1ll, (long long)n, (const uint8_t *)btext, (const uint8_t *)bnonna,
                        nbc, (int)ncols, (int)time_col, h->D);
-    KSCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipEventRecord(h->ev[1], st));
     if ((rc = fetch_state(h, n, st))) return rc;
-    KSCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[0], h->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[0], h->ev[1]));
     h->ms[1] = h->ms[2] = 0;
     h->ms[3] = h->ms_keys_copy;
     *n_rows = n;
@@ -742,7 +637,7 @@ static int reserve_store(kw_sort *h, int64_t expect_bytes, const char *who)
         // and its offset, 40 bytes, at the 160 bytes and more of a per-ticker file's record -- and a margin for
         // the slabs; a store that is replaced gives its own bytes back first
         size_t free_b = 0, total_b = 0;
-        KSCHK(h, hipMemGetInfo(&free_b, &total_b));
+        KWCHK(h, hipMemGetInfo(&free_b, &total_b));
         const size_t need = want + want / 4 + ((size_t)64 << 20);
         if (need > free_b + h->store.cap) {
             h->err = std::string(who) + ": a store of " + std::to_string(expect_bytes) + " bytes does not fit in the " +
@@ -771,7 +666,7 @@ extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, i
         h->err = "kw_sort_begin: bad arguments";
         return KW_EINVAL;
     }
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
     if ((rc = reserve_store(h, expect_bytes, "kw_sort_begin"))) return rc;
     h->time_col = time_col;
@@ -781,7 +676,7 @@ extern "C" int kw_sort_begin(kw_sort *h, int32_t time_col, int64_t block_rows, i
     h->ncols = 0;
     h->ms[0] = h->ms[1] = h->ms[2] = h->ms[3] = h->ms_keys_copy = 0;
     if ((rc = reset_state(h, nullptr))) return rc;
-    KSCHK(h, hipStreamSynchronize(nullptr));
+    KWCHK(h, hipStreamSynchronize(nullptr));
     h->open = true;
     return KW_OK;
 }
@@ -795,7 +690,7 @@ extern "C" int kw_sort_window(kw_sort *h, kw_ingest *ig, int64_t consumed, void 
     }
     h->open = false;   // (an error below ends the file)
     hipStream_t st = (hipStream_t)stream;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     const int64_t *rs, *re, *coff;
     const uint8_t *text, *cells, *cfl;
     int64_t n, n_bytes, cell_bytes;
@@ -819,36 +714,36 @@ extern "C" int kw_sort_window(kw_sort *h, kw_ingest *ig, int64_t consumed, void 
     const long long nbc = ((rows + h->block_rows - 1) / h->block_rows) * ncols;
     const long long nbc0 = ((base + h->block_rows - 1) / h->block_rows) * ncols;
     int rc;
-    if ((rc = ensure_keep(h, h->keys, (size_t)rows * 8, (size_t)base * 8, st)) ||
-        (rc = ensure_keep(h, h->srs, (size_t)rows * 8, (size_t)base * 8, st)) ||
-        (rc = ensure_keep(h, h->sre, (size_t)rows * 8, (size_t)base * 8, st)) ||
-        (rc = ensure_keep(h, h->btext, (size_t)nbc, (size_t)nbc0, st)) ||
-        (rc = ensure_keep(h, h->bnonna, (size_t)nbc, (size_t)nbc0, st)))
+    if ((rc = fit_keep(h, h->keys, (size_t)rows * 8, (size_t)base * 8, st)) ||
+        (rc = fit_keep(h, h->srs, (size_t)rows * 8, (size_t)base * 8, st)) ||
+        (rc = fit_keep(h, h->sre, (size_t)rows * 8, (size_t)base * 8, st)) ||
+        (rc = fit_keep(h, h->btext, (size_t)nbc, (size_t)nbc0, st)) ||
+        (rc = fit_keep(h, h->bnonna, (size_t)nbc, (size_t)nbc0, st)))
         return rc;
     uint8_t *btext = (uint8_t *)h->btext.p, *bnonna = (uint8_t *)h->bnonna.p;
     const int gcap = grid_cap();
-    KSCHK(h, hipEventRecord(h->ev[0], st));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
     // (the witnesses of the blocks this window opens: a buffer that did not grow holds an earlier file's)
     if (nbc > nbc0) {
-        KSCHK(h, hipMemsetAsync(btext + nbc0, 0, (size_t)(nbc - nbc0), st));
-        KSCHK(h, hipMemsetAsync(bnonna + nbc0, 0, (size_t)(nbc - nbc0), st));
+        KWCHK(h, hipMemsetAsync(btext + nbc0, 0, (size_t)(nbc - nbc0), st));
+        KWCHK(h, hipMemsetAsync(bnonna + nbc0, 0, (size_t)(nbc - nbc0), st));
     }
-    hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
+    hipLaunchKernelGGL(ks_rows_kernel, grid_for(n, BLOCK, gcap), dim3(BLOCK), 0, st, cells, (const long long *)coff, cfl,
                        (const long long *)rs, (const long long *)re, (long long)n, (int)ncols, h->time_col, h->block_rows,
                        (long long *)h->keys.p, btext, bnonna, h->D, base, h->used, (long long *)h->srs.p,
                        (long long *)h->sre.p);
     // (the first row of a later window against the last row of the window before)
-    hipLaunchKernelGGL(ks_check_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, (const long long *)h->keys.p,
+    hipLaunchKernelGGL(ks_check_kernel, grid_for(n, BLOCK, gcap), dim3(BLOCK), 0, st, (const long long *)h->keys.p,
                        base > 0 ? base : 1ll, rows, (const uint8_t *)btext, (const uint8_t *)bnonna, 0ll, (int)ncols,
                        h->time_col, h->D);
-    KSCHK(h, hipEventRecord(h->ev[1], st));
-    KSCHK(h, hipMemcpyAsync((uint8_t *)h->store.p + h->used, text, (size_t)consumed, hipMemcpyDeviceToDevice, st));
-    KSCHK(h, hipEventRecord(h->ev[2], st));
-    KSCHK(h, hipStreamSynchronize(st));
-    KSCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipMemcpyAsync((uint8_t *)h->store.p + h->used, text, (size_t)consumed, hipMemcpyDeviceToDevice, st));
+    KWCHK(h, hipEventRecord(h->ev[2], st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     float a = 0, b = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-    KSCHK(h, hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    KWCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
     h->ms[0] += a;
     h->ms[3] += b;
     h->ms_keys_copy = h->ms[3];
@@ -878,18 +773,18 @@ extern "C" int kw_sort_finish(kw_sort *h, const int64_t **keys, int64_t *n_rows,
     *verdict = KW_SORT_OK;
     *bad_col = *ascending = 0;
     hipStream_t st = h->stream;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     const long long n = h->rows, nbc = ((n + h->block_rows - 1) / h->block_rows) * h->ncols;
     int rc;
-    if ((rc = ensure_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8))) return rc;
-    KSCHK(h, hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(ks_check_kernel, grid_for(nbc, grid_cap()), dim3(BLOCK), 0, st, (const long long *)h->keys.p, 1ll,
+    if ((rc = fit_pinned(h, &h->h_keys, &h->h_keys_cap, (size_t)n * 8))) return rc;
+    KWCHK(h, hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(ks_check_kernel, grid_for(nbc, BLOCK, grid_cap()), dim3(BLOCK), 0, st, (const long long *)h->keys.p, 1ll,
                        0ll, (const uint8_t *)h->btext.p, (const uint8_t *)h->bnonna.p, nbc, h->ncols, h->time_col, h->D);
-    KSCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipEventRecord(h->ev[1], st));
     const float copies = h->ms[3];
     if ((rc = fetch_state(h, n, st))) return rc;
     float a = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
     h->ms[0] += a;
     h->ms[3] = h->ms_keys_copy = copies + h->ms_keys_copy;
     *n_rows = n;
@@ -909,9 +804,9 @@ static int settle_slot(kw_sort *h, int slot)
 {
     if (!h->busy[slot]) return KW_OK;
     h->busy[slot] = false;
-    KSCHK(h, hipEventSynchronize(h->wev[slot][1]));
+    KWCHK(h, hipEventSynchronize(h->wev[slot][1]));
     float a = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->wev[slot][0], h->wev[slot][1]));
+    KWCHK(h, hipEventElapsedTime(&a, h->wev[slot][0], h->wev[slot][1]));
     h->ms[3] += a;
     return KW_OK;
 }
@@ -925,35 +820,35 @@ extern "C" int kw_sort_index_begin(kw_sort *h, const int64_t *lens, int64_t n_ro
         return KW_EINVAL;
     }
     *bad_row = -1;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
     // (a slot whose copy into the last file's store is still under way: the store may be replaced below)
     if ((rc = settle_slot(h, 0)) || (rc = settle_slot(h, 1))) return rc;
     if ((rc = reserve_store(h, body_bytes, "kw_sort_index_begin"))) return rc;
     const long long ntiles = (n_rows + BLOCK - 1) / BLOCK;
-    if ((rc = ensure(h, h->keys, (size_t)n_rows * 8)) || (rc = ensure(h, h->srs, (size_t)n_rows * 8)) ||
-        (rc = ensure(h, h->sre, (size_t)n_rows * 8)) || (rc = ensure(h, h->tsum, (size_t)ntiles * 8)))
+    if ((rc = fit(h, h->keys, (size_t)n_rows * 8)) || (rc = fit(h, h->srs, (size_t)n_rows * 8)) ||
+        (rc = fit(h, h->sre, (size_t)n_rows * 8)) || (rc = fit(h, h->tsum, (size_t)ntiles * 8)))
         return rc;
     h->ms[0] = h->ms[1] = h->ms[2] = h->ms[3] = h->ms_keys_copy = 0;
     hipStream_t st = nullptr;
     const int gcap = grid_cap();
     const long long *d_lens = (const long long *)h->keys.p;
-    KSCHK(h, hipEventRecord(h->ev[0], st));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
     if ((rc = reset_state(h, st))) return rc;
-    KSCHK(h, hipMemcpyAsync(h->keys.p, lens, (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
-    KSCHK(h, hipEventRecord(h->ev[1], st));
-    hipLaunchKernelGGL(ks_span_kernel, grid_for(n_rows, gcap), dim3(BLOCK), 0, st, d_lens, (long long)n_rows,
+    KWCHK(h, hipMemcpyAsync(h->keys.p, lens, (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipEventRecord(h->ev[1], st));
+    hipLaunchKernelGGL(ks_span_kernel, grid_for(n_rows, BLOCK, gcap), dim3(BLOCK), 0, st, d_lens, (long long)n_rows,
                        (long long)body_bytes, (long long *)h->srs.p, (u64 *)h->tsum.p, h->D);
     hipLaunchKernelGGL(ks_scan_kernel, dim3(1), dim3(BLOCK), 0, st, (u64 *)h->tsum.p, ntiles, &h->D->total);
-    hipLaunchKernelGGL(ks_span_add_kernel, grid_for(n_rows, gcap), dim3(BLOCK), 0, st, d_lens, (long long)n_rows,
+    hipLaunchKernelGGL(ks_span_add_kernel, grid_for(n_rows, BLOCK, gcap), dim3(BLOCK), 0, st, d_lens, (long long)n_rows,
                        (long long)body_bytes, (long long *)h->srs.p, (long long *)h->sre.p, (const u64 *)h->tsum.p,
                        h->D);
-    KSCHK(h, hipEventRecord(h->ev[2], st));
-    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipStreamSynchronize(st));
-    KSCHK(h, hipGetLastError());
-    KSCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[1]));
-    KSCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[1], h->ev[2]));
+    KWCHK(h, hipEventRecord(h->ev[2], st));
+    KWCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
+    KWCHK(h, hipEventElapsedTime(&h->ms[3], h->ev[0], h->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&h->ms[0], h->ev[1], h->ev[2]));
     const Dev &R = *h->H;
     if (R.first_len != NONE || R.total != (u64)body_bytes) {
         // (with no offender every length was counted and every record ends inside the body: the sum is short)
@@ -980,9 +875,9 @@ extern "C" int kw_sort_index_stage(kw_sort *h, int32_t slot, int64_t n_bytes, ui
         return KW_EINVAL;
     }
     *host = nullptr;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = settle_slot(h, slot)) || (rc = ensure_pinned(h, &h->h_stage[slot], &h->h_stage_cap[slot], (size_t)n_bytes)))
+    if ((rc = settle_slot(h, slot)) || (rc = fit_pinned(h, &h->h_stage[slot], &h->h_stage_cap[slot], (size_t)n_bytes)))
         return rc;
     *host = (uint8_t *)h->h_stage[slot];
     return KW_OK;
@@ -1006,12 +901,12 @@ extern "C" int kw_sort_index_window(kw_sort *h, int32_t slot, int64_t n_bytes, v
         return KW_EOVERFLOW;
     }
     hipStream_t st = (hipStream_t)stream;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     int rc;
     if ((rc = settle_slot(h, slot))) return rc;
-    KSCHK(h, hipEventRecord(h->wev[slot][0], st));
-    KSCHK(h, hipMemcpyAsync((uint8_t *)h->store.p + h->used, h->h_stage[slot], (size_t)n_bytes, hipMemcpyHostToDevice, st));
-    KSCHK(h, hipEventRecord(h->wev[slot][1], st));
+    KWCHK(h, hipEventRecord(h->wev[slot][0], st));
+    KWCHK(h, hipMemcpyAsync((uint8_t *)h->store.p + h->used, h->h_stage[slot], (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipEventRecord(h->wev[slot][1], st));
     h->busy[slot] = true;
     h->used += n_bytes;
     h->stream = st;
@@ -1037,18 +932,18 @@ extern "C" int kw_sort_index_finish(kw_sort *h, int32_t *verdict, int64_t *bad_r
     *verdict = KW_INDEX_OK;
     *bad_row = -1;
     hipStream_t st = h->stream;
-    KSCHK(h, hipSetDevice(h->device));
-    KSCHK(h, hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(ks_term_kernel, grid_for(h->rows, grid_cap()), dim3(BLOCK), 0, st, (const uint8_t *)h->store.p,
+    KWCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(ks_term_kernel, grid_for(h->rows, BLOCK, grid_cap()), dim3(BLOCK), 0, st, (const uint8_t *)h->store.p,
                        (const long long *)h->sre.p, h->rows, h->D);
-    KSCHK(h, hipEventRecord(h->ev[1], st));
-    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipStreamSynchronize(st));
-    KSCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(h->ev[1], st));
+    KWCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     int rc;
     if ((rc = settle_slot(h, 0)) || (rc = settle_slot(h, 1))) return rc;
     float a = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    KWCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
     h->ms[0] += a;
     h->ms_keys_copy = h->ms[3];
     if (h->H->first_term != NONE) {
@@ -1072,34 +967,34 @@ static int gather_scan(kw_sort *h, const int64_t *order, int64_t n, u64 *total)
     h->scanned = false;
     int rc;
     const long long ntiles = (n + BLOCK - 1) / BLOCK;
-    if ((rc = ensure(h, h->order, (size_t)n * 8)) || (rc = ensure(h, h->doff, (size_t)(n + 1) * 8)) ||
-        (rc = ensure(h, h->tsum, (size_t)ntiles * 8)))
+    if ((rc = fit(h, h->order, (size_t)n * 8)) || (rc = fit(h, h->doff, (size_t)(n + 1) * 8)) ||
+        (rc = fit(h, h->tsum, (size_t)ntiles * 8)))
         return rc;
     const int gcap = grid_cap();
     h->H->total = 0;
     h->H->bad_order = 0;
-    KSCHK(h, hipEventRecord(h->ev[3], st));
-    KSCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
-    KSCHK(h, hipMemcpyAsync(h->order.p, order, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    KSCHK(h, hipEventRecord(h->ev[4], st));
-    hipLaunchKernelGGL(ks_len_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, (const long long *)h->order.p, (long long)n,
+    KWCHK(h, hipEventRecord(h->ev[3], st));
+    KWCHK(h, hipMemcpyAsync(h->D, h->H, sizeof(Dev), hipMemcpyHostToDevice, st));
+    KWCHK(h, hipMemcpyAsync(h->order.p, order, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    KWCHK(h, hipEventRecord(h->ev[4], st));
+    hipLaunchKernelGGL(ks_len_kernel, grid_for(n, BLOCK, gcap), dim3(BLOCK), 0, st, (const long long *)h->order.p, (long long)n,
                        h->n_rows, (const long long *)h->rs, (const long long *)h->re, (u64 *)h->doff.p, (u64 *)h->tsum.p,
                        h->D);
     hipLaunchKernelGGL(ks_scan_kernel, dim3(1), dim3(BLOCK), 0, st, (u64 *)h->tsum.p, ntiles, &h->D->total);
-    hipLaunchKernelGGL(ks_add_kernel, grid_for(n, gcap), dim3(BLOCK), 0, st, (u64 *)h->doff.p, (long long)n,
+    hipLaunchKernelGGL(ks_add_kernel, grid_for(n, BLOCK, gcap), dim3(BLOCK), 0, st, (u64 *)h->doff.p, (long long)n,
                        (const u64 *)h->tsum.p, (const u64 *)&h->D->total);
-    KSCHK(h, hipEventRecord(h->ev[5], st));
-    KSCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipStreamSynchronize(st));
-    KSCHK(h, hipGetLastError());
+    KWCHK(h, hipEventRecord(h->ev[5], st));
+    KWCHK(h, hipMemcpyAsync(h->H, h->D, sizeof(Dev), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipStreamSynchronize(st));
+    KWCHK(h, hipGetLastError());
     if (h->H->bad_order) {
         h->err = "kw_sort_gather: an order entry outside [0, n_rows)";
         return KW_EINVAL;
     }
     *total = h->H->total;
     float a = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->ev[3], h->ev[4]));
-    KSCHK(h, hipEventElapsedTime(&h->ms[1], h->ev[4], h->ev[5]));
+    KWCHK(h, hipEventElapsedTime(&a, h->ev[3], h->ev[4]));
+    KWCHK(h, hipEventElapsedTime(&h->ms[1], h->ev[4], h->ev[5]));
     h->ms[2] = 0;
     h->ms[3] = h->ms_keys_copy + a;
     return KW_OK;
@@ -1111,18 +1006,18 @@ static int gather_range(kw_sort *h, long long n, u64 x_lo, u64 x_hi, void *d_out
 {
     hipStream_t st = h->stream;
     const int gcap = grid_cap();
-    KSCHK(h, hipEventRecord(h->ev[6], st));
+    KWCHK(h, hipEventRecord(h->ev[6], st));
     // the KiB a wave lays out: one while the range gives every wave of a full grid something to do, up to 16 beyond
     const long long kib = (long long)((x_hi - x_lo + 1023) >> 10), waves = (long long)gcap * (BLOCK / 64);
     long long iters = (kib + waves - 1) / waves;
     iters = iters < 1 ? 1 : (iters > 16 ? 16 : iters);
     const long long spans = (kib + iters - 1) / iters;
-    hipLaunchKernelGGL(ks_copy_kernel, grid_for(spans * 64, gcap), dim3(BLOCK), 0, st, h->text,
+    hipLaunchKernelGGL(ks_copy_kernel, grid_for(spans * 64, BLOCK, gcap), dim3(BLOCK), 0, st, h->text,
                        (const long long *)h->rs, (const long long *)h->order.p, (const u64 *)h->doff.p, n,
                        (uint8_t *)d_out, (int)iters, x_lo, x_hi);
-    KSCHK(h, hipEventRecord(h->ev[7], st));
-    KSCHK(h, hipMemcpyAsync(h_out, d_out, (size_t)(x_hi - x_lo), hipMemcpyDeviceToHost, st));
-    KSCHK(h, hipEventRecord(h->ev[8], st));
+    KWCHK(h, hipEventRecord(h->ev[7], st));
+    KWCHK(h, hipMemcpyAsync(h_out, d_out, (size_t)(x_hi - x_lo), hipMemcpyDeviceToHost, st));
+    KWCHK(h, hipEventRecord(h->ev[8], st));
     return KW_OK;
 }
 
@@ -1130,8 +1025,8 @@ static int gather_range(kw_sort *h, long long n, u64 x_lo, u64 x_hi, void *d_out
 static int gather_times(kw_sort *h)
 {
     float a = 0, b = 0;
-    KSCHK(h, hipEventElapsedTime(&a, h->ev[6], h->ev[7]));
-    KSCHK(h, hipEventElapsedTime(&b, h->ev[7], h->ev[8]));
+    KWCHK(h, hipEventElapsedTime(&a, h->ev[6], h->ev[7]));
+    KWCHK(h, hipEventElapsedTime(&b, h->ev[7], h->ev[8]));
     h->ms[2] += a;
     h->ms[3] += b;
     return KW_OK;
@@ -1150,7 +1045,7 @@ extern "C" int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const
     }
     *out = nullptr;
     *out_bytes = 0;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     u64 total = 0;
     int rc;
     if ((rc = gather_scan(h, order, n, &total))) return rc;
@@ -1158,12 +1053,12 @@ extern "C" int kw_sort_gather(kw_sort *h, const int64_t *order, int64_t n, const
         h->err = "kw_sort_gather: the body holds " + std::to_string(total) + " bytes";
         return KW_EOVERFLOW;
     }
-    if ((rc = ensure(h, h->out, (size_t)total + 32)) ||
-        (rc = ensure_pinned(h, &h->h_out, &h->h_out_cap, (size_t)total + 16)) ||
+    if ((rc = fit(h, h->out, (size_t)total + 32)) ||
+        (rc = fit_pinned(h, &h->h_out, &h->h_out_cap, (size_t)total + 16)) ||
         (rc = gather_range(h, n, 0, total, h->out.p, h->h_out)))
         return rc;
-    KSCHK(h, hipStreamSynchronize(h->stream));
-    KSCHK(h, hipGetLastError());
+    KWCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipGetLastError());
     if ((rc = gather_times(h))) return rc;
     *out = (const uint8_t *)h->h_out;
     *out_bytes = (int64_t)total;
@@ -1185,13 +1080,13 @@ extern "C" int kw_sort_gather_begin(kw_sort *h, const int64_t *order, int64_t n,
         return KW_EINVAL;
     }
     *total_bytes = *n_slabs = 0;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     u64 total = 0;
     int rc;
     if ((rc = gather_scan(h, order, n, &total))) return rc;
     for (int s = 0; s < 2; ++s)
-        if ((rc = ensure(h, h->slab[s], (size_t)slab_bytes + 32)) ||
-            (rc = ensure_pinned(h, &h->h_slab[s], &h->h_slab_cap[s], (size_t)slab_bytes)))
+        if ((rc = fit(h, h->slab[s], (size_t)slab_bytes + 32)) ||
+            (rc = fit_pinned(h, &h->h_slab[s], &h->h_slab_cap[s], (size_t)slab_bytes)))
             return rc;
     h->g_n = n;
     h->g_total = total;
@@ -1218,7 +1113,7 @@ extern "C" int kw_sort_gather_slab(kw_sort *h, int64_t k, const uint8_t **out, i
     }
     *out = nullptr;
     *out_bytes = 0;
-    KSCHK(h, hipSetDevice(h->device));
+    KWCHK(h, hipSetDevice(h->device));
     const u64 sb = (u64)h->slab_bytes;
     auto hi_of = [&](long long j) { return (u64)(j + 1) * sb < h->g_total ? (u64)(j + 1) * sb : h->g_total; };
     int rc;
@@ -1226,14 +1121,14 @@ extern "C" int kw_sort_gather_slab(kw_sort *h, int64_t k, const uint8_t **out, i
     const int slot = 1 - h->last_slot;
     if (h->pre_k != k) {
         if (h->pre_k >= 0) {   // (another one is under way into this slab)
-            KSCHK(h, hipStreamSynchronize(h->stream));
+            KWCHK(h, hipStreamSynchronize(h->stream));
             if ((rc = gather_times(h))) return rc;
         }
         if ((rc = gather_range(h, h->g_n, (u64)k * sb, hi_of(k), h->slab[slot].p, h->h_slab[slot]))) return rc;
     }
     h->pre_k = -1;
-    KSCHK(h, hipStreamSynchronize(h->stream));
-    KSCHK(h, hipGetLastError());
+    KWCHK(h, hipStreamSynchronize(h->stream));
+    KWCHK(h, hipGetLastError());
     if ((rc = gather_times(h))) return rc;
     *out = (const uint8_t *)h->h_slab[slot];
     *out_bytes = (int64_t)(hi_of(k) - (u64)k * sb);

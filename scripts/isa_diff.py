@@ -5,8 +5,8 @@
 
 Every ``.hip`` unit of ``advanced_scrapper_amd/csrc`` is compiled device-only to assembly with the library's
 build flags, once from an export of <git-rev> and once from the working tree.  The assembly is normalised
-(comments from ``;`` to end of line, trailing blanks, empty lines and the source-hash ``__hip_cuid_`` symbol
-are dropped) and compared function by function.  A refactor that claims "same code" shows every unit
+(comments from ``;`` to end of line, trailing blanks, empty lines, the source-hash ``__hip_cuid_`` symbol and
+the function ordinal inside local labels are dropped) and compared function by function.  A refactor that claims "same code" shows every unit
 identical; anything else lists the kernels that differ with their register, scratch and LDS figures before
 and after and the head of a unified diff.  Exit status 1 if any unit differs.  Needs hipcc, no GPU.
 """
@@ -23,8 +23,11 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join('advanced_scrapper_amd', 'csrc')
-JOBS = 8            # compiles in flight (two trees x five units today); never sized by the machine
+JOBS = 8            # compiles in flight (two trees x every unit); never sized by the machine
 DIFF_LINES = 60     # "a screenful" of unified diff per kernel
+# a block or function-end label carries its function's ordinal in the unit (.LBB7_3): a kernel that leaves or joins
+# a unit renumbers every function after it, so the ordinal is dropped (the label stays unique inside its function)
+LOCAL_LABEL = re.compile(r'(\.L(?:BB|func_begin|func_end|JTI))\d+')
 FIGURES = ('.vgpr_count', '.sgpr_count', '.private_segment_fixed_size', '.group_segment_fixed_size')
 
 
@@ -58,7 +61,7 @@ def normalise(asm: str) -> list[str]:
     for line in asm.splitlines():
         line = line.split(';', 1)[0].rstrip()
         if line and '__hip_cuid_' not in line:
-            out.append(line)
+            out.append(LOCAL_LABEL.sub(r'\1', line))
     return out
 
 
